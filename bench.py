@@ -31,10 +31,15 @@ and `dist.reduce_ciphertexts` sums one ciphertext per GPU on rank 0 inside the t
 `--gpus N --dry-run` validates the launch environment and prints the per-rank shapes without touching a GPU.
 
 Timing: W warmup steps, then untimed steps for about `--settle-ms` (150 ms: the shader clock settles under the package power
-cap these kernels run at; the count is agreed between the ranks and reported as `settle_steps`), then `--repeats` R (5) timed
-regions of EXACTLY K steps each, every region between two barriers (+ torch.cuda.synchronize) and MAX-reduced over the ranks:
-`value` / `ms_per_step` are the MEDIAN region, `values` lists all R and `spread` = (slowest - fastest) / median.  At N = 1 an untimed leg after the measurement samples `rocm-smi` while the steps keep running (`power`:
+cap these kernels run at; the count is agreed between the ranks and reported as `settle_steps`), then EXACTLY K timed steps,
+split into R = min(`--repeats` (5), K) consecutive regions of K / R steps (sizes differing by at most one), every region between
+two barriers (+ torch.cuda.synchronize) and MAX-reduced over the ranks: `ms_per_step` is the MEDIAN region's time per step and
+`value` the rate at it, `values` lists all R rates and `spread` = (slowest - fastest) / median.  At N = 1 an untimed leg after the measurement samples `rocm-smi` while the steps keep running (`power`:
 package watts, shader clock, cap; `--no-power` skips it).
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's share) as DIR/<name>.npy, float32, at most 64 MB in all
+(dump_outputs).  The inputs come from fixed seeds: the same arguments give the same inputs on every run, so two builds can be
+compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -58,7 +63,7 @@ HBM_BYTES = 288 * 10**9
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps of the measured workload in all (split into --repeats regions)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=4096, help="ciphertext pairs (or polynomials for --workload ntt) per GPU per step; "
                     "pir: database columns (and rows unless --pir-rows)")
@@ -80,9 +85,9 @@ def parse(argv=None):
                     "key (item i belongs to client i %% keys -- interleaved, the order a batching server sees): the per-key entry point "
                     "hipbfv_batch_multiply_relin_keys; --keys = --batch is SURVEY 8d config 3's per-ciphertext-key worst case, where the key "
                     "(16 K (K+1) N bytes) is part of every item's compulsory traffic")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of exactly --steps steps each (every one between two barriers); value = the "
-                    "MEDIAN region, all of them are printed (`values`, `spread`): one box differs from the next by 2-3 %, a claim smaller than "
-                    "the spread of its own repeats is noise")
+    ap.add_argument("--repeats", type=int, default=5, help="timed regions the --steps steps are split into (every one between two barriers; at most "
+                    "one per step); value = the MEDIAN region, all of them are printed (`values`, `spread`): one box differs from the next by "
+                    "2-3 %%, a claim smaller than the spread of its own repeats is noise")
     ap.add_argument("--chunk", type=int, default=0, help="override the executor's chunk size (ops per launch group)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="ops in the CPU-baseline sample (0 = auto)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -103,7 +108,13 @@ def parse(argv=None):
     ap.add_argument("--check-sets", type=int, default=8, help="chi_sq / dot_prod: input sets compared bit for bit with the oracle's graph interpreter")
     ap.add_argument("--gather", action="store_true", help="N>1: also time one gather of the result batch to rank 0 (reported as result_gather_ms, never part of value)")
     ap.add_argument("--dry-run", action="store_true", help="validate the launch environment, per-rank shapes and HBM footprint for --gpus N and exit (no GPU needed)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last one computed (rank 0's share of the "
+                    "measured workload; not the secondary workloads) as DIR/<name>.npy: every 64-bit word as its 8 little-endian bytes in float32, "
+                    "a fixed seeded sample of the words where the whole output would exceed 64 MB (dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -357,6 +368,35 @@ def kernel_source_hash() -> str:
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT = 64 << 20  # bytes of all the .npy files --dump-outputs writes
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array of {name: int64 tensor} as outdir/<name>.npy.  The words are u64 residues (or integers), which
+    float64 would round above 2^53: each is written as its 8 little-endian bytes in float32 (a trailing axis of 8), so the file is
+    exact and a one-bit difference between two builds is a difference of at least 1 in a value below 256.  An array whose words do
+    not fit its share of 3/4 of DUMP_LIMIT is replaced by a fixed sample of them (flattened; DUMP_SEED, sorted indices: the same
+    words on every run with the same arguments).  Returns {name: shape written}."""
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_LIMIT * 3 // 4 // len(arrays) // 32  # words per array; 8 float32 = 32 bytes each
+    rng = np.random.default_rng(DUMP_SEED)
+    shapes, total = {}, 0
+    for name, x in arrays.items():
+        if x.numel() > share:
+            idx = np.unique(rng.integers(0, x.numel(), share))
+            x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+        w = np.ascontiguousarray(x.cpu().numpy(), dtype="<i8")
+        b = w.view(np.uint8).reshape(w.shape + (8,)).astype(np.float32)
+        total += b.nbytes
+        assert total <= DUMP_LIMIT, total
+        np.save(os.path.join(outdir, name + ".npy"), b)
+        shapes[name] = list(b.shape)
+    return shapes
+
+
 def measure(args, env: Env, secondary: bool = False):
     """Run ONE workload: W warm-up steps, K timed steps between barriers, parity gate, roofline, CPU baseline.
     Returns the JSON object on rank 0, None on the other ranks."""
@@ -446,6 +486,9 @@ def measure(args, env: Env, secondary: bool = False):
         def step():
             ev.multiply_relin_keys(a, b, rk_sets, key_index, out=out)
 
+        def results():
+            return {"ciphertexts": out}
+
         key_bytes = 16 * K * KK * n
         # SURVEY 8(d) + the keys that are now compulsory: read 2 ciphertexts, write 1, and every DISTINCT key of the step once
         unit_bytes = 48 * K * n + key_bytes * nkeys // B
@@ -468,6 +511,9 @@ def measure(args, env: Env, secondary: bool = False):
         def step():
             ev.multiply_relin(a, b, rkd, out=out)
 
+        def results():
+            return {"ciphertexts": out}
+
         unit_bytes = 48 * K * n  # read 2 ciphertexts, write 1 (compulsory HBM traffic per op)
         units_per_step = B
         metric, unit = "bfv_mul_relin_ops_per_sec", "ops/s"
@@ -485,6 +531,9 @@ def measure(args, env: Env, secondary: bool = False):
             prod = ev.multiply_relin(ca, cb, rkd)
             holder["ct"] = prod
             holder["out"] = ev.decode(ev.decrypt(prod, skd))
+
+        def results():
+            return {"decoded": holder["out"]}
 
         unit_bytes = 32 * n + 8 * n  # compulsory: read two slot vectors, write one
         units_per_step = B
@@ -543,6 +592,9 @@ def measure(args, env: Env, secondary: bool = False):
             # rows of this shard -> one partial ciphertext; one ciphertext per GPU summed on rank 0 (SURVEY 8e "Exception")
             holder["out"] = D.reduce_ciphertexts(run_shard(), ev.add, 0)
 
+        def results():
+            return {"answer": holder["out"]}
+
         exchange = f"gather(dst=0) of one ciphertext per rank ({2 * K * n * 8} B) + {world - 1} additions on rank 0, inside every timed step" if world > 1 else None
         unit_bytes = 8 * K * n  # compulsory traffic per database entry: its transform-domain residues, read once
         units_per_step = (hi - lo) * cols
@@ -577,6 +629,9 @@ def measure(args, env: Env, secondary: bool = False):
         def step():
             outs_holder[:] = prog.run(ev, ins, rkd, gkd)
 
+        def results():
+            return {f"output{k}": x for k, x in enumerate(outs_holder)}
+
         nout = prog.num_outputs()
         unit_bytes = 16 * K * n * (nin + nout)  # compulsory traffic of one program run: read the inputs, write the outputs
         units_per_step = B
@@ -594,6 +649,9 @@ def measure(args, env: Env, secondary: bool = False):
         def step():
             ev.ntt(data, nprimes, inverse=False)
             ev.ntt(data, nprimes, inverse=True)
+
+        def results():
+            return {"polys": data}
 
         unit_bytes = 16 * n  # one single-residue transform: read + write
         units_per_step = 2 * B * nprimes
@@ -629,18 +687,19 @@ def measure(args, env: Env, secondary: bool = False):
         for _ in range(more):
             step()
         settle_steps = args.warmup + more
-    # R timed regions of EXACTLY K steps each, every one bracketed by a barrier + torch.cuda.synchronize() on both sides and
-    # reduced with MAX over the ranks; the line reports the MEDIAN region (`values` lists them all).  The HIP-event kernel
-    # times accumulate over all R regions.
-    repeats = max(1, args.repeats)
-    regions = []
+    # EXACTLY K timed steps in R = min(--repeats, K) consecutive regions (sizes differ by at most one step), every one bracketed by
+    # a barrier + torch.cuda.synchronize() on both sides and reduced with MAX over the ranks; the line reports the MEDIAN region's
+    # time per step (`values` lists them all).  The HIP-event kernel times accumulate over all K steps.
+    repeats = max(1, min(args.repeats, args.steps))
+    sizes = [args.steps // repeats + (1 if i < args.steps % repeats else 0) for i in range(repeats)]
+    regions = []  # seconds per step of each region
     barrier()
     ev.profile(not args.no_kernel_events)
     ev.profile_reset()
-    for _ in range(repeats):
+    for k in sizes:
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k):
             step()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
@@ -649,10 +708,14 @@ def measure(args, env: Env, secondary: bool = False):
             tt = torch.tensor([el], dtype=torch.float64, device=cdev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
-        regions.append(el)
+        regions.append(el / k)
     prof = ev.profile_read()
     ev.profile(False)
-    elapsed = sorted(regions)[len(regions) // 2] if len(regions) % 2 else sum(sorted(regions)[len(regions) // 2 - 1 : len(regions) // 2 + 1]) / 2
+    step_s = sorted(regions)[len(regions) // 2] if len(regions) % 2 else sum(sorted(regions)[len(regions) // 2 - 1 : len(regions) // 2 + 1]) / 2
+
+    dumped = None
+    if args.dump_outputs and not secondary and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, results())
 
     # ---- optional result gather (only if the consumer wants every result on one device), timed apart ----
     gather_ms = None
@@ -787,8 +850,7 @@ def measure(args, env: Env, secondary: bool = False):
     if rank != 0:
         return None
 
-    total_units = total_items * args.steps  # every rank's units of every timed step
-    value = total_units / elapsed
+    value = total_items / step_s  # every rank's units of one timed step
     # dominant kernel by accumulated HIP-event time
     dom = max(prof.items(), key=lambda kv: kv[1]["ms"]) if prof else None
     roofline = None
@@ -827,7 +889,7 @@ def measure(args, env: Env, secondary: bool = False):
         # SURVEY 8(d) ALGORITHMIC bytes: the per-unit compulsory figure x the units ONE launch of this kernel processes.
         # A unit is one op / program run / database entry (the dominant kernel sees this rank's units / launches of them per
         # launch); for the transform workload the unit is one single-residue transform = the kernel's own work unit.
-        units_per_launch = rec["units"] / rec["launches"] if args.workload == "ntt" else units_per_step * args.steps * repeats / rec["launches"]
+        units_per_launch = rec["units"] / rec["launches"] if args.workload == "ntt" else units_per_step * args.steps / rec["launches"]
         achieved = unit_bytes * units_per_launch / (avg_ms * 1e-3) / 1e9
         # measured HBM bytes per launch and VALU issue occupancy from the committed PMC profile of THIS workload
         # (FETCH_SIZE x2 + WRITE_SIZE, SQ_INSTS_VALU*, GRBM_GUI_ACTIVE in separate rocprofv3 --pmc passes:
@@ -897,9 +959,9 @@ def measure(args, env: Env, secondary: bool = False):
         "warmup": args.warmup,
         "settle_steps": settle_steps,
         "repeats": repeats,
-        "values": [round(total_units / r, 2) for r in regions],
-        "spread": round((max(regions) - min(regions)) / elapsed, 4),
-        "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "values": [round(total_items / r, 2) for r in regions],
+        "spread": round((max(regions) - min(regions)) / step_s, 4),
+        "ms_per_step": round(1e3 * step_s, 3),
         "higher_is_better": True,
         "scaling": scaling_of(args),
         "vs_baseline": None,
@@ -913,7 +975,7 @@ def measure(args, env: Env, secondary: bool = False):
         "valu": valu,
         "whole_op_hbm": {"algorithmic_bytes_per_unit": unit_bytes, "achieved_GBps_per_gpu": round(op_rate_gbs, 1),
                          "frac_of_peak": round(op_rate_gbs / HBM_PEAK_GBS, 4)},
-        "kernels_ms_per_step": {k: round(v["ms"] / (args.steps * repeats), 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
+        "kernels_ms_per_step": {k: round(v["ms"] / args.steps, 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
         "kernel_units_per_launch": {k: v["units"] / v["launches"] for k, v in prof.items()},
         "cpu_baseline": cpu,
         "parity": parity,
@@ -931,6 +993,8 @@ def measure(args, env: Env, secondary: bool = False):
         line["config"]["exchange"] = exchange
     if gather_ms is not None:
         line["result_gather_ms"] = round(gather_ms, 3)
+    if dumped is not None:
+        line["outputs_dumped"] = dumped
     return line
 
 
@@ -953,7 +1017,7 @@ def main():
         jobs = [
             # the other two quantities of the metric
             ("mulrelin_n16384", dict(n=16384, batch=q4, total_batch=args.total_batch // 4)),
-            ("ntt_n8192", dict(workload="ntt", steps=max(args.steps, 100))),  # a step is 0.7 ms: time at least 70 ms per region
+            ("ntt_n8192", dict(workload="ntt", steps=max(args.steps, 100 * max(args.repeats, 1)))),  # a step is 0.7 ms: time at least 70 ms per region
             # the north star's literal prime set ("n=8192, 3 x 54-bit RNS primes")
             ("mulrelin_n8192_bits54-54-54-56", dict(coeff_bits="54,54,54,56")),
         ]

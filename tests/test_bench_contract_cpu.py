@@ -127,6 +127,32 @@ def test_power_leg_parses_rocm_smi_and_survives_its_absence(tmp_path, monkeypatc
     assert bench.power_leg(lambda: None, lambda: None) is None
 
 
+def test_dump_outputs_is_exact_bounded_and_the_same_sample_every_run(tmp_path):
+    """--dump-outputs: 64-bit words come back bit for bit from their float32 bytes, the files stay within 64 MB however large the
+    output, and a sampled output is the same words on every run."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = torch.tensor([[0, 1, (1 << 62) - 1], [1125899906826240, 255, 1 << 40]], dtype=torch.int64)
+    big = torch.randint(0, 1 << 60, (5_000_000,), dtype=torch.int64, generator=torch.Generator().manual_seed(3))
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big})
+    assert shapes["small"] == [2, 3, 8] and shapes["big"][1] == 8 and shapes["big"][0] < big.numel()
+    total = 0
+    for name in ("small", "big"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and list(a.shape) == shapes[name] and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 << 20
+    words = np.load(tmp_path / "a" / "small.npy").astype(np.uint8).view("<i8")[..., 0]
+    assert np.array_equal(words, small.numpy())
+    sampled = np.load(tmp_path / "a" / "big.npy").astype(np.uint8).view("<i8")[:, 0]
+    assert np.isin(sampled, big.numpy()).all()
+
+
 def test_default_line_is_compact_and_ends_in_the_summary_of_every_metric_quantity():
     """The driver stores the TAIL of the printed line (2000 characters): the last key is `summary`, it carries the three quantities
     BASELINE.json's metric names (mul+relin at n = 8192 and 16384, NTTs/s), the per-key worst cases and the program workloads, and the
