@@ -290,7 +290,16 @@ long hipbfv_wire_decode_plaintext(const uint8_t *in, uint64_t in_size, uint8_t *
                                   uint64_t *coeffs, uint64_t capacity_words, int64_t *in_bytes);
 
 /* Batched entry points: device pointers, `count` independent ciphertexts u64[count][size][K][N],
- * enqueued asynchronously on `stream` (a hipStream_t; NULL = default stream). */
+ * enqueued asynchronously on `stream` (a hipStream_t; NULL = default stream).
+ *
+ * Aliasing.  An output may be EXACTLY one of the inputs (the same pointer) when it has the same number of words per item as
+ * that input: add(a, b, out = a), multiply_relin(a, a, out = a), rotate_rows(ct, steps, out = ct) and the like.  Any other
+ * overlap between an output range and any input range is HIPBFV_E_INVALIDARG, and nothing is launched.  The ranges are
+ * [ptr, ptr + count * words_per_item) (a plaintext operand: its plaintext width, one item when shared).  So the calls whose
+ * output is wider or narrower than their input (multiply 2 + 2 -> 3 polynomials, relinearize 3 -> 2, mod_switch K -> K-1) take
+ * no in-place form, and an output shifted against its input by any amount is refused.  The transforms either side of the
+ * evaluator (encode, decode, decrypt, encrypt, plain_to_ntt, ct_to_ntt, dot_plain_ntt) accept no overlap at all.
+ * hipbfv_batch_ntt works in place by definition. */
 long hipbfv_batch_multiply(void *evaluator, const uint64_t *a, uint64_t size_a, const uint64_t *b, uint64_t size_b,
                            uint64_t *out, uint64_t count, void *stream);
 long hipbfv_batch_relinearize(void *evaluator, const uint64_t *ct3, void *relin_keys, uint64_t *out2, uint64_t count,
@@ -308,10 +317,15 @@ long hipbfv_batch_rotate_columns(void *evaluator, const uint64_t *ct2, void *gal
  * runtime.rs:310-327), so a server that batches the calls of many clients holds one key set per client.  These are the
  * three key-switching operations above with `num_key_sets` key handles (RelinearizationKeys resp. GaloisKeys objects of the
  * evaluator's context) and, per item, the set it uses: key_index is a HOST array of `count` entries < num_key_sets, read
- * before the call returns.  Item i gives the bits of the single-key call with key_sets[key_index[i]].  Items need not be
- * grouped by key: the key-switch kernel walks them in key order, so items of one client share that client's key rows in
- * one XCD's L2; with one key set per item the key (16 K (K+1) N bytes) is part of every item's compulsory traffic.
- * rotate_rows_keys follows SEAL's rotate_internal: the direct key when EVERY set holds it, the NAF chain otherwise. */
+ * before the call returns.  Item i gives the bits of the single-key call with key_sets[key_index[i]], whoever else is in the
+ * batch.  Only the REFERENCED sets (those key_index names) are validated and read: an unreferenced entry may be NULL, a set
+ * without the key or a key object of another context.  A referenced set without the key fails as the single-key call does
+ * (HIPBFV_E_INVALIDARG before anything is launched; hipbfv_last_error names the set).  rotate_rows_keys decides per set, as
+ * SEAL's rotate_internal does for one set: the direct Galois key when that set holds it, the NAF chain of power-of-two keys
+ * otherwise (a set with neither lacks the key); when the referenced sets decide differently the two groups run apart.
+ * Items need not be grouped by key: the key-switch kernel walks them in key order, so items of one client share that
+ * client's key rows in one XCD's L2; with one key set per item the key (16 K (K+1) N bytes) is part of every item's
+ * compulsory traffic. */
 long hipbfv_batch_relinearize_keys(void *evaluator, const uint64_t *ct3, void *const *relin_key_sets, uint64_t num_key_sets,
                                    const uint32_t *key_index, uint64_t *out2, uint64_t count, void *stream);
 long hipbfv_batch_multiply_relin_keys(void *evaluator, const uint64_t *a, const uint64_t *b, void *const *relin_key_sets,
@@ -443,7 +457,11 @@ long hipbfv_Program_Run(void *program, void *evaluator, uint64_t batch, uint64_t
 
 /* Run with one key set per client: input set i of the batch uses relin_keys[key_index[i]] / galois_keys[key_index[i]]
  * (HOST arrays: num_key_sets handles each -- an entry may be NULL when the program needs no such key -- and `batch`
- * indices).  Same bits per input set as hipbfv_Program_Run with that set's keys (the reference's call, run.rs:100-105). */
+ * indices).  Same bits per input set as hipbfv_Program_Run with that set's keys alone (the reference's call,
+ * run.rs:100-105), whoever else is in the batch.  Only the referenced sets count, as in the per-key batches above: an
+ * unreferenced entry may be anything, a referenced handle that is not a key object of the evaluator's context is
+ * HIPBFV_E_INVALIDARG (naming the set).  Input sets whose key sets hold different kinds of keys (a relinearisation key or
+ * not, which Galois elements) run as separate runs, one per kind, gathered and scattered through scratch buffers. */
 long hipbfv_Program_RunKeys(void *program, void *evaluator, uint64_t batch, uint64_t num_inputs, const uint32_t *input_kinds,
                             const uint64_t *const *input_ptrs, const uint64_t *input_strides, uint64_t num_key_sets,
                             void *const *relin_keys, void *const *galois_keys, const uint32_t *key_index,

@@ -37,6 +37,11 @@ def _stream():
 
 
 class BatchEvaluator:
+    """`out=`: an output may be exactly one of the inputs (the same tensor) when it has that input's shape -- add(a, b, out=a),
+    multiply_relin(a, a, out=a), rotate_rows(ct, s, gk, out=ct).  Any other overlap between an output and an input (a shifted
+    view of the same storage, an output of another width such as multiply(a, b, out=a), relinearize(ct3, rk, out=ct3)) is
+    refused with HipBfvError (InvalidArgument) before anything is launched (include/hipbfv.h, "Aliasing")."""
+
     def __init__(self, ctx: Context):
         self.ctx = ctx
         self._ev = BFVEvaluator(ctx)
@@ -131,13 +136,15 @@ class BatchEvaluator:
     # ---- per-key batches (multi-tenant: the reference passes the keys per call, sunscreen_runtime/src/run.rs:100-105) ----
     @staticmethod
     def _key_sets(key_sets, key_index, count: int):
-        handles = (C.c_void_p * len(key_sets))(*[k.get_handle() for k in key_sets])
+        # a None entry is a NULL handle: allowed for a set no item names (only the sets key_index names are read)
+        handles = (C.c_void_p * len(key_sets))(*[k.get_handle() if k is not None else None for k in key_sets])
         idx = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint32))
         assert idx.shape == (count,), (idx.shape, count)
         return handles, len(key_sets), idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx
 
     def relinearize_keys(self, ct3: torch.Tensor, key_sets: Sequence[RelinearizationKeys], key_index, out: torch.Tensor | None = None) -> torch.Tensor:
-        """Item i is relinearised with key_sets[key_index[i]] (key_index: `count` host integers)."""
+        """Item i is relinearised with key_sets[key_index[i]] (key_index: `count` host integers).  Only the sets key_index names
+        are read: the others may be None or lack the key."""
         self._shape_ok(ct3, 3)
         out = out if out is not None else self._new(ct3.shape[0], 2, ct3)
         hs, n, ip, _keep = self._key_sets(key_sets, key_index, ct3.shape[0])

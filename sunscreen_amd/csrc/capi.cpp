@@ -11,6 +11,7 @@
 
 #include <cerrno>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -1651,15 +1652,42 @@ static const u64* key_or_null(void* keys, EvalObj* e, u32 index) {
   return k->find(index);
 }
 
+// ---- the aliasing rule of the batched entry points (include/hipbfv.h, "Aliasing") ----
+// An operand: `items` items of `width` u64 words, `stride` words apart (stride 0: one item shared by the whole batch).
+struct Span {
+  const void* p;
+  size_t width, stride, items;
+  size_t words() const { return !p || !items ? 0 : (stride ? (items - 1) * stride + width : width); }
+};
+static Span cts(const void* p, size_t width, size_t items) { return Span{p, width, width, items}; }
+
+// E_INVALIDARG unless every input is disjoint from the output or (exact_ok) IS the output: the same pointer and the same
+// width per item.  Checked before anything is launched; an O(1) interval test per operand.
+static long check_alias(const Span& out, std::initializer_list<Span> ins, bool exact_ok = true) {
+  const uintptr_t o0 = (uintptr_t)out.p, o1 = o0 + out.words() * sizeof(u64);
+  for (const Span& in : ins) {
+    const uintptr_t i0 = (uintptr_t)in.p, i1 = i0 + in.words() * sizeof(u64);
+    if (i0 == i1 || o0 == o1 || i1 <= o0 || o1 <= i0) continue;
+    if (exact_ok && i0 == o0 && in.width == out.width && in.stride == out.stride && in.items == out.items) continue;
+    return fail(HIPBFV_E_INVALIDARG, "an output buffer overlaps an input buffer other than as exactly that buffer (include/hipbfv.h: aliasing)");
+  }
+  return HIPBFV_S_OK;
+}
+#define ALIAS_OR_RETURN(...) \
+  if (long hr__ = check_alias(__VA_ARGS__)) return hr__;
+
 long hipbfv_batch_multiply(void* h, const uint64_t* a, uint64_t sa, const uint64_t* b, uint64_t sb, uint64_t* out, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!a || !b || !out) return HIPBFV_E_POINTER;
+  const Context& c = *e->ctx;
+  ALIAS_OR_RETURN(cts(out, c.ct_words(sa && sb ? sa + sb - 1 : 0), count), {cts(a, c.ct_words(sa), count), cts(b, c.ct_words(sb), count)});
   return from_status(e->ev->multiply((const u64*)a, (u32)sa, (const u64*)b, (u32)sb, (u64*)out, count, (hipStream_t)stream));
 HIPBFV_END
 
 long hipbfv_batch_relinearize(void* h, const uint64_t* ct3, void* keys, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!ct3 || !out2) return HIPBFV_E_POINTER;
+  ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct3, e->ctx->ct_words(3), count)});
   const u64* rk = key_or_null(keys, e, 0);
   if (!rk) return from_status(kNoKey);
   return from_status(e->ev->relinearize((const u64*)ct3, rk, (u64*)out2, count, (hipStream_t)stream));
@@ -1668,6 +1696,8 @@ HIPBFV_END
 long hipbfv_batch_multiply_relin(void* h, const uint64_t* a, const uint64_t* b, void* keys, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!a || !b || !out2) return HIPBFV_E_POINTER;
+  const size_t w = e->ctx->ct_words(2);
+  ALIAS_OR_RETURN(cts(out2, w, count), {cts(a, w, count), cts(b, w, count)});
   const u64* rk = key_or_null(keys, e, 0);
   if (!rk) return from_status(kNoKey);
   return from_status(e->ev->multiply_relin((const u64*)a, (const u64*)b, rk, (u64*)out2, count, (hipStream_t)stream));
@@ -1677,6 +1707,7 @@ long hipbfv_batch_apply_galois(void* h, const uint64_t* ct2, uint32_t elt, void*
   EVAL_OR_RETURN(h);
   if (!ct2 || !out2) return HIPBFV_E_POINTER;
   if (!(elt & 1) || elt >= 2 * e->ctx->n()) return from_status(kInvalidArg);
+  ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct2, e->ctx->ct_words(2), count)});
   const u64* key = key_or_null(keys, e, (elt - 1) >> 1);
   if (!key) return from_status(kNoKey);
   return from_status(e->ev->apply_galois((const u64*)ct2, elt, key, (u64*)out2, count, (hipStream_t)stream));
@@ -1712,6 +1743,7 @@ long hipbfv_batch_rotate_rows(void* h, const uint64_t* ct2, int steps, void* key
   EVAL_OR_RETURN(h);
   if (!ct2 || !out2) return HIPBFV_E_POINTER;
   if (!e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
+  ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct2, e->ctx->ct_words(2), count)});
   hipStream_t s = (hipStream_t)stream;
   if (steps == 0) {
     if ((const u64*)ct2 != (u64*)out2 &&
@@ -1729,13 +1761,36 @@ long hipbfv_batch_rotate_columns(void* h, const uint64_t* ct2, void* keys, uint6
 HIPBFV_END
 
 // ---- per-key batches: item i of the batch uses key set key_index[i] (include/hipbfv.h) ----
-// the key `index` (0 = relinearisation, (elt - 1) / 2 = Galois) of every set, as the evaluator's per-item selection; `tab` keeps
-// the pointer table alive for the call.  !present(): a handle is not a key object of this context, or a set lacks the key.
+// Only the sets key_index names are validated and read: a set no item names may be NULL, lack the key or belong to another
+// context.  `used[k]`: set k is named by one of the first `count` entries.
+static std::vector<char> referenced_sets(const uint32_t* key_index, uint64_t count, uint64_t num_sets) {
+  std::vector<char> used(num_sets, 0);
+  for (uint64_t i = 0; i < count; i++) used[key_index[i]] = 1;
+  return used;
+}
+static long no_key_in_set(uint64_t set) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "key set %llu (named by key_index) does not hold the required key-switching key", (unsigned long long)set);
+  return fail(HIPBFV_E_INVALIDARG, msg);
+}
+// the key `index` (0 = relinearisation, (elt - 1) / 2 = Galois) of every referenced set, as the evaluator's per-item selection;
+// `tab` keeps the pointer table alive for the call, and its unreferenced slots repeat a referenced key (never read).
+// !present(): a referenced handle is not a key object of this context, or lacks the key -- *missing names the first such set.
 static KeySel keys_sel(void* const* key_sets, uint64_t num_sets, const uint32_t* key_index, uint64_t count, EvalObj* e, u32 index,
-                       std::vector<const u64*>& tab) {
+                       std::vector<const u64*>& tab, uint64_t* missing = nullptr) {
+  const std::vector<char> used = referenced_sets(key_index, count, num_sets);
   tab.assign(num_sets, nullptr);
-  for (uint64_t k = 0; k < num_sets; k++)
-    if (!(tab[k] = key_or_null(key_sets[k], e, index))) return KeySel();
+  const u64* any = nullptr;
+  for (uint64_t k = 0; k < num_sets; k++) {
+    if (!used[k]) continue;
+    if (!(tab[k] = key_or_null(key_sets[k], e, index))) {
+      if (missing) *missing = k;
+      return KeySel();
+    }
+    any = tab[k];
+  }
+  for (auto& t : tab)
+    if (!t) t = any;
   KeySel sel;
   sel.keys = tab.data();
   sel.nkeys = (u32)num_sets;
@@ -1747,16 +1802,20 @@ static KeySel keys_sel(void* const* key_sets, uint64_t num_sets, const uint32_t*
   if (!key_sets || !key_index || !num_sets || num_sets > 0xFFFFFFFFull) return HIPBFV_E_POINTER; \
   for (uint64_t i__ = 0; i__ < count; i__++)                                                  \
     if (key_index[i__] >= num_sets) return fail(HIPBFV_E_INVALIDARG, "key_index names a key set that was not given");
+#define KEYSEL_OR_RETURN(sel, index)                                                 \
+  std::vector<const u64*> tab;                                                       \
+  uint64_t missing = 0;                                                              \
+  const KeySel sel = keys_sel(key_sets, num_sets, key_index, count, e, index, tab, &missing); \
+  if (!sel.present()) return no_key_in_set(missing);
 
 long hipbfv_batch_relinearize_keys(void* h, const uint64_t* ct3, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
                                    uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!ct3 || !out2) return HIPBFV_E_POINTER;
   KEYSETS_OR_RETURN();
+  ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct3, e->ctx->ct_words(3), count)});
   if (!count) return HIPBFV_S_OK;
-  std::vector<const u64*> tab;
-  const KeySel sel = keys_sel(key_sets, num_sets, key_index, count, e, 0, tab);
-  if (!sel.present()) return from_status(kNoKey);
+  KEYSEL_OR_RETURN(sel, 0);
   return from_status(e->ev->relinearize((const u64*)ct3, sel, (u64*)out2, count, (hipStream_t)stream));
 HIPBFV_END
 
@@ -1765,10 +1824,10 @@ long hipbfv_batch_multiply_relin_keys(void* h, const uint64_t* a, const uint64_t
   EVAL_OR_RETURN(h);
   if (!a || !b || !out2) return HIPBFV_E_POINTER;
   KEYSETS_OR_RETURN();
+  const size_t w = e->ctx->ct_words(2);
+  ALIAS_OR_RETURN(cts(out2, w, count), {cts(a, w, count), cts(b, w, count)});
   if (!count) return HIPBFV_S_OK;
-  std::vector<const u64*> tab;
-  const KeySel sel = keys_sel(key_sets, num_sets, key_index, count, e, 0, tab);
-  if (!sel.present()) return from_status(kNoKey);
+  KEYSEL_OR_RETURN(sel, 0);
   return from_status(e->ev->multiply_relin((const u64*)a, (const u64*)b, sel, (u64*)out2, count, (hipStream_t)stream));
 HIPBFV_END
 
@@ -1778,22 +1837,15 @@ long hipbfv_batch_apply_galois_keys(void* h, const uint64_t* ct2, uint32_t elt, 
   if (!ct2 || !out2) return HIPBFV_E_POINTER;
   if (!(elt & 1) || elt >= 2 * e->ctx->n()) return from_status(kInvalidArg);
   KEYSETS_OR_RETURN();
+  ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct2, e->ctx->ct_words(2), count)});
   if (!count) return HIPBFV_S_OK;
-  std::vector<const u64*> tab;
-  const KeySel sel = keys_sel(key_sets, num_sets, key_index, count, e, (elt - 1) >> 1, tab);
-  if (!sel.present()) return from_status(kNoKey);
+  KEYSEL_OR_RETURN(sel, (elt - 1) >> 1);
   return from_status(e->ev->apply_galois((const u64*)ct2, elt, sel, (u64*)out2, count, (hipStream_t)stream));
 HIPBFV_END
 
-// SEAL's rotate_internal over per-item key sets: the direct key when EVERY set has it, the NAF chain otherwise
-static long batch_rotate_keys_internal(EvalObj* e, const u64* in, int steps, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
-                                       u64* out, uint64_t count, hipStream_t s) {
-  if (steps == 0) return HIPBFV_S_OK;
-  const u32 elt = e->ev->galois_elt_from_step(steps);
-  if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
-  std::vector<const u64*> tab;
-  if (const KeySel sel = keys_sel(key_sets, num_sets, key_index, count, e, (elt - 1) >> 1, tab); sel.present())
-    return from_status(e->ev->apply_galois(in, elt, sel, out, count, s));
+// SEAL's decomposition of a row rotation into power-of-two rotations (non-adjacent form, rotate_internal).  A part of n/2 rows
+// is the identity on the rows: the chains skip it (naf_skip).
+static std::vector<int> naf_parts(int steps) {
   std::vector<int> naf;
   const bool neg = steps < 0;
   int v = neg ? -steps : steps;
@@ -1802,15 +1854,47 @@ static long batch_rotate_keys_internal(EvalObj* e, const u64* in, int steps, voi
     v = (v - zi) >> 1;
     if (zi) naf.push_back((neg ? -zi : zi) * (1 << i));
   }
-  if (naf.size() == 1) return from_status(kNoKey);
+  return naf;
+}
+static bool naf_skip(int part, u64 n) { return (u64)(part < 0 ? -part : part) == (n >> 1); }
+
+// SEAL's rotate_internal over per-item key sets that all decide alike: the direct key when the referenced sets hold it, the NAF
+// chain otherwise (hipbfv_batch_rotate_rows_keys splits a batch whose sets decide differently)
+static long batch_rotate_keys_internal(EvalObj* e, const u64* in, int steps, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
+                                       u64* out, uint64_t count, hipStream_t s) {
+  if (steps == 0) return HIPBFV_S_OK;
+  const u32 elt = e->ev->galois_elt_from_step(steps);
+  if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
+  std::vector<const u64*> tab;
+  uint64_t missing = 0;
+  if (const KeySel sel = keys_sel(key_sets, num_sets, key_index, count, e, (elt - 1) >> 1, tab, &missing); sel.present())
+    return from_status(e->ev->apply_galois(in, elt, sel, out, count, s));
+  const std::vector<int> naf = naf_parts(steps);
+  if (naf.size() == 1) return no_key_in_set(missing);
   const u64* cur = in;
   for (int part : naf) {
-    if ((u32)(part < 0 ? -part : part) == (e->ctx->n() >> 1)) continue;
+    if (naf_skip(part, e->ctx->n())) continue;
     long hr = batch_rotate_keys_internal(e, cur, part, key_sets, num_sets, key_index, out, count, s);
     if (hr != HIPBFV_S_OK) return hr;
     cur = out;
   }
   return HIPBFV_S_OK;
+}
+
+// Item copies between a batch and a compact stage: stage item j <-> batch item items[j] (`width` words each, batch items
+// `stride` words apart); a run of consecutive items is one copy.
+static hipError_t copy_items(u64* stage, const u64* batch_in, u64* batch_out, size_t width, size_t stride, const std::vector<uint64_t>& items,
+                             hipStream_t s) {
+  for (size_t j = 0; j < items.size();) {
+    size_t r = 1;
+    while (stride == width && j + r < items.size() && items[j + r] == items[j] + r) r++;
+    const size_t bytes = ((r - 1) * stride + width) * sizeof(u64);
+    const hipError_t err = batch_in ? hipMemcpyAsync(stage + j * width, batch_in + items[j] * stride, bytes, hipMemcpyDeviceToDevice, s)
+                                    : hipMemcpyAsync(batch_out + items[j] * stride, stage + j * width, bytes, hipMemcpyDeviceToDevice, s);
+    if (err != hipSuccess) return err;
+    j += r;
+  }
+  return hipSuccess;
 }
 
 long hipbfv_batch_rotate_rows_keys(void* h, const uint64_t* ct2, int steps, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
@@ -1819,15 +1903,53 @@ long hipbfv_batch_rotate_rows_keys(void* h, const uint64_t* ct2, int steps, void
   if (!ct2 || !out2) return HIPBFV_E_POINTER;
   if (!e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
   KEYSETS_OR_RETURN();
+  const size_t w = e->ctx->ct_words(2);
+  ALIAS_OR_RETURN(cts(out2, w, count), {cts(ct2, w, count)});
   hipStream_t s = (hipStream_t)stream;
   if (steps == 0) {
-    if ((const u64*)ct2 != (u64*)out2 &&
-        hipMemcpyAsync(out2, ct2, count * e->ctx->ct_words(2) * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess)
+    if ((const u64*)ct2 != (u64*)out2 && hipMemcpyAsync(out2, ct2, count * w * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess)
       return from_status(kHipError);
     return HIPBFV_S_OK;
   }
   if (!count) return HIPBFV_S_OK;
-  return batch_rotate_keys_internal(e, (const u64*)ct2, steps, key_sets, num_sets, key_index, (u64*)out2, count, s);
+  const u32 elt = e->ev->galois_elt_from_step(steps);
+  if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
+  // per referenced set, as the single-key call decides: the direct key, or else every key of the NAF chain
+  const std::vector<char> used = referenced_sets(key_index, count, num_sets);
+  const std::vector<int> naf = naf_parts(steps);
+  std::vector<char> direct(num_sets, 0);
+  bool any_direct = false, any_naf = false;
+  for (uint64_t k = 0; k < num_sets; k++) {
+    if (!used[k]) continue;
+    direct[k] = key_or_null(key_sets[k], e, (elt - 1) >> 1) != nullptr;
+    if (!direct[k]) {
+      bool chain = naf.size() > 1;
+      for (int part : naf) chain = chain && (naf_skip(part, e->ctx->n()) || key_or_null(key_sets[k], e, (e->ev->galois_elt_from_step(part) - 1) >> 1));
+      if (!chain) return no_key_in_set(k);
+    }
+    (direct[k] ? any_direct : any_naf) = true;
+  }
+  if (!(any_direct && any_naf))  // the common case: one call over the caller's buffers
+    return batch_rotate_keys_internal(e, (const u64*)ct2, steps, key_sets, num_sets, key_index, (u64*)out2, count, s);
+  // the sets disagree: the direct group and the NAF group run apart, each gathered into a compact stage and scattered back
+  std::vector<uint64_t> items[2];
+  std::vector<uint32_t> kidx[2];
+  for (uint64_t i = 0; i < count; i++) {
+    const int g = direct[key_index[i]] ? 0 : 1;
+    items[g].push_back(i);
+    kidx[g].push_back(key_index[i]);
+  }
+  ScratchGuard sg(e->ev->scratch(), 2 * std::max(items[0].size(), items[1].size()) * w * sizeof(u64), s);
+  if (!sg.p) return from_status(kOutOfMemory);
+  u64* in_stage = (u64*)sg.p;
+  u64* out_stage = in_stage + std::max(items[0].size(), items[1].size()) * w;
+  for (int g = 0; g < 2; g++) {
+    const uint64_t c = items[g].size();
+    if (copy_items(in_stage, (const u64*)ct2, nullptr, w, w, items[g], s) != hipSuccess) return from_status(kHipError);
+    if (long hr = batch_rotate_keys_internal(e, in_stage, steps, key_sets, num_sets, kidx[g].data(), out_stage, c, s)) return hr;
+    if (copy_items(out_stage, nullptr, (u64*)out2, w, w, items[g], s) != hipSuccess) return from_status(kHipError);
+  }
+  return HIPBFV_S_OK;
 HIPBFV_END
 
 long hipbfv_batch_rotate_columns_keys(void* h, const uint64_t* ct2, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
@@ -1840,36 +1962,44 @@ HIPBFV_END
 long hipbfv_batch_add(void* h, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t size, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!a || !b || !out) return HIPBFV_E_POINTER;
+  const size_t w = e->ctx->ct_words(size);
+  ALIAS_OR_RETURN(cts(out, w, count), {cts(a, w, count), cts(b, w, count)});
   return from_status(e->ev->add((const u64*)a, (const u64*)b, (u64*)out, (u32)size, count, (hipStream_t)stream));
 HIPBFV_END
 
 long hipbfv_batch_sub(void* h, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t size, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!a || !b || !out) return HIPBFV_E_POINTER;
+  const size_t w = e->ctx->ct_words(size);
+  ALIAS_OR_RETURN(cts(out, w, count), {cts(a, w, count), cts(b, w, count)});
   return from_status(e->ev->sub((const u64*)a, (const u64*)b, (u64*)out, (u32)size, count, (hipStream_t)stream));
 HIPBFV_END
 
 long hipbfv_batch_negate(void* h, const uint64_t* a, uint64_t* out, uint64_t size, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!a || !out) return HIPBFV_E_POINTER;
+  ALIAS_OR_RETURN(cts(out, e->ctx->ct_words(size), count), {cts(a, e->ctx->ct_words(size), count)});
   return from_status(e->ev->negate((const u64*)a, (u64*)out, (u32)size, count, (hipStream_t)stream));
 HIPBFV_END
 
 long hipbfv_batch_add_plain(void* h, const uint64_t* ct, uint64_t size, const uint64_t* plain, uint64_t pstride, uint64_t* out, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!ct || !plain || !out) return HIPBFV_E_POINTER;
+  ALIAS_OR_RETURN(cts(out, e->ctx->ct_words(size), count), {cts(ct, e->ctx->ct_words(size), count), Span{plain, e->ctx->n(), pstride, count}});
   return from_status(e->ev->add_plain((const u64*)ct, (u32)size, (const u64*)plain, pstride, (u64*)out, count, (hipStream_t)stream));
 HIPBFV_END
 
 long hipbfv_batch_sub_plain(void* h, const uint64_t* ct, uint64_t size, const uint64_t* plain, uint64_t pstride, uint64_t* out, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!ct || !plain || !out) return HIPBFV_E_POINTER;
+  ALIAS_OR_RETURN(cts(out, e->ctx->ct_words(size), count), {cts(ct, e->ctx->ct_words(size), count), Span{plain, e->ctx->n(), pstride, count}});
   return from_status(e->ev->sub_plain((const u64*)ct, (u32)size, (const u64*)plain, pstride, (u64*)out, count, (hipStream_t)stream));
 HIPBFV_END
 
 long hipbfv_batch_multiply_plain(void* h, const uint64_t* ct, uint64_t size, const uint64_t* plain, uint64_t pstride, uint64_t* out, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!ct || !plain || !out) return HIPBFV_E_POINTER;
+  ALIAS_OR_RETURN(cts(out, e->ctx->ct_words(size), count), {cts(ct, e->ctx->ct_words(size), count), Span{plain, e->ctx->n(), pstride, count}});
   return from_status(e->ev->multiply_plain((const u64*)ct, (u32)size, (const u64*)plain, pstride, (u64*)out, count, (hipStream_t)stream));
 HIPBFV_END
 
@@ -2287,10 +2417,74 @@ long hipbfv_Program_Describe(void* h, char* buffer, uint64_t capacity, uint64_t*
   return HIPBFV_S_OK;
 HIPBFV_END
 
-// key_index == nullptr: one key set (num_key_sets = 1) for every input set -- the reference's call
 static long program_run_impl(void* h, void* evaluator, uint64_t batch, uint64_t num_inputs, const uint32_t* input_kinds,
                              const uint64_t* const* input_ptrs, const uint64_t* input_strides, uint64_t num_key_sets, void* const* relin_keys,
-                             void* const* galois_keys, const uint32_t* key_index, uint64_t num_outputs, uint64_t* const* outputs, void* stream) {
+                             void* const* galois_keys, const uint32_t* key_index, uint64_t num_outputs, uint64_t* const* outputs, void* stream,
+                             const uint64_t* item_of = nullptr);
+
+// Program_RunKeys whose referenced key sets hold different kinds of keys (`cls`: the class of every referenced set -- whether it
+// holds a relinearisation key, which Galois elements it holds): one run per class, so that every input set decides its
+// rotations (direct key or NAF chain) as Program_Run with its own keys does.  A class's input sets are gathered into a compact
+// stage (shared plaintexts stay shared), run with their own key_index, and its outputs scattered back.
+static long program_run_by_class(void* h, void* evaluator, EvalObj* e, uint64_t batch, uint64_t num_inputs, const uint32_t* input_kinds,
+                                 const uint64_t* const* input_ptrs, const uint64_t* input_strides, uint64_t num_key_sets, void* const* relin_keys,
+                                 void* const* galois_keys, const uint32_t* key_index, uint64_t num_outputs, uint64_t* const* outputs, hipStream_t s,
+                                 const std::vector<int>& cls, int nclasses, const uint64_t* item_of) {
+  const Context& c = *e->ctx;
+  const size_t ct_words = c.ct_words(2);
+  for (int g = 0; g < nclasses; g++) {
+    std::vector<uint64_t> items, callers;
+    std::vector<uint32_t> kidx;
+    for (uint64_t i = 0; i < batch; i++)
+      if (cls[key_index[i]] == g) {
+        items.push_back(i);
+        kidx.push_back(key_index[i]);
+        callers.push_back(item_of ? item_of[i] : i);  // a transparent-result error names the caller's input set
+      }
+    const uint64_t m = items.size();
+    std::vector<size_t> width(num_inputs, 0);  // words per staged item; 0 = passed through (absent or shared)
+    size_t words = 0;
+    for (uint64_t i = 0; i < num_inputs; i++) {
+      if (!input_ptrs[i] || (input_kinds[i] != 0 && !input_strides[i])) continue;
+      width[i] = input_kinds[i] == 0 ? ct_words : input_kinds[i] == 1 ? c.n() : input_kinds[i] == 2 ? c.ct_words(1) : 0;
+      words += width[i] * m;
+    }
+    for (uint64_t k = 0; k < num_outputs; k++)
+      if (outputs[k]) words += ct_words * m;
+    ScratchGuard sg(e->ev->scratch(), words * sizeof(u64), s);
+    if (!sg.p) return from_status(kOutOfMemory);
+    u64* cur = (u64*)sg.p;
+    std::vector<const uint64_t*> ptrs(input_ptrs, input_ptrs + num_inputs);
+    std::vector<uint64_t> strides(input_strides, input_strides + num_inputs);
+    for (uint64_t i = 0; i < num_inputs; i++) {
+      if (!width[i]) continue;
+      if (copy_items(cur, (const u64*)input_ptrs[i], nullptr, width[i], input_kinds[i] == 0 ? ct_words : input_strides[i], items, s) != hipSuccess)
+        return from_status(kHipError);
+      ptrs[i] = (const uint64_t*)cur;
+      if (input_kinds[i] != 0) strides[i] = width[i];
+      cur += width[i] * m;
+    }
+    std::vector<uint64_t*> outs(num_outputs, nullptr);
+    for (uint64_t k = 0; k < num_outputs; k++)
+      if (outputs[k]) {
+        outs[k] = (uint64_t*)cur;
+        cur += ct_words * m;
+      }
+    if (long hr = program_run_impl(h, evaluator, m, num_inputs, input_kinds, ptrs.data(), strides.data(), num_key_sets, relin_keys, galois_keys,
+                                   kidx.data(), num_outputs, outs.data(), s, callers.data()))
+      return hr;
+    for (uint64_t k = 0; k < num_outputs; k++)
+      if (outputs[k] && copy_items((u64*)outs[k], nullptr, (u64*)outputs[k], ct_words, ct_words, items, s) != hipSuccess) return from_status(kHipError);
+  }
+  return HIPBFV_S_OK;
+}
+
+// key_index == nullptr: one key set (num_key_sets = 1) for every input set -- the reference's call.  item_of: the caller's
+// input set of every input set of this run (a run of one class of key sets), for the error message
+static long program_run_impl(void* h, void* evaluator, uint64_t batch, uint64_t num_inputs, const uint32_t* input_kinds,
+                             const uint64_t* const* input_ptrs, const uint64_t* input_strides, uint64_t num_key_sets, void* const* relin_keys,
+                             void* const* galois_keys, const uint32_t* key_index, uint64_t num_outputs, uint64_t* const* outputs, void* stream,
+                             const uint64_t* item_of) {
   ProgramObj* p = as<ProgramObj>(h, kMagicProgram);
   EvalObj* e = as<EvalObj>(evaluator, kMagicEval);
   if (!p || !e || (num_inputs && (!input_kinds || !input_ptrs || !input_strides)) || (num_outputs && !outputs)) return HIPBFV_E_POINTER;
@@ -2306,9 +2500,36 @@ static long program_run_impl(void* h, void* evaluator, uint64_t batch, uint64_t 
       if (ko->ctx.get() == e->ctx.get())
         for (auto& kv : ko->keys) keys.galois[k][kv.first] = kv.second;
   }
-  if (key_index)
+  if (key_index) {
     for (uint64_t i = 0; i < batch; i++)
       if (key_index[i] >= num_key_sets) return fail(HIPBFV_E_INVALIDARG, "key_index names a key set that was not given");
+    // the per-item key rule (include/hipbfv.h): only the sets key_index names are validated and decide anything.  A named
+    // handle must be a key object of this context; an unnamed slot takes the keys of a named set (never read).
+    const std::vector<char> used = referenced_sets(key_index, batch, num_key_sets);
+    std::vector<int> cls(num_key_sets, -1);
+    std::vector<std::pair<bool, std::vector<u32>>> kinds;
+    uint64_t first = num_key_sets;
+    for (uint64_t k = 0; k < num_key_sets; k++) {
+      if (!used[k]) continue;
+      for (void* const* arr : {relin_keys, galois_keys}) {
+        KeysObj* ko = arr && arr[k] ? as<KeysObj>(arr[k], kMagicKeys) : nullptr;
+        if (arr && arr[k] && (!ko || ko->ctx.get() != e->ctx.get())) return no_key_in_set(k);
+      }
+      if (first == num_key_sets) first = k;
+      std::pair<bool, std::vector<u32>> kind{keys.relin[k] != nullptr, {}};
+      for (auto& kv : keys.galois[k]) kind.second.push_back(kv.first);
+      cls[k] = (int)(std::find(kinds.begin(), kinds.end(), kind) - kinds.begin());
+      if (cls[k] == (int)kinds.size()) kinds.push_back(std::move(kind));
+    }
+    for (uint64_t k = 0; k < num_key_sets && first < num_key_sets; k++)
+      if (!used[k]) {
+        keys.relin[k] = keys.relin[first];
+        keys.galois[k] = keys.galois[first];
+      }
+    if (kinds.size() > 1)
+      return program_run_by_class(h, evaluator, e, batch, num_inputs, input_kinds, input_ptrs, input_strides, num_key_sets, relin_keys, galois_keys,
+                                  key_index, num_outputs, outputs, (hipStream_t)stream, cls, (int)kinds.size(), item_of);
+  }
   std::string err;
   // the reference's runtime.run fails when any node's result is transparent (SEAL built with throw-on-transparent,
   // seal_fhe/build.rs:46-66; sunscreen/tests/features.rs:8-34; error collapse run.rs:78-82): every node's results are
@@ -2356,7 +2577,8 @@ static long program_run_impl(void* h, void* evaluator, uint64_t batch, uint64_t 
     if (first_bad != 0xFFFFFFFFu) {
       char msg[128];
       // a merged launch numbers its ciphertexts member-major (member * batch + item): the item is what the caller knows
-      snprintf(msg, sizeof(msg), "result ciphertext is transparent (input set %llu of the batch)", (unsigned long long)(off + first_bad % (c ? c : 1)));
+      const uint64_t set = off + first_bad % (c ? c : 1);
+      snprintf(msg, sizeof(msg), "result ciphertext is transparent (input set %llu of the batch)", (unsigned long long)(item_of ? item_of[set] : set));
       hr = fail(HIPBFV_COR_E_INVALIDOPERATION, msg);
       break;
     }
@@ -2953,10 +3175,13 @@ static Evaluator* eval_of(void* evaluator) {
   EvalObj* e = as<EvalObj>(evaluator, kMagicEval);
   return e ? e->ev.get() : nullptr;
 }
+// (the transforms either side of the evaluator take no aliasing at all: every output is disjoint from every input)
 long hipbfv_batch_encode(void* evaluator, const uint64_t* values, uint64_t* plain, uint64_t count, int is_signed, void* stream) HIPBFV_BEGIN
   Evaluator* ev = eval_of(evaluator);
   if (!ev || !values || !plain) return HIPBFV_E_POINTER;
   u32 bad = 0;
+  const size_t n = as<EvalObj>(evaluator, kMagicEval)->ctx->n();
+  ALIAS_OR_RETURN(cts(plain, n, count), {cts(values, n, count)}, false);
   if (int st = ev->batch_encode((const u64*)values, (u64*)plain, count, is_signed != 0, &bad, (hipStream_t)stream)) return from_status(st);
   if (bad) return fail(HIPBFV_E_INVALIDARG, "input value is larger than plain_modulus");
   return HIPBFV_S_OK;
@@ -2964,6 +3189,8 @@ HIPBFV_END
 long hipbfv_batch_decode(void* evaluator, const uint64_t* plain, uint64_t* values, uint64_t count, int is_signed, void* stream) HIPBFV_BEGIN
   Evaluator* ev = eval_of(evaluator);
   if (!ev || !values || !plain) return HIPBFV_E_POINTER;
+  const size_t n = as<EvalObj>(evaluator, kMagicEval)->ctx->n();
+  ALIAS_OR_RETURN(cts(values, n, count), {cts(plain, n, count)}, false);
   return from_status(ev->batch_decode((const u64*)plain, (u64*)values, count, is_signed != 0, (hipStream_t)stream));
 HIPBFV_END
 long hipbfv_batch_decrypt(void* evaluator, const uint64_t* ct, uint32_t size, void* secret_key, uint64_t* plain, uint64_t count, void* stream) HIPBFV_BEGIN
@@ -2971,6 +3198,7 @@ long hipbfv_batch_decrypt(void* evaluator, const uint64_t* ct, uint32_t size, vo
   AsymKeyObj* k = as<AsymKeyObj>(secret_key, kMagicSecretKey);
   if (!e || !k || !ct || !plain) return HIPBFV_E_POINTER;
   if (!k->key || k->key->ctx.get() != e->ctx.get()) return fail(HIPBFV_E_INVALIDARG, "secret key is not valid for encryption parameters");
+  ALIAS_OR_RETURN(cts(plain, e->ctx->n(), count), {cts(ct, e->ctx->ct_words(size), count)}, false);
   return from_status(e->ev->decrypt((const u64*)ct, size, k->key->dev, (u64*)plain, count, (hipStream_t)stream));
 HIPBFV_END
 long hipbfv_batch_encrypt(void* evaluator, const uint64_t* plain, uint64_t plain_stride, void* public_key, uint64_t seed, uint64_t first_op,
@@ -2979,6 +3207,7 @@ long hipbfv_batch_encrypt(void* evaluator, const uint64_t* plain, uint64_t plain
   AsymKeyObj* k = as<AsymKeyObj>(public_key, kMagicPublicKey);
   if (!e || !k || !ct || !plain) return HIPBFV_E_POINTER;
   if (!k->key || k->key->ctx.get() != e->ctx.get()) return fail(HIPBFV_E_INVALIDARG, "public key is not valid for encryption parameters");
+  ALIAS_OR_RETURN(cts(ct, e->ctx->ct_words(2), count), {Span{plain, e->ctx->n(), plain_stride, count}}, false);
   // TEST ONLY: a 64-bit seed (reproducible batches for the parity tests); production callers use hipbfv_batch_encrypt_seeded
   return from_status(e->ev->encrypt((const u64*)plain, plain_stride, k->key->dev, rng_seed_from_u64_for_tests(seed), first_op, (u64*)ct, count, (hipStream_t)stream));
 HIPBFV_END
@@ -2988,6 +3217,7 @@ long hipbfv_batch_encrypt_seeded(void* evaluator, const uint64_t* plain, uint64_
   AsymKeyObj* k = as<AsymKeyObj>(public_key, kMagicPublicKey);
   if (!e || !k || !ct || !plain) return HIPBFV_E_POINTER;
   if (!k->key || k->key->ctx.get() != e->ctx.get()) return fail(HIPBFV_E_INVALIDARG, "public key is not valid for encryption parameters");
+  ALIAS_OR_RETURN(cts(ct, e->ctx->ct_words(2), count), {Span{plain, e->ctx->n(), plain_stride, count}}, false);
   RngSeed seed;
   if (seed64)
     seed = rng_seed_from_512(seed64);
@@ -3004,12 +3234,15 @@ HIPBFV_END
 long hipbfv_batch_plain_to_ntt(void* evaluator, const uint64_t* plain, uint64_t plain_stride, uint64_t* pntt, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(evaluator);
   if (!plain || !pntt) return HIPBFV_E_POINTER;
+  ALIAS_OR_RETURN(cts(pntt, e->ctx->ct_words(1), count), {Span{plain, e->ctx->n(), plain_stride, count}}, false);
   return from_status(e->ev->plain_to_ntt((const u64*)plain, plain_stride, (u64*)pntt, count, (hipStream_t)stream, 1));
 HIPBFV_END
 long hipbfv_batch_ct_to_ntt(void* evaluator, const uint64_t* ct, uint64_t size, uint64_t* ctn, uint64_t count, void* stream) HIPBFV_BEGIN
   Evaluator* ev = eval_of(evaluator);
   if (!ev || !ct || !ctn) return HIPBFV_E_POINTER;
   if (size < 1) return fail(HIPBFV_E_INVALIDARG, "invalid ciphertext size");
+  const size_t w = as<EvalObj>(evaluator, kMagicEval)->ctx->ct_words(size);
+  ALIAS_OR_RETURN(cts(ctn, w, count), {cts(ct, w, count)}, false);
   return from_status(ev->ct_to_ntt((const u64*)ct, (u32)size, (u64*)ctn, count, (hipStream_t)stream));
 HIPBFV_END
 long hipbfv_batch_dot_plain_ntt(void* evaluator, const uint64_t* ctn, uint64_t cols, const uint64_t* pntt, uint64_t rows, uint64_t* out,
@@ -3017,6 +3250,8 @@ long hipbfv_batch_dot_plain_ntt(void* evaluator, const uint64_t* ctn, uint64_t c
   Evaluator* ev = eval_of(evaluator);
   if (!ev || !ctn || !pntt || !out) return HIPBFV_E_POINTER;
   if (cols > 0xFFFFFFFFull || rows > 0xFFFFFFFFull) return fail(HIPBFV_E_INVALIDARG, "matrix too large");
+  const Context& c = *as<EvalObj>(evaluator, kMagicEval)->ctx;
+  ALIAS_OR_RETURN(cts(out, c.ct_words(2), rows), {cts(ctn, c.ct_words(2), cols), cts(pntt, c.ct_words(1) * cols, rows)}, false);
   return from_status(ev->dot_plain_ntt((const u64*)ctn, (u32)cols, (const u64*)pntt, (u32)rows, (u64*)out, (hipStream_t)stream));
 HIPBFV_END
 
@@ -3071,6 +3306,7 @@ long hipbfv_batch_mod_switch(void* evaluator, const uint64_t* ct, uint64_t size,
   Evaluator* ev = e->ev.get();
   if (!ct || !out) return HIPBFV_E_POINTER;
   if (size < 1) return fail(HIPBFV_E_INVALIDARG, "invalid ciphertext size");
+  ALIAS_OR_RETURN(cts(out, size * (e->ctx->K() - 1) * e->ctx->n(), count), {cts(ct, e->ctx->ct_words(size), count)});
   return from_status(ev->mod_switch_next((const u64*)ct, (u32)size, (u64*)out, count, (hipStream_t)stream));
 HIPBFV_END
 

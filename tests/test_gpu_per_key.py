@@ -331,3 +331,264 @@ def test_concurrent_clients_with_their_own_keys_on_one_evaluator():
     for th in ts:
         th.join()
     assert not errors, errors
+
+
+# ---- per-client key isolation: tenants that hold DIFFERENT kinds of keys (include/hipbfv.h: the per-item key rule) ----
+E_INVALIDARG = 0x80070057
+
+
+def _mixed_tenants(name):
+    """Tenant D: the power-of-two Galois keys plus the direct keys of steps 3 and -5; tenant P: the power-of-two keys only
+    (steps 3, -5, 7 take SEAL's NAF chain); tenant R: a relinearisation key and no Galois key; `foreign`: P's keys loaded
+    into another context of the same parameters (a key object the evaluator must not accept)."""
+    from sunscreen_amd import Context, GaloisKeys, RelinearizationKeys
+    from sunscreen_amd.batch import BatchEvaluator
+
+    n, primes, t = params(name)
+    o = oracle_for(name)
+    ctx = Context.from_raw(n, primes, t)
+    ev = BatchEvaluator(ctx)
+    O.seed(501)
+    skP, pkP, rkP, gkP = o.keygen(galois_elts="all")
+    elts = sorted(gkP) + [o.galois_elt_from_step(3), o.galois_elt_from_step(-5)]
+    O.seed(502)
+    skD, pkD, rkD, gkD = o.keygen(galois_elts=elts)
+    O.seed(503)
+    skR, pkR, rkR, _ = o.keygen()
+    ten = {
+        "D": {"sk": skD, "pk": pkD, "rk": rkD, "gk": gkD},
+        "P": {"sk": skP, "pk": pkP, "rk": rkP, "gk": gkP},
+        "R": {"sk": skR, "pk": pkR, "rk": rkR, "gk": {}},
+    }
+    for x in ten.values():
+        x["rkd"] = RelinearizationKeys.from_array(ctx, x["rk"])
+        x["gkd"] = GaloisKeys.from_arrays(ctx, x["gk"]) if x["gk"] else None
+    other = Context.from_raw(n, primes, t)
+    foreign = {"rkd": RelinearizationKeys.from_array(other, rkP), "gkd": GaloisKeys.from_arrays(other, gkP), "ctx": other}
+    return o, ctx, ev, ten, foreign
+
+
+def _enc_for(o, pks, rng):
+    return np.stack([o.encrypt(pk, o.batch_encode(rng.integers(0, o.t, o.n).astype(np.uint64))) for pk in pks])
+
+
+@pytest.mark.parametrize(
+    "name,count,chunk",
+    [
+        ("default_4096_16", 23, 5),  # chunks of 5, a short last chunk
+        ("default_8192_17", 21, 7),  # above the small-batch limit (16 at n = 8192), three chunks
+        ("default_8192_17", 9, 0),
+    ],
+)
+def test_rotate_rows_keys_with_mixed_holdings(name, count, chunk):
+    """D's items rotate with D's direct keys, P's items over P's NAF chain, whoever else is in the batch: every item equals the
+    oracle with its own keys and, word for word, the single-key call with that item's set; out of place and in place."""
+    import torch
+    from sunscreen_amd.batch import to_device, to_host
+
+    o, ctx, ev, ten, _ = _mixed_tenants(name)
+    if chunk:
+        ev.set_chunk_ops(chunk)
+    rng = np.random.default_rng(count * 31 + chunk)
+    key_index = rng.integers(0, 2, count).astype(np.uint32)
+    key_index[:2] = (1, 0)
+    who = ["D", "P"]
+    a = _enc_for(o, [ten[who[k]]["pk"] for k in key_index], rng)
+    da = to_device(a)
+    sets = [ten["D"]["gkd"], ten["P"]["gkd"]]
+    ki = torch.from_numpy(key_index.astype(np.int64)).to(da.device)
+    for steps in (3, -5, 7):
+        got = ev.rotate_rows_keys(da, steps, sets, key_index)
+        inplace = da.clone()
+        ev.rotate_rows_keys(inplace, steps, sets, key_index, out=inplace)
+        torch.cuda.synchronize()
+        assert torch.equal(got, inplace), (name, steps)
+        for k in (0, 1):
+            sel = ki == k
+            single = ev.rotate_rows(da[sel].contiguous(), steps, sets[k])
+            assert torch.equal(got[sel], single), (name, steps, who[k])
+        host = to_host(got)
+        for i, k in enumerate(key_index):
+            ref = o.rotate_rows(a[i], steps, ten[who[k]]["gk"])
+            assert (host[i] == ref).all(), (name, steps, i, who[k])
+    ev.check()
+
+
+def test_unreferenced_key_sets_are_not_validated():
+    """NULL, a set without the key and a key object of another context in the key arrays, never named by key_index: every
+    per-key call succeeds with the bits of the referenced sets alone."""
+    from sunscreen_amd.batch import to_device, to_host
+
+    o, ctx, ev, ten, foreign = _mixed_tenants("default_4096_16")
+    rng = np.random.default_rng(5)
+    key_index = np.array([0, 4, 4, 0, 4, 0, 0, 4, 4, 0, 4], dtype=np.uint32)  # sets 1, 2, 3 unused
+    who = {0: "D", 4: "P"}
+    a = _enc_for(o, [ten[who[k]]["pk"] for k in key_index], rng)
+    b = _enc_for(o, [ten[who[k]]["pk"] for k in key_index], rng)
+    da, db = to_device(a), to_device(b)
+    rsets = [ten["D"]["rkd"], None, ten["P"]["gkd"], foreign["rkd"], ten["P"]["rkd"]]  # 2: a Galois object, no relin key
+    gsets = [ten["D"]["gkd"], None, ten["R"]["rkd"], foreign["gkd"], ten["P"]["gkd"]]  # 2: R's relin object, no Galois key
+    mr = to_host(ev.multiply_relin_keys(da, db, rsets, key_index))
+    rl = to_host(ev.relinearize_keys(ev.multiply(da, db), rsets, key_index))
+    elt = o.galois_elt_from_step(2)
+    ag = to_host(ev.apply_galois_keys(da, elt, gsets, key_index))
+    rc = to_host(ev.rotate_columns_keys(da, gsets, key_index))
+    rr = {s: to_host(ev.rotate_rows_keys(da, s, gsets, key_index)) for s in (3, -5)}
+    for i, k in enumerate(key_index):
+        x = ten[who[k]]
+        ref = o.relinearize(o.multiply(a[i], b[i]), x["rk"])
+        assert (mr[i] == ref).all() and (rl[i] == ref).all(), i
+        assert (ag[i] == o.apply_galois(a[i], elt, x["gk"])).all(), i
+        assert (rc[i] == o.rotate_columns(a[i], x["gk"])).all(), i
+        for s in (3, -5):
+            assert (rr[s][i] == o.rotate_rows(a[i], s, x["gk"])).all(), (s, i)
+    ev.check()
+
+
+def test_referenced_key_set_without_the_key_fails_like_the_single_key_call():
+    """A set key_index names that lacks the key (NULL, a set without it, another context's object): E_INVALIDARG before
+    anything is launched, the error names the set, the output keeps its sentinel, the evaluator serves the next call.  For
+    rotate_rows_keys "without the key" means neither the direct key nor the NAF chain's power-of-two keys."""
+    import torch
+    from sunscreen_amd.batch import to_device, to_host
+    from sunscreen_amd.seal import HipBfvError
+
+    o, ctx, ev, ten, foreign = _mixed_tenants("default_4096_16")
+    rng = np.random.default_rng(6)
+    count = 6
+    a = _enc_for(o, [ten["P"]["pk"]] * count, rng)
+    da = to_device(a)
+    ct3 = ev.multiply(da, da)
+    # the single-key calls fail the same way
+    with pytest.raises(HipBfvError) as exc:
+        ev.rotate_rows(da, 3, ten["R"]["rkd"])
+    assert exc.value.hresult == E_INVALIDARG
+    with pytest.raises(HipBfvError) as exc:
+        ev.relinearize(ct3, ten["P"]["gkd"])
+    assert exc.value.hresult == E_INVALIDARG
+    key_index = np.array([0, 1, 0, 2, 0, 0], dtype=np.uint32)
+    cases = {
+        "relinearize_keys": lambda bad, out: ev.relinearize_keys(ct3, [ten["P"]["rkd"], ten["P"]["rkd"], bad], key_index, out=out),
+        "multiply_relin_keys": lambda bad, out: ev.multiply_relin_keys(da, da, [ten["P"]["rkd"], ten["P"]["rkd"], bad], key_index, out=out),
+        "apply_galois_keys": lambda bad, out: ev.apply_galois_keys(da, o.galois_elt_from_step(1), [ten["P"]["gkd"], ten["D"]["gkd"], bad], key_index, out=out),
+        "rotate_columns_keys": lambda bad, out: ev.rotate_columns_keys(da, [ten["P"]["gkd"], ten["D"]["gkd"], bad], key_index, out=out),
+        "rotate_rows_keys": lambda bad, out: ev.rotate_rows_keys(da, 3, [ten["P"]["gkd"], ten["D"]["gkd"], bad], key_index, out=out),
+    }
+    relin_bad = [None, ten["P"]["gkd"], foreign["rkd"]]
+    galois_bad = [None, ten["R"]["rkd"], foreign["gkd"]]
+    sentinel = -0x5A5A5A5A5A5A5A5B
+    for what, call in cases.items():
+        for bad in relin_bad if "relin" in what else galois_bad:
+            out = torch.full_like(da, sentinel)
+            with pytest.raises(HipBfvError) as exc:
+                call(bad, out)
+            assert exc.value.hresult == E_INVALIDARG, (what, exc.value)
+            assert "key set 2" in str(exc.value), (what, str(exc.value))
+            torch.cuda.synchronize()
+            assert bool((out == sentinel).all()), what
+    ev.check()
+    # the evaluator works for the next call
+    good = to_host(ev.rotate_rows_keys(da, 3, [ten["P"]["gkd"], ten["D"]["gkd"]], key_index % 2))
+    for i, k in enumerate(key_index % 2):
+        assert (good[i] == o.rotate_rows(a[i], 3, ten[("P", "D")[k]]["gk"])).all(), i
+
+
+def _rotate_3_5_program():
+    from sunscreen_amd.program import FheProgram
+
+    p = FheProgram()
+    a = p.append_input_ciphertext(0)
+    r3 = p.append_rotate_left(a, p.append_input_literal(3))
+    r5 = p.append_rotate_left(a, p.append_input_literal(5))
+    p.append_output_ciphertext(p.append_add(r3, r5))
+    return p
+
+
+def test_program_run_keys_with_mixed_holdings():
+    """hipbfv_Program_RunKeys, both executors: input sets of D (direct key of step 3) and P (NAF chain) interleaved -- every set
+    equals hipbfv_Program_Run with that set's keys alone and the oracle with its keys; chi_sq with an unreferenced NULL
+    relinearisation slot; a referenced key object of another context fails as in the batch calls."""
+    import torch
+    from sunscreen_amd.batch import to_device, to_host
+    from sunscreen_amd.seal import HipBfvError
+    from sunscreen_amd.workloads import chi_sq_optimized
+
+    o, ctx, ev, ten, foreign = _mixed_tenants("default_4096_16")
+    rng = np.random.default_rng(44)
+    prog = _rotate_3_5_program()
+    key_index = np.array([0, 1, 1, 0, 1, 0, 0, 1, 0], dtype=np.uint32)
+    who = ["D", "P"]
+    cts = _enc_for(o, [ten[who[k]]["pk"] for k in key_index], rng)
+    dct = to_device(cts)
+    gks = [ten["D"]["gkd"], ten["P"]["gkd"]]
+    for serial in ("0", "1"):
+        os.environ["HIPBFV_PROGRAM_SERIAL"] = serial
+        try:
+            (out,) = prog.run(ev, [dct], None, gks, key_index=key_index)
+            singles = [prog.run(ev, [dct[i : i + 1].contiguous()], None, gks[int(k)])[0] for i, k in enumerate(key_index)]
+        finally:
+            os.environ.pop("HIPBFV_PROGRAM_SERIAL", None)
+        torch.cuda.synchronize()
+        host = to_host(out)
+        for i, k in enumerate(key_index):
+            assert torch.equal(out[i : i + 1], singles[i]), (serial, i, who[k])
+            (ref,) = run_program(o, prog.nodes, prog.edges, [cts[i]], None, ten[who[k]]["gk"])
+            assert (host[i] == ref).all(), (serial, i, who[k])
+    # chi_sq: relin slot 1 is NULL and never named
+    prog = chi_sq_optimized()
+    key_index = np.array([0, 2, 2, 0, 2], dtype=np.uint32)
+    rks = [ten["D"]["rkd"], None, ten["P"]["rkd"]]
+    own = {0: "D", 2: "P"}
+    args = [_enc_for(o, [ten[own[k]]["pk"] for k in key_index], np.random.default_rng(j)) for j in range(3)]
+    for serial in ("0", "1"):
+        os.environ["HIPBFV_PROGRAM_SERIAL"] = serial
+        try:
+            outs = [to_host(t) for t in prog.run(ev, [to_device(c) for c in args], rks, None, key_index=key_index)]
+        finally:
+            os.environ.pop("HIPBFV_PROGRAM_SERIAL", None)
+        for i, k in enumerate(key_index):
+            ref = run_program(o, prog.nodes, prog.edges, [c[i] for c in args], ten[own[int(k)]]["rk"])
+            for j in range(4):
+                assert (outs[j][i] == ref[j]).all(), (serial, i, j)
+    with pytest.raises(HipBfvError) as exc:
+        prog.run(ev, [to_device(c) for c in args], [ten["D"]["rkd"], None, foreign["rkd"]], None, key_index=key_index)
+    assert exc.value.hresult == E_INVALIDARG
+    assert "key set 2" in str(exc.value), str(exc.value)
+    ev.check()
+
+
+def test_concurrent_clients_with_mixed_galois_holdings_on_one_evaluator():
+    """The handle-level drop-in shape with clients D and P rotating by 3 at once: requests that meet in flight combine only
+    when they share a Galois element, so D's thread gets the direct-key bits and P's the NAF-chain bits."""
+    import threading
+
+    from sunscreen_amd import BFVEvaluator, Ciphertext
+
+    o, ctx, _, ten, _ = _mixed_tenants("default_4096_16")
+    ev = BFVEvaluator(ctx)
+    rng = np.random.default_rng(67)
+    clients = ["D", "P", "D", "P", "D", "P"]
+    cts = [_enc_for(o, [ten[c]["pk"]], rng)[0] for c in clients]
+    exp = [o.rotate_rows(ct, 3, ten[c]["gk"]) for ct, c in zip(cts, clients)]
+    naf_only = {e: k for e, k in ten["D"]["gk"].items() if e != o.galois_elt_from_step(3)}
+    assert not (exp[0] == o.rotate_rows(cts[0], 3, naf_only)).all()  # the direct key and the NAF chain give other bits
+    errors = []
+    start = threading.Barrier(len(clients))
+
+    def worker(i):
+        try:
+            a = Ciphertext.from_array(ctx, cts[i])
+            start.wait()
+            for _ in range(8):
+                r = ev.rotate_rows(a, 3, ten[clients[i]]["gkd"])
+                if not (r.to_array() == exp[i]).all():
+                    errors.append((i, clients[i], "rotation mismatch"))
+        except Exception as e:  # noqa: BLE001
+            errors.append((i, repr(e)))
+
+    ts = [threading.Thread(target=worker, args=(i,)) for i in range(len(clients))]
+    for th in ts:
+        th.start()
+    for th in ts:
+        th.join()
+    assert not errors, errors
