@@ -298,7 +298,9 @@ long hipbfv_wire_decode_plaintext(const uint8_t *in, uint64_t in_size, uint8_t *
  * [ptr, ptr + count * words_per_item) (a plaintext operand: its plaintext width, one item when shared).  So the calls whose
  * output is wider or narrower than their input (multiply 2 + 2 -> 3 polynomials, relinearize 3 -> 2, mod_switch K -> K-1) take
  * no in-place form, and an output shifted against its input by any amount is refused.  The transforms either side of the
- * evaluator (encode, decode, decrypt, encrypt, plain_to_ntt, ct_to_ntt, dot_plain_ntt) accept no overlap at all.
+ * evaluator (encode, decode, decrypt, encrypt, plain_to_ntt, ct_to_ntt, dot_plain_ntt) accept no overlap at all.  So do the
+ * noise measures (noise_budget, decrypt_checked): no output may overlap `ct`, and no output may overlap another output (byte
+ * ranges: budget is int32_t[count], noise double[count]); any overlap is HIPBFV_E_INVALIDARG before anything is launched.
  * hipbfv_batch_ntt works in place by definition. */
 long hipbfv_batch_multiply(void *evaluator, const uint64_t *a, uint64_t size_a, const uint64_t *b, uint64_t size_b,
                            uint64_t *out, uint64_t count, void *stream);
@@ -370,6 +372,17 @@ long hipbfv_batch_mod_switch(void *evaluator, const uint64_t *ct, uint64_t size,
 long hipbfv_batch_encode(void *evaluator, const uint64_t *values, uint64_t *plain, uint64_t count, int is_signed, void *stream);
 long hipbfv_batch_decode(void *evaluator, const uint64_t *plain, uint64_t *values, uint64_t count, int is_signed, void *stream);
 long hipbfv_batch_decrypt(void *evaluator, const uint64_t *ct, uint32_t size, void *secret_key, uint64_t *plain, uint64_t count, void *stream);
+/* Invariant noise on device batches (Decryptor_InvariantNoiseBudget / Decryptor_InvariantNoise per item, from the phase that
+ * decrypt computes): budget int32_t[count] = max(0, bits(q) - bits(max_x |[t * ct(s)(x)]_q|) - 1), the centred norm taken exactly;
+ * noise double[count] (nullable) = that norm / q.  decrypt_checked writes the plaintexts of hipbfv_batch_decrypt (the same bits)
+ * and the budgets of noise_budget from ONE phase computation: an item with budget 0 decrypted to garbage (the reference's
+ * Runtime::decrypt returns Error::TooMuchNoise for it).  hipbfv_batch_decrypt's key and level rules; NULL required pointer:
+ * HIPBFV_E_POINTER; size < 2: HIPBFV_E_INVALIDARG; count == 0: HIPBFV_S_OK, nothing launched.  Asynchronous on `stream`; the
+ * evaluator's status word is not touched (budget is the only report). */
+long hipbfv_batch_noise_budget(void *evaluator, const uint64_t *ct, uint32_t size, void *secret_key, int32_t *budget, double *noise,
+                               uint64_t count, void *stream);
+long hipbfv_batch_decrypt_checked(void *evaluator, const uint64_t *ct, uint32_t size, void *secret_key, uint64_t *plain, int32_t *budget,
+                                  uint64_t count, void *stream);
 long hipbfv_batch_encrypt(void *evaluator, const uint64_t *plain, uint64_t plain_stride, void *public_key, uint64_t seed, uint64_t first_op,
                           uint64_t *ct, uint64_t count, void *stream);
 long hipbfv_batch_encrypt_seeded(void *evaluator, const uint64_t *plain, uint64_t plain_stride, void *public_key, const uint8_t *seed64,

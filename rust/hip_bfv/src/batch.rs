@@ -8,7 +8,7 @@
 use std::ffi::c_void;
 use std::ptr::null_mut;
 
-use crate::{bindgen, check, BFVEvaluator, GaloisKeys, RelinearizationKeys, Result};
+use crate::{bindgen, check, BFVEvaluator, GaloisKeys, RelinearizationKeys, Result, SecretKey};
 
 /// A borrowed device buffer of `count` ciphertexts of `size` polynomials (memory is owned by the caller's allocator:
 /// hipMalloc, a torch tensor, ...).  The library cannot check a device address: constructing one is the `unsafe` step, the
@@ -144,6 +144,23 @@ impl<'e> BatchEvaluator<'e> {
     pub unsafe fn plain_to_ntt(&self, plain: *const u64, plain_stride: u64, pntt: *mut u64, count: u64) -> Result<()> {
         check(bindgen::hipbfv_batch_plain_to_ntt(self.h(), plain, plain_stride, pntt, count, self.stream))?;
         self.check()
+    }
+    /// `Decryptor::invariant_noise_budget` per item, on the device: `budget` = `i32[count]`, `noise` (optional) = the fork's
+    /// `invariant_noise` as `f64[count]`.  `Runtime::measure_noise_budget` is the minimum of a value's budgets.  No output may
+    /// overlap `ct` or another output.  Asynchronous: read `budget` after the stream work has completed.
+    ///
+    /// # Safety
+    /// `budget` (and `noise`) must be device addresses of `ct.count()` entries on the evaluator's device.
+    pub unsafe fn noise_budget(&self, ct: DeviceBatch, sk: &SecretKey, budget: *mut i32, noise: *mut f64) -> Result<()> {
+        check(bindgen::hipbfv_batch_noise_budget(self.h(), ct.ptr, ct.size as u32, sk.get_handle(), budget, noise, ct.count, self.stream))
+    }
+    /// `hipbfv_batch_decrypt` and [`BatchEvaluator::noise_budget`] from one phase computation: `plain` = `u64[count][N]`,
+    /// `budget` = `i32[count]`.  An item with budget 0 decrypted to garbage: `Runtime::decrypt` returns `Error::TooMuchNoise`.
+    ///
+    /// # Safety
+    /// `plain` and `budget` must be device addresses of `ct.count()` plaintexts / entries on the evaluator's device.
+    pub unsafe fn decrypt_checked(&self, ct: DeviceBatch, sk: &SecretKey, plain: *mut u64, budget: *mut i32) -> Result<()> {
+        check(bindgen::hipbfv_batch_decrypt_checked(self.h(), ct.ptr, ct.size as u32, sk.get_handle(), plain, budget, ct.count, self.stream))
     }
     /// Synchronise the stream; `Err(InternalError(COR_E_INVALIDOPERATION, ..))` if any operation since the last call
     /// produced a transparent ciphertext.

@@ -244,6 +244,26 @@ class BatchEvaluator:
         _check(_lib.load().hipbfv_batch_decrypt(self._h, _ptr(ct), ct.shape[1], secret_key.get_handle(), _ptr(out), ct.shape[0], _stream()))
         return out
 
+    def noise_budget(self, ct: torch.Tensor, secret_key, with_noise: bool = False):
+        """Decryptor_InvariantNoiseBudget per item: int32[batch] (and, with_noise, Decryptor_InvariantNoise as float64[batch]).
+        Asynchronous like the other calls; a budget of 0 means the item no longer decrypts correctly."""
+        assert ct.dim() == 4 and ct.shape[2] == self.K and ct.shape[3] == self.n
+        budget = torch.empty((ct.shape[0],), dtype=torch.int32, device=ct.device)
+        noise = torch.empty((ct.shape[0],), dtype=torch.float64, device=ct.device) if with_noise else None
+        _check(_lib.load().hipbfv_batch_noise_budget(self._h, _ptr(ct), ct.shape[1], secret_key.get_handle(), C.c_void_p(budget.data_ptr()),
+                                                     C.c_void_p(noise.data_ptr()) if with_noise else None, ct.shape[0], _stream()))
+        return (budget, noise) if with_noise else budget
+
+    def decrypt_checked(self, ct: torch.Tensor, secret_key):
+        """decrypt() and noise_budget() from one phase computation: (int64[batch, N] plaintexts, int32[batch] budgets).  An item
+        with budget 0 decrypted to garbage: the reference's Runtime::decrypt returns Error::TooMuchNoise for it."""
+        assert ct.dim() == 4 and ct.shape[2] == self.K and ct.shape[3] == self.n
+        plain = torch.empty((ct.shape[0], self.n), dtype=torch.int64, device=ct.device)
+        budget = torch.empty((ct.shape[0],), dtype=torch.int32, device=ct.device)
+        _check(_lib.load().hipbfv_batch_decrypt_checked(self._h, _ptr(ct), ct.shape[1], secret_key.get_handle(), _ptr(plain),
+                                                        C.c_void_p(budget.data_ptr()), ct.shape[0], _stream()))
+        return plain, budget
+
     def encrypt(self, plain: torch.Tensor, public_key, seed: int | bytes | None = None, first_op: int = 0) -> torch.Tensor:
         """int64[batch, N] (or one shared int64[N]) plaintexts -> fresh encryptions int64[batch', 2, K, N].
         seed: None = 512 fresh bits from the OS (production); 64 bytes = SEAL's prng_seed_type; an int = the TEST-ONLY

@@ -2958,8 +2958,8 @@ long Decryptor_Decrypt(void* h, void* encrypted, void* destination) HIPBFV_BEGIN
 HIPBFV_END
 
 // Decryptor::invariant_noise_budget (encryptor_decryptor.rs:640-660): bits(q) - bits(|t * phase mod q| centred, max over
-// coefficients) - 1, floored at 0.  The phase comes from the device; the multi-word arithmetic (one CRT composition
-// per coefficient) runs on the host -- a diagnostic, not a hot path.
+// coefficients) - 1, floored at 0.  The maximum comes from the device (Evaluator::decrypt's noise stage, one item: only its K limbs
+// travel back); the two final formulas below run on the host.
 namespace {
 struct Big {
   std::vector<u64> w;  // little-endian, fixed length
@@ -2970,20 +2970,6 @@ struct Big {
       const unsigned __int128 p = (unsigned __int128)(i < a.w.size() ? a.w[i] : 0) * m + w[i] + carry;
       w[i] = (u64)p;
       carry = (u64)(p >> 64);
-    }
-  }
-  int cmp(const Big& o) const {
-    for (size_t i = w.size(); i-- > 0;) {
-      if (w[i] != o.w[i]) return w[i] < o.w[i] ? -1 : 1;
-    }
-    return 0;
-  }
-  void sub(const Big& o) {
-    u64 borrow = 0;
-    for (size_t i = 0; i < w.size(); i++) {
-      const unsigned __int128 d = (unsigned __int128)w[i] - o.w[i] - borrow;
-      w[i] = (u64)d;
-      borrow = (u64)(d >> 64) & 1;
     }
   }
   int bits() const {
@@ -3013,54 +2999,28 @@ static long invariant_noise_norm(void* h, void* encrypted, Big* worst_out, Big* 
   EvalObj* le = c->ctx ? level_eval(&d->core, c->ctx) : nullptr;
   if (!le || !c->dev || c->size < 2) return fail(HIPBFV_E_INVALIDARG, "encrypted is not valid for encryption parameters");
   const Context& cx = *le->ctx;
-  const size_t n = cx.n(), K = cx.K();
+  const size_t K = cx.K(), len = K + 1;
   hipStream_t s = thread_stream();
-  u64* dev = g_buffers.get(K * n);
+  u64* dev = g_buffers.get(len);  // worst u64[K] | budget (one word)
   if (!dev) return from_status(kOutOfMemory);
-  std::vector<u64> ph(K * n);
+  NoiseOut out;
+  out.worst = dev;
+  out.budget = (int*)(dev + K);
+  Big worst(len);
   long hr = HIPBFV_S_OK;
-  if (int st = le->ev->phase(c->dev, c->size, d->sk->dev, dev, 1, s))
+  if (int st = le->ev->decrypt(c->dev, c->size, d->sk->dev, nullptr, 1, s, &out))
     hr = from_status(st);
-  else if (hipMemcpyAsync(ph.data(), dev, ph.size() * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+  else if (hipMemcpyAsync(worst.w.data(), dev, K * sizeof(u64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
     hr = from_status(kHipError);
-  g_buffers.put(dev, K * n);
+  g_buffers.put(dev, len);
   if (hr != HIPBFV_S_OK) return hr;
   const std::vector<u64>& q = cx.key_primes();
-  const size_t len = K + 1;
   Big Q(len);
   Q.w[0] = 1;
   for (size_t i = 0; i < K; i++) {
     Big t2(len);
     t2.add_mul(Q, q[i]);
     Q = t2;
-  }
-  Big half = Q;  // floor(q / 2)
-  for (size_t i = 0; i < len; i++) half.w[i] = (Q.w[i] >> 1) | (i + 1 < len ? Q.w[i + 1] << 63 : 0);
-  std::vector<Big> punct(K, Big(len));  // q / q_i
-  std::vector<u64> scale(K);            // t * (q/q_i)^{-1} mod q_i
-  for (size_t i = 0; i < K; i++) {
-    punct[i].w[0] = 1;
-    u64 pm = 1;
-    for (size_t j = 0; j < K; j++) {
-      if (j == i) continue;
-      Big t2(len);
-      t2.add_mul(punct[i], q[j]);
-      punct[i] = t2;
-      pm = mulmod64(pm, q[j] % q[i], q[i]);
-    }
-    scale[i] = mulmod64(cx.t() % q[i], invmod64(pm, q[i]), q[i]);
-  }
-  Big worst(len);
-  for (size_t x = 0; x < n; x++) {
-    Big v(len);
-    for (size_t i = 0; i < K; i++) v.add_mul(punct[i], mulmod64(ph[i * n + x], scale[i], q[i]));
-    while (v.cmp(Q) >= 0) v.sub(Q);
-    if (v.cmp(half) > 0) {
-      Big r = Q;
-      r.sub(v);
-      v = r;
-    }
-    if (v.cmp(worst) > 0) worst = v;
   }
   *worst_out = worst;
   *q_out = Q;
@@ -3200,6 +3160,43 @@ long hipbfv_batch_decrypt(void* evaluator, const uint64_t* ct, uint32_t size, vo
   if (!k->key || k->key->ctx.get() != e->ctx.get()) return fail(HIPBFV_E_INVALIDARG, "secret key is not valid for encryption parameters");
   ALIAS_OR_RETURN(cts(plain, e->ctx->n(), count), {cts(ct, e->ctx->ct_words(size), count)}, false);
   return from_status(e->ev->decrypt((const u64*)ct, size, k->key->dev, (u64*)plain, count, (hipStream_t)stream));
+HIPBFV_END
+// The invariant-noise measure on device batches (include/hipbfv.h): hipbfv_batch_decrypt's validation, no overlap at all between ct and
+// the outputs or between two outputs (exact byte ranges: budget is int32, noise f64), nothing launched for count == 0.  Exhausted items
+// are reported through budget only -- the evaluator's status word is not touched.
+static long noise_call(void* evaluator, const uint64_t* ct, uint32_t size, void* secret_key, uint64_t* plain, int32_t* budget, double* noise,
+                       uint64_t count, void* stream) {
+  EvalObj* e = as<EvalObj>(evaluator, kMagicEval);
+  AsymKeyObj* k = as<AsymKeyObj>(secret_key, kMagicSecretKey);
+  if (!e || !k || !ct || !budget) return HIPBFV_E_POINTER;
+  if (size < 2) return fail(HIPBFV_E_INVALIDARG, "invalid ciphertext size");
+  if (!k->key || k->key->ctx.get() != e->ctx.get()) return fail(HIPBFV_E_INVALIDARG, "secret key is not valid for encryption parameters");
+  if (!count) return HIPBFV_S_OK;
+  const Context& c = *e->ctx;
+  struct Range {
+    uintptr_t a, b;
+  };
+  const Range r[] = {{(uintptr_t)ct, (uintptr_t)ct + count * c.ct_words(size) * sizeof(u64)},
+                     {(uintptr_t)plain, plain ? (uintptr_t)plain + count * c.n() * sizeof(u64) : (uintptr_t)plain},
+                     {(uintptr_t)budget, (uintptr_t)budget + count * sizeof(int32_t)},
+                     {(uintptr_t)noise, noise ? (uintptr_t)noise + count * sizeof(double) : (uintptr_t)noise}};
+  for (size_t i = 0; i < 4; i++)
+    for (size_t j = i + 1; j < 4; j++)
+      if (r[i].a != r[i].b && r[j].a != r[j].b && r[i].a < r[j].b && r[j].a < r[i].b)
+        return fail(HIPBFV_E_INVALIDARG, "an output buffer overlaps the ciphertexts or another output (include/hipbfv.h: aliasing)");
+  NoiseOut out;
+  out.budget = (int*)budget;
+  out.noise = noise;
+  return from_status(e->ev->decrypt((const u64*)ct, size, k->key->dev, (u64*)plain, count, (hipStream_t)stream, &out));
+}
+long hipbfv_batch_noise_budget(void* evaluator, const uint64_t* ct, uint32_t size, void* secret_key, int32_t* budget, double* noise, uint64_t count,
+                               void* stream) HIPBFV_BEGIN
+  return noise_call(evaluator, ct, size, secret_key, nullptr, budget, noise, count, stream);
+HIPBFV_END
+long hipbfv_batch_decrypt_checked(void* evaluator, const uint64_t* ct, uint32_t size, void* secret_key, uint64_t* plain, int32_t* budget,
+                                  uint64_t count, void* stream) HIPBFV_BEGIN
+  if (!plain) return HIPBFV_E_POINTER;
+  return noise_call(evaluator, ct, size, secret_key, plain, budget, nullptr, count, stream);
 HIPBFV_END
 long hipbfv_batch_encrypt(void* evaluator, const uint64_t* plain, uint64_t plain_stride, void* public_key, uint64_t seed, uint64_t first_op,
                           uint64_t* ct, uint64_t count, void* stream) HIPBFV_BEGIN

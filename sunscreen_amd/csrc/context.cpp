@@ -407,6 +407,7 @@ Context::~Context() {
   if (tw_fwd_) (void)hipFree(tw_fwd_);
   if (tw_inv_) (void)hipFree(tw_inv_);
   if (batch_map_) (void)hipFree(batch_map_);
+  if (noise_) (void)hipFree(noise_);
 }
 
 Context* Context::create(u32 n, const std::vector<u64>& key_primes, u64 t, int device, std::string* err) {
@@ -849,6 +850,25 @@ Context* Context::create(u32 n, const std::vector<u64>& key_primes, u64 t, int d
     if (!invm(gamma % t, t, &inv)) return fail("gamma not invertible mod t");
     h.inv_gamma_mod_t = make_mulop(inv, t);
   }
+  // ---- invariant-noise measure (NoiseConsts): the exact composition sum_i y_i * (Q/q_i) and its reduction mod Q ----
+  NoiseConsts nc{};
+  {
+    nc.K = K;
+    nc.q_bits = (u32)q_bits;
+    for (u32 i = 0; i < K; i++) {
+      BigUint punct;
+      punct.w[0] = 1;
+      for (u32 j = 0; j < K; j++)
+        if (j != i) punct.mul(q[j]);
+      for (size_t l = 0; l < punct.w.size() && l < K; l++) nc.punct[i][l] = punct.w[l];
+      u64 inv_punct;
+      invm(prod_mod(q, q[i], (int)i), q[i], &inv_punct);
+      nc.scale[i] = make_mulop(mulm(t % q[i], inv_punct, q[i]), q[i]);
+      nc.inv_q[i] = 1.0 / (double)q[i];
+    }
+    for (size_t l = 0; l < Q.w.size() && l < K; l++) nc.q[l] = Q.w[l];
+    for (u32 l = 0; l < K; l++) nc.half[l] = (nc.q[l] >> 1) | (l + 1 < K ? nc.q[l + 1] << 63 : 0);  // Q odd: floor(Q/2) = (Q-1)/2
+  }
   // BatchEncoder matrix_reps_index_map (SEAL batchencoder.cpp; seal_fhe/src/encoder.rs:75-190)
   std::vector<u32> bmap;
   if (c->batching_) {
@@ -875,6 +895,9 @@ Context* Context::create(u32 n, const std::vector<u64>& key_primes, u64 t, int d
       hipMemcpy(c->tw_inv_, twi.data(), tw_bytes, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(c->dev_, &h, sizeof(DevCtx), hipMemcpyHostToDevice) != hipSuccess)
     return fail("hipMemcpy failed");
+  if (hipMalloc((void**)&c->noise_, sizeof(NoiseConsts)) != hipSuccess ||
+      hipMemcpy(c->noise_, &nc, sizeof(NoiseConsts), hipMemcpyHostToDevice) != hipSuccess)
+    return fail("hipMalloc failed");
   if (!bmap.empty()) {
     if (hipMalloc((void**)&c->batch_map_, bmap.size() * sizeof(u32)) != hipSuccess ||
         hipMemcpy(c->batch_map_, bmap.data(), bmap.size() * sizeof(u32), hipMemcpyHostToDevice) != hipSuccess)

@@ -53,6 +53,7 @@ class Context {
   int level() const { return level_; }
   void set_chain_enabled(bool on) { chain_enabled_ = on; }  // SEALContext_Create(expand_mod_chain = false)  // 0 = the context the user created
   const u32* batch_index_map() const { return batch_map_; }  // device u32[n]: BatchEncoder matrix_reps_index_map
+  const NoiseConsts* noise_consts() const { return noise_; }  // device: the invariant-noise measure's constants
   size_t ct_words(size_t size) const { return size * (size_t)host_.K * host_.n; }
   size_t key_words() const { return (size_t)host_.K * 2 * host_.KK * host_.n; }
 
@@ -63,6 +64,7 @@ class Context {
   MulOp* tw_fwd_ = nullptr;
   MulOp* tw_inv_ = nullptr;
   u32* batch_map_ = nullptr;
+  NoiseConsts* noise_ = nullptr;
   int device_ = 0;
   int level_ = 0;
   bool chain_enabled_ = true;

@@ -178,6 +178,20 @@ struct DevCtx {
   u32 pad2;
 };
 
+// The invariant-noise measure (kernels_client.hip noise_partial_kernel; SEAL Decryptor::invariant_noise_budget) of one context: its own
+// device block beside the DevCtx, built once when the context is created.  Big integers are little-endian u64 limbs; Q = q_0 ... q_{K-1}
+// (the data primes, K <= 16) fits in K limbs.  Every entry is uniform across a launch: the kernels read them through scalar loads.
+constexpr int kMaxData = kMaxKey - 1;
+struct NoiseConsts {
+  u64 punct[kMaxData][kMaxData];  // limbs of Q / q_i
+  MulOp scale[kMaxData];           // t * (Q/q_i)^{-1} mod q_i
+  double inv_q[kMaxData];          // 1.0 / q_i (the quotient estimate of the reduction mod Q)
+  u64 q[kMaxData];                 // limbs of Q
+  u64 half[kMaxData];              // limbs of (Q - 1) / 2: a value above it is centred to Q - v
+  u32 q_bits;                      // bits(Q)
+  u32 K;
+};
+
 // the residue lists are read through aligned 32-bit scalar loads (kernels_split.hip residue_of)
 static_assert(offsetof(DevCtx, mid_res_d) % 4 == 0 && offsetof(DevCtx, mid_res_dp) % 4 == 0 && offsetof(DevCtx, mid_res_i) % 4 == 0 &&
                   offsetof(DevCtx, ks_res_d) % 4 == 0 && offsetof(DevCtx, ks_res_dp) % 4 == 0 && offsetof(DevCtx, ks_res_i) % 4 == 0,

@@ -132,6 +132,14 @@ struct KeySel {
   bool present() const { return per_item() ? nkeys != 0 : key != nullptr; }
 };
 
+// The invariant-noise outputs of Evaluator::decrypt (device memory, one entry per item): budget = SEAL's invariant_noise_budget,
+// noise (optional) = the fork's invariant_noise as a double, worst (optional) = u64[count][K] limbs of max_x |[t * phase(x)]_q|.
+struct NoiseOut {
+  int* budget = nullptr;
+  double* noise = nullptr;
+  u64* worst = nullptr;
+};
+
 // RAII lease of a scratch-pool buffer on a stream
 struct ScratchGuard {
   ScratchPool& pool;
@@ -204,7 +212,8 @@ class Evaluator {
   // ---- the steps either side of the path (evaluator_client.cpp) ----
   int batch_encode(const u64* values, u64* plain, size_t count, bool is_signed, u32* bad_host, hipStream_t s);
   int batch_decode(const u64* plain, u64* values, size_t count, bool is_signed, hipStream_t s);
-  int decrypt(const u64* ct, u32 size, const u64* sk_ntt, u64* plain, size_t count, hipStream_t s);
+  // plain (u64[count][N]) and / or noise: the plaintexts, the invariant-noise measure, or both from one phase computation
+  int decrypt(const u64* ct, u32 size, const u64* sk_ntt, u64* plain, size_t count, hipStream_t s, const NoiseOut* noise = nullptr);
   int keygen_secret(const RngSeed& seed, u64* sk_coeff, u64* sk_ntt, hipStream_t s);
   int keygen_zero_encryptions(const RngSeed& seed, u64 stream, const u64* sk_ntt, const u64* w, u64* key, u32 count, hipStream_t s);
   // single encryptions that also return the sampled polynomials (fork-only API used by logproof), and secret-key encryption
@@ -227,7 +236,6 @@ class Evaluator {
   int multiply_plain_ntt(const u64* ct, u32 size, const u64* pntt, size_t pnstride, u64* out, size_t count, hipStream_t s);
   // the transparent-result watch of one n-ary sum launch (device descriptor table)
   int note_nary(const NaryOut* douts, u32 nouts, u32 batch, hipStream_t s);
-  int phase(const u64* ct, u32 size, const u64* sk_ntt, u64* out, size_t count, hipStream_t s);
   int encrypt(const u64* plain, size_t pstride, const u64* pk, const RngSeed& seed, u64 first_op, u64* ct2, size_t count, hipStream_t s);
 
   // ---- NTT entry points (BASELINE config 2) ----

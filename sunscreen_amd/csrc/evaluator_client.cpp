@@ -78,19 +78,24 @@ int Evaluator::batch_decode(const u64* plain, u64* values, size_t count, bool is
   return kOk;
 }
 
-// plain[op] = Decryptor_Decrypt(ct[op]) ; ct: u64[count][size][K][N], sk: u64[KK][N] in NTT form (SEAL SecretKey data)
-int Evaluator::decrypt(const u64* ct, u32 size, const u64* sk_ntt, u64* plain, size_t count, hipStream_t s) {
+// plain[op] = Decryptor_Decrypt(ct[op]) ; ct: u64[count][size][K][N], sk: u64[KK][N] in NTT form (SEAL SecretKey data).
+// One phase computation c0 + c1*s + c2*s^2 ... per chunk feeds the plaintext rounding (plain != nullptr), the invariant-noise measure
+// (noise != nullptr: NoiseOut) or both in one pass over the phase; at least one of the two outputs must be given.
+int Evaluator::decrypt(const u64* ct, u32 size, const u64* sk_ntt, u64* plain, size_t count, hipStream_t s, const NoiseOut* noise) {
   const DevCtx& h = ctx_->host();
   if (size < 2 || !sk_ntt) return kInvalidArg;
+  if (!plain && !(noise && noise->budget)) return kInvalidArg;
   if (h.logn > 15) return kUnsupported;
   const u32 n = h.n, K = h.K;
   const size_t per = (size_t)(size - 1) * K;  // transformed residue polynomials per op
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, 65535 / std::max<size_t>(per, 1)));
   const size_t cc = std::min(chunk, count);
-  ScratchGuard sg(pool_, cc * (per + K) * n * sizeof(u64), s);
+  const size_t slab_words = noise ? (size_t)noise_blocks(n) * K : 0;  // per op: the noise measure's per-block maxima
+  ScratchGuard sg(pool_, cc * ((per + K) * n + slab_words) * sizeof(u64), s);
   if (!sg.p) return kOutOfMemory;
   u64* ctn = (u64*)sg.p;
   u64* acc = ctn + cc * per * n;
+  u64* slab = acc + cc * K * n;
   const NttPlan plan = range_plan(K);
   const size_t cs = ctx_->ct_words(size);
   for (size_t off = 0; off < count; off += chunk) {
@@ -105,7 +110,14 @@ int Evaluator::decrypt(const u64* ct, u32 size, const u64* sk_ntt, u64* plain, s
       HC_CHECK(launch_dot_secret(ctx_->dev(), n, K, ctn, size, sk_ntt, acc, c, s));
       HB_LAUNCH_CLIENT(kKernNttInv, c * K, launch_ntt(ctx_->dev(), h.tw_inv, h.logn, acc, c * K, plan, true, 0, s));
     }
-    HC_CHECK(launch_decrypt_round(ctx_->dev(), n, ct + off * cs, size, acc, plain + off * n, c, s));
+    u64* pl = plain ? plain + off * n : nullptr;
+    if (!noise) {
+      HC_CHECK(launch_decrypt_round(ctx_->dev(), n, ct + off * cs, size, acc, pl, c, s));
+      continue;
+    }
+    HC_CHECK(launch_noise_partial(ctx_->dev(), ctx_->noise_consts(), n, K, ct + off * cs, size, acc, pl, slab, c, s));
+    HC_CHECK(launch_noise_final(ctx_->noise_consts(), n, K, slab, noise->worst ? noise->worst + off * K : nullptr, noise->budget + off,
+                                noise->noise ? noise->noise + off : nullptr, c, s));
   }
   return kOk;
 }
@@ -255,31 +267,6 @@ int Evaluator::note_nary(const NaryOut* douts, u32 nouts, u32 batch, hipStream_t
   u32* status = watch_status();
   if (!status || !nouts) return kOk;
   HC_CHECK(launch_transparent_watch_nary(ctx_->dev(), douts, nouts, batch, status, s));
-  return kOk;
-}
-
-// phase[op][i] = (c0 + c1*s + c2*s^2 ...) mod q_i in coefficient form: u64[count][K][N].  The quantity SEAL's
-// Decryptor::invariant_noise_budget measures (diagnostics; not a hot path: one small launch per op for the last step)
-int Evaluator::phase(const u64* ct, u32 size, const u64* sk_ntt, u64* out, size_t count, hipStream_t s) {
-  const DevCtx& h = ctx_->host();
-  if (size < 2 || !sk_ntt) return kInvalidArg;
-  if (h.logn > 15) return kUnsupported;
-  const u32 n = h.n, K = h.K;
-  const size_t per = (size_t)(size - 1) * K;
-  ScratchGuard sg(pool_, per * n * sizeof(u64), s);
-  if (!sg.p) return kOutOfMemory;
-  u64* ctn = (u64*)sg.p;
-  const NttPlan plan = range_plan(K);
-  const size_t cs = ctx_->ct_words(size);
-  for (size_t op = 0; op < count; op++) {
-    const u64* c = ct + op * cs;
-    u64* acc = out + op * (size_t)K * n;
-    HC_CHECK(hipMemcpyAsync(ctn, c + (size_t)K * n, per * n * sizeof(u64), hipMemcpyDeviceToDevice, s));
-    HC_CHECK(launch_ntt(ctx_->dev(), h.tw_fwd, h.logn, ctn, per, plan, false, 0, s));
-    HC_CHECK(launch_dot_secret(ctx_->dev(), n, K, ctn, size, sk_ntt, acc, 1, s));
-    HC_CHECK(launch_ntt(ctx_->dev(), h.tw_inv, h.logn, acc, K, plan, true, 0, s));
-    HC_CHECK(launch_eltwise(ctx_->dev(), n, acc, c, acc, K, 0, s));
-  }
   return kOk;
 }
 

@@ -130,6 +130,13 @@ hipError_t launch_batch_scatter(const DevCtx* ctx, u32 n, const u32* map, const 
 hipError_t launch_batch_gather(const DevCtx* ctx, u32 n, const u32* map, const u64* tmp, u64* values, size_t ops, int is_signed, hipStream_t s);
 hipError_t launch_dot_secret(const DevCtx* ctx, u32 n, u32 K, const u64* ctn, u32 size, const u64* sk, u64* acc, size_t ops, hipStream_t s);
 hipError_t launch_decrypt_round(const DevCtx* ctx, u32 n, const u64* ct, u32 size, const u64* acc, u64* plain, size_t ops, hipStream_t s);
+// invariant noise of `ops` items from the decrypt phase (c0 + acc): slab u64[ops][noise_blocks(n)][K] per-block maxima, then per item
+// worst u64[ops][K] (optional), budget i32[ops], noise f64[ops] (optional); plain (optional) also receives the decrypt_round result
+u32 noise_blocks(u32 n);
+hipError_t launch_noise_partial(const DevCtx* ctx, const NoiseConsts* nc, u32 n, u32 K, const u64* ct, u32 size, const u64* acc, u64* plain,
+                                u64* slab, size_t ops, hipStream_t s);
+hipError_t launch_noise_final(const NoiseConsts* nc, u32 n, u32 K, const u64* slab, u64* worst, int* budget, double* noise, size_t ops,
+                              hipStream_t s);
 hipError_t launch_encrypt_sample(const DevCtx* ctx, u32 n, const RngSeed& seed, u64 op0, u64* u, u64* e, size_t ops, hipStream_t s);
 hipError_t launch_ntt_inv_dyadic(const DevCtx* ctx, const MulOp* tw_inv, u32 logn, const u64* a, const u64* b, u64* c, u32 nmod, u32 nb, u32 bstride,
                                  size_t ops, hipStream_t s);

@@ -79,34 +79,276 @@ __global__ __launch_bounds__(kClientThreads) void dot_secret_kernel(const DevCtx
   acc[((size_t)op * K + i) * n + x] = a;
 }
 
-// plain[op][x] = round(t * (c0 + acc) / q) mod t, SEAL RNSTool::decrypt_scale_and_round:
+// round(t * phase / q) mod t of one coefficient, SEAL RNSTool::decrypt_scale_and_round:
 //   y_i = phase_i * t * gamma * (q/q_i)^{-1} mod q_i ; fast base conversion q -> {t, gamma} ; times -q^{-1} ;
 //   centred gamma correction ; times gamma^{-1} mod t.
+// add() takes the residues one by one (i = 0 .. K-1), finish() gives the plaintext coefficient: decrypt_round_kernel and
+// noise_partial_kernel share this one piece of plaintext arithmetic.
+struct DecryptRound {
+  u128 at = 0, ag = 0;
+  __device__ __forceinline__ void add(const DevCtx* __restrict__ ctx, u32 i, u64 phase) {
+    const u64 y = mul_shoup(phase, ctx->dec_scale_q[i], ctx->mod[i].q);
+    at += (u128)y * ctx->q_to_t[i];
+    ag += (u128)y * ctx->q_to_gamma[i];
+  }
+  __device__ __forceinline__ u64 finish(const DevCtx* __restrict__ ctx) const {
+    const u64 t = ctx->t, gamma = ctx->gamma.q;
+    const u64 a = mul_shoup(reduce128(at, ctx->tm), ctx->neg_inv_q_mod_t, t);
+    const u64 g = mul_shoup(reduce128_fast(ag, ctx->gamma), ctx->neg_inv_q_mod_gamma, gamma);
+    u64 r;
+    if (g > (gamma >> 1))
+      r = add_mod(a, reduce64(gamma - g, ctx->tm), t);
+    else
+      r = sub_mod(a, reduce64(g, ctx->tm), t);
+    if (r) r = mul_shoup(r, ctx->inv_gamma_mod_t, t);
+    return r;
+  }
+};
+
+// plain[op][x] = round(t * (c0 + acc) / q) mod t
 __global__ __launch_bounds__(kClientThreads) void decrypt_round_kernel(const DevCtx* __restrict__ ctx, const u64* __restrict__ ct, u32 size,
                                                                        const u64* __restrict__ acc, u64* __restrict__ plain) {
   const u32 n = ctx->n, K = ctx->K;
   const u32 x = blockIdx.x * kClientThreads + threadIdx.x;
   const u32 op = blockIdx.y;
   if (x >= n) return;
-  u128 at = 0, ag = 0;
+  DecryptRound dr;
   for (u32 i = 0; i < K; i++) {
-    const DevMod& dm = ctx->mod[i];
     const u64 c0 = ct[((size_t)op * size * K + i) * n + x];
-    const u64 phase = add_mod(c0, acc[((size_t)op * K + i) * n + x], dm.q);
-    const u64 y = mul_shoup(phase, ctx->dec_scale_q[i], dm.q);
-    at += (u128)y * ctx->q_to_t[i];
-    ag += (u128)y * ctx->q_to_gamma[i];
+    dr.add(ctx, i, add_mod(c0, acc[((size_t)op * K + i) * n + x], ctx->mod[i].q));
   }
-  const u64 t = ctx->t, gamma = ctx->gamma.q;
-  const u64 a = mul_shoup(reduce128(at, ctx->tm), ctx->neg_inv_q_mod_t, t);
-  const u64 g = mul_shoup(reduce128_fast(ag, ctx->gamma), ctx->neg_inv_q_mod_gamma, gamma);
-  u64 r;
-  if (g > (gamma >> 1))
-    r = add_mod(a, reduce64(gamma - g, ctx->tm), t);
-  else
-    r = sub_mod(a, reduce64(g, ctx->tm), t);
-  if (r) r = mul_shoup(r, ctx->inv_gamma_mod_t, t);
-  plain[(size_t)op * n + x] = r;
+  plain[(size_t)op * n + x] = dr.finish(ctx);
+}
+
+// ---- invariant noise (SEAL Decryptor::invariant_noise_budget, util::poly_infty_norm_coeffmod) ----
+// worst[op] = max_x |[t * phase(x)]_Q| (centred), exactly, as KC limbs.  Stage 1 (noise_partial_kernel): every block takes
+// kNoiseSpan coefficients of one item and writes the maximum over them to slab[op][block]; stage 2 (noise_final_kernel): one wave
+// per item reduces its nb slab entries.  No atomics: the result does not depend on the order in which blocks finish.
+constexpr int kNoiseThreads = 256;
+constexpr int kNoiseCoeffs = 4;  // coefficients per thread (kNoiseThreads apart: coalesced)
+constexpr u32 kNoiseSpan = kNoiseThreads * kNoiseCoeffs;
+u32 noise_blocks(u32 n) { return (n + kNoiseSpan - 1) / kNoiseSpan; }
+
+template <int KC>
+__device__ __forceinline__ bool big_gt(const u64 (&a)[KC], const u64 (&b)[KC]) {
+  bool gt = false, eq = true;
+#pragma unroll
+  for (int l = KC - 1; l >= 0; l--) {
+    gt = gt || (eq && a[l] > b[l]);
+    eq = eq && a[l] == b[l];
+  }
+  return gt;
+}
+template <int KC>
+__device__ __forceinline__ void big_max_into(u64 (&best)[KC], const u64 (&v)[KC]) {
+  const bool gt = big_gt<KC>(v, best);
+#pragma unroll
+  for (int l = 0; l < KC; l++) best[l] = gt ? v[l] : best[l];
+}
+// the maximum over the 64 lanes of a wave, in every lane
+template <int KC>
+__device__ __forceinline__ void wave_big_max(u64 (&best)[KC]) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    u64 o[KC];
+#pragma unroll
+    for (int l = 0; l < KC; l++) o[l] = __shfl_xor(best[l], off, 64);
+    big_max_into<KC>(best, o);
+  }
+}
+
+// v = (t * phase mod Q), centred (Q - v when v >= (Q+1)/2), from the residues phase_i:
+//   y_i = phase_i * t * (Q/q_i)^{-1} mod q_i ; v' = sum_i y_i * (Q/q_i) < KC * Q (KC + 1 limbs) ; v = v' - k Q.
+// v' / Q = sum_i y_i / q_i exactly, so k = floor(sum_i y_i / q_i) is the quotient.  In doubles the sum (< 16) carries an absolute
+// error below 2^-44; floor(sum - 2^-30) is the quotient or one less (never more), and one conditional subtraction finishes.
+template <int KC>
+struct NoiseCompose {
+  u64 v[KC + 1];
+  double est = 0.0;
+  __device__ __forceinline__ NoiseCompose() {
+#pragma unroll
+    for (int l = 0; l <= KC; l++) v[l] = 0;
+  }
+  __device__ __forceinline__ void add(const NoiseConsts* __restrict__ nc, int i, u64 phase, u64 qi) {
+    const u64 y = mul_shoup(phase, nc->scale[i], qi);
+    est += (double)y * nc->inv_q[i];
+    constexpr int L = KC > 1 ? KC - 1 : 1;  // limbs of Q / q_i (< 2^(64 (KC - 1)); 1 when KC = 1)
+    u64 carry = 0;
+#pragma unroll
+    for (int l = 0; l < L; l++) {
+      const u128 t = (u128)y * nc->punct[i][l] + v[l] + carry;
+      v[l] = (u64)t;
+      carry = (u64)(t >> 64);
+    }
+#pragma unroll
+    for (int l = L; l <= KC; l++) {
+      const u128 t = (u128)v[l] + carry;
+      v[l] = (u64)t;
+      carry = (u64)(t >> 64);
+    }
+  }
+  __device__ __forceinline__ void finish(const NoiseConsts* __restrict__ nc, u64 (&out)[KC]) const {
+    const double kd = floor(est - 0x1p-30);
+    const u64 k = kd > 0.0 ? (u64)kd : 0;
+    u64 r[KC + 1];
+    u64 mcarry = 0, borrow = 0;
+#pragma unroll
+    for (int l = 0; l < KC; l++) {  // r = v - k Q
+      const u128 m = (u128)k * nc->q[l] + mcarry;
+      mcarry = (u64)(m >> 64);
+      const u128 d = (u128)v[l] - (u64)m - borrow;
+      r[l] = (u64)d;
+      borrow = (u64)(d >> 64) & 1;
+    }
+    r[KC] = v[KC] - mcarry - borrow;
+    // r < 2Q: subtract Q once if r >= Q
+    bool ge = r[KC] != 0;
+    if (!ge) {
+      u64 qq[KC];
+#pragma unroll
+      for (int l = 0; l < KC; l++) qq[l] = nc->q[l];
+      u64 rr[KC];
+#pragma unroll
+      for (int l = 0; l < KC; l++) rr[l] = r[l];
+      ge = !big_gt<KC>(qq, rr);
+    }
+    borrow = 0;
+#pragma unroll
+    for (int l = 0; l < KC; l++) {
+      const u128 d = (u128)r[l] - (ge ? nc->q[l] : 0ull) - borrow;
+      r[l] = (u64)d;
+      borrow = (u64)(d >> 64) & 1;
+    }
+    // centre: v > (Q - 1) / 2  ->  Q - v
+    u64 hh[KC], rr[KC];
+#pragma unroll
+    for (int l = 0; l < KC; l++) {
+      hh[l] = nc->half[l];
+      rr[l] = r[l];
+    }
+    const bool neg = big_gt<KC>(rr, hh);
+    borrow = 0;
+#pragma unroll
+    for (int l = 0; l < KC; l++) {
+      const u128 d = (u128)nc->q[l] - r[l] - borrow;
+      borrow = (u64)(d >> 64) & 1;
+      out[l] = neg ? (u64)d : r[l];
+    }
+  }
+};
+
+// slab[op][blockIdx.x][KC] = max over this block's coefficients; PLAIN: also plain[op][x] (the decrypt_round_kernel result) from the
+// same loads of c0 and acc
+template <int KC, bool PLAIN>
+__global__ __launch_bounds__(kNoiseThreads) void noise_partial_kernel(const DevCtx* __restrict__ ctx, const NoiseConsts* __restrict__ nc,
+                                                                      const u64* __restrict__ ct, u32 size, const u64* __restrict__ acc,
+                                                                      u64* __restrict__ plain, u64* __restrict__ slab) {
+  __shared__ u64 part[kNoiseThreads / 64][KC];
+  const u32 n = ctx->n;
+  const u32 op = blockIdx.y;
+  u64 best[KC];
+#pragma unroll
+  for (int l = 0; l < KC; l++) best[l] = 0;
+  for (int j = 0; j < kNoiseCoeffs; j++) {
+    const u32 x = blockIdx.x * kNoiseSpan + j * kNoiseThreads + threadIdx.x;
+    if (x >= n) break;
+    NoiseCompose<KC> nco;
+    DecryptRound dr;
+#pragma unroll
+    for (int i = 0; i < KC; i++) {
+      const u64 qi = ctx->mod[i].q;
+      const u64 phase = add_mod(ct[((size_t)op * size * KC + i) * n + x], acc[((size_t)op * KC + i) * n + x], qi);
+      if (PLAIN) dr.add(ctx, i, phase);
+      nco.add(nc, i, phase, qi);
+    }
+    if (PLAIN) plain[(size_t)op * n + x] = dr.finish(ctx);
+    u64 v[KC];
+    nco.finish(nc, v);
+    big_max_into<KC>(best, v);
+  }
+  wave_big_max<KC>(best);
+  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  if (lane == 0) {
+#pragma unroll
+    for (int l = 0; l < KC; l++) part[wave][l] = best[l];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (u32 w = 1; w < kNoiseThreads / 64; w++) {
+      u64 o[KC];
+#pragma unroll
+      for (int l = 0; l < KC; l++) o[l] = part[w][l];
+      big_max_into<KC>(best, o);
+    }
+    u64* dst = slab + ((size_t)op * gridDim.x + blockIdx.x) * KC;
+#pragma unroll
+    for (int l = 0; l < KC; l++) dst[l] = best[l];
+  }
+}
+
+// a (KC limbs, non-zero) ~ m * 2^e with m = the top 64 significant bits rounded to a double (relative error < 2^-52)
+template <int KC>
+__device__ __forceinline__ double big_top_double(const u64 (&a)[KC], int* e) {
+  int j = 0;
+#pragma unroll
+  for (int l = 0; l < KC; l++)
+    if (a[l]) j = l;
+  u64 hi = a[0], lo = 0;
+#pragma unroll
+  for (int l = 1; l < KC; l++)
+    if (l == j) {
+      hi = a[l];
+      lo = a[l - 1];
+    }
+  const int s = __clzll(hi);
+  const u64 top = s ? (hi << s) | (lo >> (64 - s)) : hi;
+  *e = 64 * j - s;
+  return (double)top;
+}
+template <int KC>
+__device__ __forceinline__ int big_bits(const u64 (&a)[KC]) {
+  int b = 0;
+#pragma unroll
+  for (int l = 0; l < KC; l++)
+    if (a[l]) b = 64 * l + 64 - __clzll(a[l]);
+  return b;
+}
+
+// one wave per item: worst = max over the item's nb slab entries; budget = max(0, bits(Q) - bits(worst) - 1) (SEAL
+// invariant_noise_budget); noise = worst / Q (the fork's invariant_noise).  worst / noise may be null.
+template <int KC>
+__global__ __launch_bounds__(64) void noise_final_kernel(const NoiseConsts* __restrict__ nc, const u64* __restrict__ slab, u32 nb,
+                                                         u64* __restrict__ worst, int* __restrict__ budget, double* __restrict__ noise) {
+  const u32 op = blockIdx.x;
+  u64 best[KC];
+#pragma unroll
+  for (int l = 0; l < KC; l++) best[l] = 0;
+  for (u32 b = threadIdx.x; b < nb; b += 64) {
+    u64 o[KC];
+#pragma unroll
+    for (int l = 0; l < KC; l++) o[l] = slab[((size_t)op * nb + b) * KC + l];
+    big_max_into<KC>(best, o);
+  }
+  wave_big_max<KC>(best);
+  if (threadIdx.x != 0) return;
+  if (worst) {
+#pragma unroll
+    for (int l = 0; l < KC; l++) worst[(size_t)op * KC + l] = best[l];
+  }
+  const int wb = big_bits<KC>(best);
+  budget[op] = max(0, (int)nc->q_bits - wb - 1);
+  if (noise) {
+    double r = 0.0;
+    if (wb) {
+      u64 q[KC];
+#pragma unroll
+      for (int l = 0; l < KC; l++) q[l] = nc->q[l];
+      int ew, eq;
+      const double mw = big_top_double<KC>(best, &ew), mq = big_top_double<KC>(q, &eq);
+      r = ldexp(mw / mq, ew - eq);
+    }
+    noise[op] = r;
+  }
 }
 
 // ---- Encryptor ----
@@ -623,6 +865,42 @@ hipError_t launch_dot_secret(const DevCtx* ctx, u32 n, u32 K, const u64* ctn, u3
   dot_secret_kernel<<<cgrid(n, K, (u32)ops), kClientThreads, 0, s>>>(ctx, ctn, size, sk, acc);
   return hipGetLastError();
 }
+#define HB_NOISE_KC(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+hipError_t launch_noise_partial(const DevCtx* ctx, const NoiseConsts* nc, u32 n, u32 K, const u64* ct, u32 size, const u64* acc, u64* plain,
+                                u64* slab, size_t ops, hipStream_t s) {
+  if (!ops) return hipSuccess;
+  const dim3 grid(noise_blocks(n), (u32)ops);
+#define HB_NP(K_)                                                                                                          \
+  case K_:                                                                                                                 \
+    if (plain)                                                                                                             \
+      noise_partial_kernel<K_, true><<<grid, kNoiseThreads, 0, s>>>(ctx, nc, ct, size, acc, plain, slab);                  \
+    else                                                                                                                   \
+      noise_partial_kernel<K_, false><<<grid, kNoiseThreads, 0, s>>>(ctx, nc, ct, size, acc, nullptr, slab);               \
+    break;
+  switch (K) {
+    HB_NOISE_KC(HB_NP)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef HB_NP
+  return hipGetLastError();
+}
+hipError_t launch_noise_final(const NoiseConsts* nc, u32 n, u32 K, const u64* slab, u64* worst, int* budget, double* noise, size_t ops,
+                              hipStream_t s) {
+  if (!ops) return hipSuccess;
+#define HB_NF(K_)                                                                                           \
+  case K_:                                                                                                  \
+    noise_final_kernel<K_><<<dim3((u32)ops), 64, 0, s>>>(nc, slab, noise_blocks(n), worst, budget, noise);   \
+    break;
+  switch (K) {
+    HB_NOISE_KC(HB_NF)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef HB_NF
+  return hipGetLastError();
+}
+#undef HB_NOISE_KC
 hipError_t launch_decrypt_round(const DevCtx* ctx, u32 n, const u64* ct, u32 size, const u64* acc, u64* plain, size_t ops, hipStream_t s) {
   decrypt_round_kernel<<<cgrid(n, (u32)ops), kClientThreads, 0, s>>>(ctx, ct, size, acc, plain);
   return hipGetLastError();
