@@ -239,7 +239,11 @@ long hipbfv_set_device(int device);                            /* HIP device use
 /* SEAL_THROW_ON_TRANSPARENT_CIPHERTEXT switch (seal_fhe `transparent-ciphertexts` feature): default on */
 long hipbfv_set_throw_on_transparent(bool enabled);
 
-/* Context shortcuts: build a context straight from raw parameters */
+/* Context shortcuts: build a context straight from raw parameters.
+ * Accepted: poly_modulus_degree a power of two in [1024, 32768]; distinct primes below 2^60, each == 1 mod 2n; a plain modulus t
+ * in [2, 2^60) that shares no factor with the data primes (SEAL's bit-count and coprimality rules).  Every such t is supported,
+ * batching or not, odd or a power of two, above a data prime or not.  Anything else fails with E_INVALIDARG (the oracle model
+ * does not check t; tests/test_gpu_plain_modulus.py checks the refusals). */
 long hipbfv_Context_Create(uint64_t poly_modulus_degree, const uint64_t *coeff_modulus, uint64_t coeff_count,
                            uint64_t plain_modulus, void **context);
 long hipbfv_Context_Info(void *context, uint64_t *poly_modulus_degree, uint64_t *data_primes, uint64_t *key_primes,

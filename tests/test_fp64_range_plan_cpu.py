@@ -41,7 +41,20 @@ def _fp64_primes():
     # the auxiliary bases are chosen below 2^48; the policy's hard limit is 2^50
     primes.update(O.get_primes(2 * 16384, 47, 3))
     primes.update(O.get_primes(2 * 16384, 50, 2))
+    primes.update(t for _, t in _plain_batching_moduli())
     return sorted(p for p in primes if p < (1 << 50))
+
+
+def _plain_batching_moduli():
+    """The batching plain moduli the BatchEncoder transforms over Z_t with the FP64 policy: PlainModulus::batching(n, b) for every
+    b below 50 at which it finds a prime (plan_f64_path admits t < 2^50)."""
+    out = set()
+    for n in (4096, 8192, 16384):
+        for b in range(2, 50):
+            t = O.plain_batching(n, b)
+            if t:
+                out.add((n, t))
+    return sorted(out)
 
 
 @pytest.mark.parametrize("q", _fp64_primes())
@@ -155,6 +168,35 @@ def test_range_plans_of_the_default_primes_hold_under_an_independent_model(n):
         assert mod.peak < room, (n, q, mod.peak, room)
         # head / middle / tail transforms
         _replay_split_plan(q, logn, sfmask, simask)
+
+
+def _replay_whole_plan(q, logn, fmask, imask):
+    """The whole-polynomial (16 elements per thread) plan of one modulus against the independent model."""
+    mod = _Model(q)
+    rad = _whole_radices(logn)
+    m = 1.0
+    for p, r in enumerate(rad):
+        m = mod.reduce_by_mask(m, fmask, p)
+        for _ in range(r):
+            m = mod.fwd_stage(m)
+    mi = 1.0
+    for p in range(len(rad)):
+        mi = mod.reduce_by_mask(mi, imask, p)
+        for _ in range(rad[len(rad) - 1 - p]):
+            mi = mod.inv_stage(mi)
+    assert mod.peak < LIMIT / q, (q, logn, mod.peak)
+
+
+@pytest.mark.parametrize("n,t", _plain_batching_moduli())
+def test_range_plans_of_the_batching_plain_moduli_hold_under_the_independent_model(n, t):
+    """BatchEncoder encode / decode run the whole-polynomial NTT over Z_t (evaluator_client.cpp, single_mod_plan(t_mod)); every
+    batching t below 2^50 takes the FP64 policy there, so its plan must hold like a data prime's."""
+    logn = n.bit_length() - 1
+    use, fmask, imask, split, sfmask, simask = _plan(t, logn)
+    assert use == 1, (n, t)
+    _replay_whole_plan(t, logn, fmask, imask)
+    if split:
+        _replay_split_plan(t, logn, sfmask, simask)
 
 
 PLAN_STORE_REDUCE = 1 << 30  # devctx.hpp kPlanStoreReduce / kPlanScaleReduce

@@ -117,27 +117,36 @@ def behz_multiply_over_the_integers(a: np.ndarray, b: np.ndarray, q: list[int], 
     return out
 
 
+# (name, n, data prime bits or None for the default set, bits of a batching t or None, explicit t or None, size_a, size_b)
 CASES = [
-    ("n1024_2x30", 1024, [30, 30, 31], 16, 2, 2),
-    ("n1024_1x27", 1024, [27, 28], 14, 2, 2),
-    ("n2048_54_55", 2048, [54, 55], 16, 2, 2),
-    ("n1024_3x40_size3x2", 1024, [40, 41, 40, 42], 20, 3, 2),
-    ("n4096_default", 4096, None, 17, 2, 2),
-    ("n8192_default_t20", 8192, None, 20, 2, 2),
-    ("n8192_3x54", 8192, [54, 54, 54, 56], 20, 2, 2),
-    ("n16384_default_t20", 16384, None, 20, 2, 2),  # K = 8: the configuration whose auxiliary base the library shortened
+    ("n1024_2x30", 1024, [30, 30, 31], 16, None, 2, 2),
+    ("n1024_1x27", 1024, [27, 28], 14, None, 2, 2),
+    ("n2048_54_55", 2048, [54, 55], 16, None, 2, 2),
+    ("n1024_3x40_size3x2", 1024, [40, 41, 40, 42], 20, None, 3, 2),
+    ("n4096_default", 4096, None, 17, None, 2, 2),
+    ("n8192_default_t20", 8192, None, 20, None, 2, 2),
+    ("n8192_3x54", 8192, [54, 54, 54, 56], 20, None, 2, 2),
+    ("n16384_default_t20", 16384, None, 20, None, 2, 2),  # K = 8: the configuration whose auxiliary base the library shortened
 ]
+# the reference's raw plain moduli, the extremes of [2, 2^60), t above a data prime, and t wide enough that SEAL's rule
+# 32 + bits(t) + bits(q) >= 61 (K + 1) adds an auxiliary prime (n = 2048: one 54-bit prime, bits(t) >= 36)
+CASES += [(f"n4096_default_t{t}", 4096, None, None, t, 2, 2) for t in [2, 3, 500, 1 << 59, (1 << 60) - 1]]
+CASES += [("n1024_2x30_t2^40+15", 1024, [30, 30, 31], None, (1 << 40) + 15, 2, 2), ("n1024_2x30_t64_size3x2", 1024, [30, 30, 31], None, 64, 3, 2)]
+CASES += [(f"n2048_default_t{b}b", 2048, None, b, None, 2, 2) for b in (36, 40)]
+CASES += [("n8192_3x54_t2^59", 8192, [54, 54, 54, 56], None, 1 << 59, 2, 2)]
 
 
-@pytest.mark.parametrize("name,n,bits,tbits,sa,sb", CASES, ids=[c[0] for c in CASES])
-def test_oracle_multiply_is_the_integer_algorithm(name, n, bits, tbits, sa, sb):
+@pytest.mark.parametrize("name,n,bits,tbits,t,sa,sb", CASES, ids=[c[0] for c in CASES])
+def test_oracle_multiply_is_the_integer_algorithm(name, n, bits, tbits, t, sa, sb):
     primes = O.bfv_default(n) if bits is None else O.coeff_modulus_create(n, bits)
-    t = O.plain_batching(n, tbits)
+    t = O.plain_batching(n, tbits) if t is None else t
     o = O.Oracle(n, primes, t)
     o.throw_on_transparent = False
+    if name.startswith("n2048_default_t"):
+        assert len(o.bsk) == o.K + 2  # |B| = K + 1: SEAL's extra auxiliary prime
     q = [int(p) for p in primes[: o.K]]
     Q = _prod(q)
-    rng = np.random.default_rng(n + tbits)
+    rng = np.random.default_rng(n + (tbits if tbits is not None else t.bit_length()))
 
     def rand(size):
         return np.stack([rng.integers(0, p, (size, n), dtype=np.uint64) for p in q], axis=1)

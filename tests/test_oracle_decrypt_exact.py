@@ -70,10 +70,23 @@ def _decrypt_over_the_integers(o, xs) -> tuple[np.ndarray, list[int]]:
     return out, slack
 
 
-@pytest.mark.parametrize("n,bits,tbits", [(1024, [30, 30, 31], 14), (4096, None, 17), (8192, None, 20)])
-def test_decrypt_is_the_integer_algorithm_and_rounds_valid_ciphertexts(n, bits, tbits):
+# (n, data prime bits or None for the default set, bits of a batching t, or None with an explicit t); the explicit t are the
+# reference's raw plain moduli, the extremes of [2, 2^60) and t above a data prime
+RAW_T = [2, 3, 64, 500, 1024, 262144, 1 << 59, (1 << 60) - 1]
+CASES = [(1024, [30, 30, 31], 14, None), (4096, None, 17, None), (8192, None, 20, None)]
+CASES += [(4096, None, None, t) for t in RAW_T]
+CASES += [(1024, [30, 30, 31], None, t) for t in [2, 3, 64, 500, 1024, 1 << 59, (1 << 40) + 15]]
+CASES += [(2048, None, 40, None)]
+
+
+IDS = ["1024-bits0-14", "4096-None-17", "8192-None-20"] + [f"{n}-{'default' if b is None else 'x'.join(map(str, b))}-{f'tbatch{tb}' if t is None else f't{t}'}" for n, b, tb, t in CASES[3:]]
+
+
+@pytest.mark.parametrize("n,bits,tbits,t", CASES, ids=IDS)
+def test_decrypt_is_the_integer_algorithm_and_rounds_valid_ciphertexts(n, bits, tbits, t):
     primes = O.bfv_default(n) if bits is None else O.coeff_modulus_create(n, bits)
-    o = O.Oracle(n, primes, O.plain_batching(n, tbits))
+    explicit_t = t is not None
+    o = O.Oracle(n, primes, O.plain_batching(n, tbits) if t is None else t)
     o.throw_on_transparent = False
     O.seed(n)
     sk, pk, rk, gk = o.keygen()
@@ -83,7 +96,9 @@ def test_decrypt_is_the_integer_algorithm_and_rounds_valid_ciphertexts(n, bits, 
     rng = np.random.default_rng(n)
     plain = rng.integers(0, t, n, dtype=np.uint64)
     ct = o.encrypt(pk, plain)
-    cases = [("fresh", ct, True)]
+    fresh_ok = o.noise_budget(ct, sk) > 0
+    assert fresh_ok or explicit_t  # a wide t can leave a fresh encryption without budget: then only the integer algorithm holds
+    cases = [("fresh", ct, fresh_ok)]
     sq = o.multiply(ct, ct)
     cases.append(("squared, size 3", sq, o.noise_budget(sq, sk) > 0))
     if n >= 4096:
@@ -105,4 +120,13 @@ def test_decrypt_is_the_integer_algorithm_and_rounds_valid_ciphertexts(n, bits, 
                 xc = x - Q if x > Q // 2 else x
                 rounded.append(((2 * t * xc + Q) // (2 * Q)) % t)
             assert (got == np.array(rounded, dtype=np.uint64)).all(), label
-    assert (o.decrypt(ct, sk) == plain).all()
+    if fresh_ok:
+        assert (o.decrypt(ct, sk) == plain).all()
+    # a noiseless encryption of m, c = (Delta*m + [q*m mod t]-rounding, 0) as add_plain builds it, is valid at every t
+    zero = np.zeros((2, o.K, n), dtype=np.uint64)
+    noiseless = o.add_plain(zero, plain)
+    xs = _dot_over_the_integers(o, noiseless, s)
+    want, _ = _decrypt_over_the_integers(o, xs)
+    got = o.decrypt(noiseless, sk)
+    assert (got == want).all() and (got == plain).all()
+    assert (got == np.array([((2 * t * (x - Q if x > Q // 2 else x) + Q) // (2 * Q)) % t for x in xs], dtype=np.uint64)).all()

@@ -90,13 +90,24 @@ def _galois_poly(poly_row: np.ndarray, elt: int, qj: int) -> np.ndarray:
     return out
 
 
+# (name, n, data prime bits or None for the default set, bits of a batching t or None, explicit t or None)
 CASES = [
-    ("n1024_2x30", 1024, [30, 30, 31], 16),
-    ("n2048_3x36", 2048, [36, 36, 36, 37], 16),
-    ("n4096_default", 4096, None, 17),
-    ("n8192_default", 8192, None, 20),
-    ("n8192_3x54", 8192, [54, 54, 54, 56], 20),
+    ("n1024_2x30", 1024, [30, 30, 31], 16, None),
+    ("n2048_3x36", 2048, [36, 36, 36, 37], 16, None),
+    ("n4096_default", 4096, None, 17, None),
+    ("n8192_default", 8192, None, 20, None),
+    ("n8192_3x54", 8192, [54, 54, 54, 56], 20, None),
 ]
+# the key switch does not involve t: the same integers at the reference's raw plain moduli and at the extremes of [2, 2^60)
+T_CASES = [(f"n4096_default_t{t}", 4096, None, None, t) for t in [3, 500, (1 << 60) - 1]]
+T_CASES += [("n1024_2x30_t2^40+15", 1024, [30, 30, 31], None, (1 << 40) + 15)]
+
+
+def _oracle(n, bits, tbits, t):
+    primes = O.bfv_default(n) if bits is None else O.coeff_modulus_create(n, bits)
+    o = O.Oracle(n, primes, O.plain_batching(n, tbits) if t is None else t)
+    o.throw_on_transparent = False
+    return o
 
 
 def _operands(o, rng, size):
@@ -106,12 +117,10 @@ def _operands(o, rng, size):
     return [rand, top]
 
 
-@pytest.mark.parametrize("name,n,bits,tbits", CASES, ids=[c[0] for c in CASES])
-def test_relinearize_is_the_integer_key_switch(name, n, bits, tbits):
-    primes = O.bfv_default(n) if bits is None else O.coeff_modulus_create(n, bits)
-    o = O.Oracle(n, primes, O.plain_batching(n, tbits))
-    o.throw_on_transparent = False
-    O.seed(n + tbits)
+@pytest.mark.parametrize("name,n,bits,tbits,t", CASES + T_CASES, ids=[c[0] for c in CASES + T_CASES])
+def test_relinearize_is_the_integer_key_switch(name, n, bits, tbits, t):
+    o = _oracle(n, bits, tbits, t)
+    O.seed(n + (tbits if tbits is not None else o.t.bit_length()))
     sk, pk, rk, gk = o.keygen()
     keyc = _key_coefficients(o, rk)
     q = o.key_primes[: o.K]
@@ -126,11 +135,9 @@ def test_relinearize_is_the_integer_key_switch(name, n, bits, tbits):
         assert (got == want).all(), (name, idx)
 
 
-@pytest.mark.parametrize("name,n,bits,tbits", CASES[:4], ids=[c[0] for c in CASES[:4]])
-def test_apply_galois_is_permutation_plus_integer_key_switch(name, n, bits, tbits):
-    primes = O.bfv_default(n) if bits is None else O.coeff_modulus_create(n, bits)
-    o = O.Oracle(n, primes, O.plain_batching(n, tbits))
-    o.throw_on_transparent = False
+@pytest.mark.parametrize("name,n,bits,tbits,t", CASES[:4] + T_CASES[1:2], ids=[c[0] for c in CASES[:4] + T_CASES[1:2]])
+def test_apply_galois_is_permutation_plus_integer_key_switch(name, n, bits, tbits, t):
+    o = _oracle(n, bits, tbits, t)
     O.seed(n + 1)
     elts = [3, 2 * n - 1]
     sk, pk, rk, gk = o.keygen(relin=False, galois_elts=elts)
@@ -150,11 +157,9 @@ def test_apply_galois_is_permutation_plus_integer_key_switch(name, n, bits, tbit
             assert (got == want).all(), (name, elt, idx)
 
 
-@pytest.mark.parametrize("name,n,bits,tbits", [CASES[1], CASES[3], CASES[4]], ids=[CASES[1][0], CASES[3][0], CASES[4][0]])
-def test_mod_switch_to_next_is_the_integer_rounding(name, n, bits, tbits):
-    primes = O.bfv_default(n) if bits is None else O.coeff_modulus_create(n, bits)
-    o = O.Oracle(n, primes, O.plain_batching(n, tbits))
-    o.throw_on_transparent = False
+@pytest.mark.parametrize("name,n,bits,tbits,t", [CASES[1], CASES[3], CASES[4], T_CASES[2]], ids=[CASES[1][0], CASES[3][0], CASES[4][0], T_CASES[2][0]])
+def test_mod_switch_to_next_is_the_integer_rounding(name, n, bits, tbits, t):
+    o = _oracle(n, bits, tbits, t)
     q = o.key_primes[: o.K]
     last = q[-1]
     rng = np.random.default_rng(n + 11)
