@@ -484,6 +484,42 @@ long hipbfv_Program_RunKeys(void *program, void *evaluator, uint64_t batch, uint
                             void *const *relin_keys, void *const *galois_keys, const uint32_t *key_index,
                             uint64_t num_outputs, uint64_t *const *outputs, void *stream);
 
+/* Device pool: HOST-fed batches sharded over several devices (sunscreen_amd/csrc/pool.hpp).
+ * Members run on devices[0..count); an ordinal may repeat (several members on one device).  Every member has its own
+ * context, built from `context`'s parameters (the same auxiliary base and HIPBFV_SEAL_AUX rule, so the same bits), its own
+ * evaluator, three streams (in / compute / out), device buffers for three chunks in flight, pinned bounce buffers and one
+ * worker thread.  Members are not contexts of the process: they do not count for hipbfv_set_device, and they never use the
+ * process's cached device blocks.
+ *  - Synchronous: a call returns when every output is in host memory.  Calls on one pool are serialised; calls on
+ *    different pools run concurrently.
+ *  - Sharding: contiguous blocks whose sizes differ by at most one (sunscreen_amd/dist.py:shard_range), one per member; an
+ *    empty shard launches nothing; batch 0 is S_OK.
+ *  - Bits: input set i gives exactly the bits of hipbfv_batch_multiply_relin / hipbfv_Program_Run on input set i, whatever
+ *    the member count, the chunk size, or whether the host memory is pinned.
+ *  - Keys: the existing key handles, of any context with the pool's parameters.  A member copies a key's device data on the
+ *    first call that needs it there (peer copy across devices, device-to-device on the same device) and keeps the copy while
+ *    the key buffer lives.  A key of other parameters counts as absent; a missing key fails before anything is launched.
+ *  - Host memory: buffers hipPointerGetAttributes reports as pinned are copied from directly; other host memory is staged
+ *    through the member's pinned bounce buffers; device pointers are E_INVALIDARG.
+ *  - A transparent result is COR_E_INVALIDOPERATION (while hipbfv_set_throw_on_transparent is on), and hipbfv_last_error
+ *    names the input set's index in the whole batch.  A failure leaves the pool usable. */
+long hipbfv_Pool_Create(void *context, const int *devices, uint32_t count, void **pool);
+long hipbfv_Pool_Destroy(void *pool);
+/* input sets per pipeline chunk per member; 0 = the library's choice (default: 2^21 / N, 256 at N = 8192) */
+long hipbfv_Pool_SetChunk(void *pool, uint64_t sets_per_chunk);
+/* one line per member: "member=0 device=0 chunk=256 key_copies=1 keys_cached=1 slot_words=... bounce_words=..."
+ * (*needed = length + 1 as in hipbfv_Program_Describe; buffer may be NULL) */
+long hipbfv_Pool_Describe(void *pool, char *buffer, uint64_t capacity, uint64_t *needed);
+/* HOST pointers, u64[count][2][K][N]; out = relinearize(a * b); the aliasing rule of hipbfv_batch_multiply_relin */
+long hipbfv_Pool_MultiplyRelin(void *pool, const uint64_t *a, const uint64_t *b, void *relin_keys, uint64_t *out, uint64_t count);
+/* hipbfv_Program_Run over HOST inputs and outputs: kinds 0 and 1 (stride 0 = one shared plaintext, copied to each member
+ * once per call); kind 2 is E_INVALIDARG */
+long hipbfv_Pool_ProgramRun(void *pool, void *program, uint64_t batch, uint64_t num_inputs, const uint32_t *input_kinds,
+                            const uint64_t *const *input_ptrs, const uint64_t *input_strides, void *relin_keys,
+                            void *galois_keys, uint64_t num_outputs, uint64_t *const *outputs);
+/* the pool's shard rule, host only: member `member` of `members` gets input sets [*begin, *end) of a batch */
+long hipbfv_debug_pool_shard(uint64_t batch, uint32_t members, uint32_t member, uint64_t *begin, uint64_t *end);
+
 /* Per-kernel timing (HIP events recorded on the launch stream, around every kernel launch):
  * total milliseconds, number of launches and work units (residue polynomials for the NTT kernels,
  * polynomials or operations for the others) since the last reset. */

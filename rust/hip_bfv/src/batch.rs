@@ -189,6 +189,10 @@ pub enum Input {
 }
 
 impl Program {
+    pub fn get_handle(&self) -> *mut c_void {
+        self.handle
+    }
+
     pub fn from_json(json: &str) -> Result<Self> {
         let mut handle = null_mut();
         check(unsafe { bindgen::hipbfv_Program_Create(&mut handle) })?;

@@ -11,7 +11,8 @@
 //! Two levels:
 //! * handle level ([`BFVEvaluator`] and friends): one ciphertext per call, synchronous, thread-safe -- the drop-in;
 //! * batch level ([`batch::BatchEvaluator`], [`batch::Program`]): device-resident `u64[count][size][K][N]` batches,
-//!   asynchronous on a HIP stream -- what replaces the per-node dispatch of `run_program_unchecked`.
+//!   asynchronous on a HIP stream -- what replaces the per-node dispatch of `run_program_unchecked`;
+//! * pool level ([`pool::DevicePool`]): host-resident batches sharded over several GPUs, synchronous.
 #![allow(non_upper_case_globals, non_camel_case_types, non_snake_case, dead_code)]
 
 use std::os::raw::c_long;
@@ -25,6 +26,7 @@ pub mod batch;
 mod client;
 mod evaluator;
 mod handles;
+pub mod pool;
 mod raw;
 
 pub use client::{

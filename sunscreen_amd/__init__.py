@@ -6,6 +6,7 @@ Layers:
   seal.py         host-side mirror of the `seal_fhe` crate surface for this path (Context, BFVEvaluator,
                   Ciphertext, Plaintext, RelinearizationKeys, GaloisKeys, ...)
   batch.py        the GPU batch executor: the same operations over device-resident batches of ciphertexts
+  pool.py         DevicePool: host-fed batches sharded over several GPUs of one process
 """
 from .seal import (  # noqa: F401
     BFVEncoder,
@@ -28,3 +29,4 @@ from .seal import (  # noqa: F401
     SecretKey,
     SecurityLevel,
 )
+from .pool import DevicePool  # noqa: E402,F401

@@ -198,6 +198,13 @@ _SIGNATURES = {
     "hipbfv_debug_graph_probe": [vp, vp, vp, vp, vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "hipbfv_Program_Run": [vp, vp, u64, u64, C.POINTER(C.c_uint32), vpp, u64p, vp, vp, u64, vpp, vp],
     "hipbfv_Program_RunKeys": [vp, vp, u64, u64, C.POINTER(C.c_uint32), vpp, u64p, u64, vpp, vpp, C.POINTER(C.c_uint32), u64, vpp, vp],
+    "hipbfv_Pool_Create": [vp, C.POINTER(C.c_int), C.c_uint32, vpp],
+    "hipbfv_Pool_Destroy": [vp],
+    "hipbfv_Pool_SetChunk": [vp, u64],
+    "hipbfv_Pool_Describe": [vp, C.c_char_p, u64, u64p],
+    "hipbfv_Pool_MultiplyRelin": [vp, vp, vp, vp, vp, u64],
+    "hipbfv_Pool_ProgramRun": [vp, vp, u64, u64, C.POINTER(C.c_uint32), vpp, u64p, vp, vp, u64, vpp],
+    "hipbfv_debug_pool_shard": [u64, C.c_uint32, C.c_uint32, u64p, u64p],
     "hipbfv_profile_enable": [vp, C.c_bool],
     "hipbfv_profile_reset": [vp],
     "hipbfv_profile_kernel_count": [C.POINTER(C.c_uint32)],

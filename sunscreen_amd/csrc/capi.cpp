@@ -23,8 +23,10 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <set>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "evaluator.hpp"
@@ -210,9 +212,30 @@ struct CipherObj : Obj {
   }
 };
 
+// Every device key buffer a KeysObj installs carries a stamp that no other buffer ever gets, registered while the buffer lives.
+// The device pool (pool.hpp) keeps its per-member key copies by stamp: a key destroyed and another one allocated at the same
+// address (g_buffers recycles blocks) is never served from a copy of the first.
+std::mutex g_key_stamp_mu;
+std::set<u64> g_live_key_stamps;
+u64 g_next_key_stamp = 1;
+u64 key_stamp_new() {
+  std::lock_guard<std::mutex> g(g_key_stamp_mu);
+  g_live_key_stamps.insert(g_next_key_stamp);
+  return g_next_key_stamp++;
+}
+void key_stamp_drop(u64 stamp) {
+  std::lock_guard<std::mutex> g(g_key_stamp_mu);
+  g_live_key_stamps.erase(stamp);
+}
+bool key_stamp_live(u64 stamp) {
+  std::lock_guard<std::mutex> g(g_key_stamp_mu);
+  return g_live_key_stamps.count(stamp) != 0;
+}
+
 struct KeysObj : Obj {
   std::shared_ptr<Context> ctx;
   std::map<u32, u64*> keys;  // index -> device key u64[K][2][K+1][N]
+  std::map<u32, u64> stamps;  // index -> stamp of keys[index] (see key_stamp_new)
   // keys re-packed for lower levels of the modulus-switching chain: (level context, index) -> u64[K'][2][K'+1][N]
   std::map<std::pair<Context*, u32>, std::pair<u64*, size_t>> lower;
   std::mutex mu;
@@ -220,6 +243,14 @@ struct KeysObj : Obj {
   ~KeysObj() override {
     for (auto& kv : keys) g_buffers.put(kv.second, ctx ? ctx->key_words() : 0);
     for (auto& kv : lower) g_buffers.put(kv.second.first, kv.second.second);
+    for (auto& kv : stamps) key_stamp_drop(kv.second);
+  }
+  // keys[index] = buf (the caller has given back any buffer it replaces)
+  void install(u32 index, u64* buf) {
+    keys[index] = buf;
+    u64& s = stamps[index];
+    if (s) key_stamp_drop(s);
+    s = key_stamp_new();
   }
   const u64* find(u32 index) const {
     auto it = keys.find(index);
@@ -1183,7 +1214,7 @@ long KSwitchKeys_Create2(void* copy, void** out) HIPBFV_BEGIN
       delete n;
       return from_status(buf ? kHipError : kOutOfMemory);
     }
-    n->keys[kv.first] = buf;
+    n->install(kv.first, buf);
   }
   *out = n;
   return HIPBFV_S_OK;
@@ -1215,7 +1246,7 @@ static long assign_key(KeysObj* k, ContextObj* x, u32 index, const uint64_t* hos
   k->ctx = x->ctx;
   auto it = k->keys.find(index);
   if (it != k->keys.end()) g_buffers.put(it->second, words);
-  k->keys[index] = buf;
+  k->install(index, buf);
   return HIPBFV_S_OK;
 }
 
@@ -3746,7 +3777,7 @@ static long keygen_kswitch_into(KeyGenObj* g, KeysObj* keys, u32 galois_elt) {
   const u32 index = galois_elt ? (galois_elt - 1) >> 1 : 0;
   auto it = keys->keys.find(index);
   if (it != keys->keys.end()) g_buffers.put(it->second, words);
-  keys->keys[index] = buf;
+  keys->install(index, buf);
   return HIPBFV_S_OK;
 }
 long KeyGenerator_CreateRelinKeys(void* h, bool save_seed, void** relin_keys) HIPBFV_BEGIN
@@ -3808,6 +3839,247 @@ long KeyGenerator_CreateGaloisKeysAll(void* h, bool save_seed, void** galois_key
     neg = (neg * neg) & (m - 1);
   }
   return KeyGenerator_CreateGaloisKeysFromElts(h, elts.size(), elts.data(), save_seed, galois_keys);
+HIPBFV_END
+
+}  // extern "C"
+#pragma GCC visibility pop
+
+// ------------------------------------------------------------------ device pool (pool.hpp)
+#include "pool.hpp"
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+long hipbfv_Pool_Create(void* context, const int* devices, uint32_t count, void** pool) HIPBFV_BEGIN
+  ContextObj* x = as<ContextObj>(context, kMagicContext);
+  if (!x || !devices || !pool) return HIPBFV_E_POINTER;
+  if (count == 0 || count > 64) return fail(HIPBFV_E_INVALIDARG, "a pool has 1 to 64 members");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess) {
+    (void)hipGetLastError();
+    ndev = 0;
+  }
+  for (uint32_t i = 0; i < count; i++)
+    if (devices[i] < 0 || devices[i] >= ndev) return fail(HIPBFV_E_INVALIDARG, "no such HIP device");
+  std::unique_ptr<PoolObj> p(new PoolObj());
+  p->n = x->ctx->n();
+  p->K = x->ctx->K();
+  p->t = x->ctx->t();
+  p->primes = x->ctx->key_primes();
+  for (uint32_t i = 0; i < count; i++) {
+    p->members.emplace_back(new PoolMember());
+    p->members.back()->device = devices[i];
+  }
+  // every member's context, evaluator, streams and events are made on its own worker thread, all members at once
+  for (auto& m : p->members) {
+    PoolMember* mp = m.get();
+    PoolObj* pp = p.get();
+    mp->thread = std::thread(pool_worker, mp);
+    pool_submit(*mp, [mp, pp] { return member_init(*mp, *pp); });
+  }
+  long hr = HIPBFV_S_OK;
+  std::string msg;
+  for (auto& m : p->members) {
+    std::string mm;
+    const long h = pool_wait(*m, &mm);
+    if (h != HIPBFV_S_OK && hr == HIPBFV_S_OK) {
+      hr = h;
+      msg = mm;
+    }
+  }
+  if (hr != HIPBFV_S_OK) {
+    pool_destroy(p.release());
+    tls_error = msg;
+    return hr;
+  }
+  *pool = p.release();
+  return HIPBFV_S_OK;
+HIPBFV_END
+
+long hipbfv_Pool_Destroy(void* pool) HIPBFV_BEGIN
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  if (!p) return HIPBFV_E_POINTER;
+  {
+    std::lock_guard<std::mutex> g(p->mu);  // a call still running on another thread finishes first
+  }
+  pool_destroy(p);
+  return HIPBFV_S_OK;
+HIPBFV_END
+
+long hipbfv_Pool_SetChunk(void* pool, uint64_t sets_per_chunk) HIPBFV_BEGIN
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  if (!p) return HIPBFV_E_POINTER;
+  if (sets_per_chunk > 32768) return fail(HIPBFV_E_INVALIDARG, "at most 32768 input sets per chunk");
+  std::lock_guard<std::mutex> g(p->mu);
+  p->chunk = sets_per_chunk;
+  return HIPBFV_S_OK;
+HIPBFV_END
+
+long hipbfv_Pool_Describe(void* pool, char* buffer, uint64_t capacity, uint64_t* needed) HIPBFV_BEGIN
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  if (!p || !needed) return HIPBFV_E_POINTER;
+  std::string text;
+  {
+    std::lock_guard<std::mutex> g(p->mu);
+    for (size_t i = 0; i < p->members.size(); i++) {
+      const PoolMember& m = *p->members[i];
+      char line[256];
+      snprintf(line, sizeof(line), "member=%zu device=%d chunk=%llu key_copies=%llu keys_cached=%zu slot_words=%zu bounce_words=%zu\n", i, m.device,
+               (unsigned long long)p->chunk_sets(), (unsigned long long)m.key_copies, m.key_copy.size(), m.dev_words, m.bounce_words);
+      text += line;
+    }
+  }
+  *needed = text.size() + 1;
+  if (buffer && capacity) {
+    const size_t c = std::min<size_t>(text.size(), capacity - 1);
+    std::memcpy(buffer, text.data(), c);
+    buffer[c] = 0;
+  }
+  return HIPBFV_S_OK;
+HIPBFV_END
+
+long hipbfv_Pool_MultiplyRelin(void* pool, const uint64_t* a, const uint64_t* b, void* relin_keys, uint64_t* out, uint64_t count) HIPBFV_BEGIN
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  if (!p) return HIPBFV_E_POINTER;
+  if (count && (!a || !b || !out)) return HIPBFV_E_POINTER;
+  std::lock_guard<std::mutex> g(p->mu);
+  const size_t w = p->ct_words();
+  ALIAS_OR_RETURN(cts(out, w, count), {cts(a, w, count), cts(b, w, count)});
+  const std::vector<PoolKey> rk = pool_keys_of(*p, relin_keys, true);
+  if (rk.empty()) return from_status(kNoKey);
+  if (!count) return HIPBFV_S_OK;
+  const size_t bytes = count * w * sizeof(u64);
+  const HostMem ka = host_kind(a, bytes), kb = host_kind(b, bytes), ko = host_kind(out, bytes);
+  if (ka == HostMem::kDevice || kb == HostMem::kDevice || ko == HostMem::kDevice)
+    return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_MultiplyRelin takes host memory (device pointers are not accepted)");
+  const std::vector<PoolIn> ins = {{(const u64*)a, w, w, ka == HostMem::kPinned}, {(const u64*)b, w, w, kb == HostMem::kPinned}};
+  const std::vector<PoolOut> outs = {{(u64*)out, w, ko == HostMem::kPinned}};
+  const u64 chunk = p->chunk_sets();
+  const bool watch = g_throw_transparent;
+  return pool_dispatch(*p, count, [&](PoolMember& m, u64 lo, u64 hi) -> long {
+    if (long hr = member_keys(m, rk, {})) return hr;
+    const u64* key = m.relin_view.find(0);
+    const u64 sets = std::min<u64>(chunk, hi - lo);  // member_run's chunk: never more than the shard
+    const u64 nch = (hi - lo + sets - 1) / sets;
+    // one watch word per chunk, all read back after the last chunk: no small copy on the compute stream queues behind the
+    // out stream's large ones
+    if (watch) {
+      if (m.status_cap < nch) {
+        if (m.status) (void)hipFree(m.status);
+        m.status = nullptr;
+        m.status_cap = 0;
+        if (hipMalloc((void**)&m.status, nch * sizeof(u32)) != hipSuccess) {
+          (void)hipGetLastError();
+          m.status = nullptr;
+          return from_status(kOutOfMemory);
+        }
+        m.status_cap = nch;
+      }
+      size_t cap = m.flag_cap;
+      if (!grow_pinned((void**)&m.flags, &cap, nch * sizeof(u32))) return from_status(kOutOfMemory);
+      m.flag_cap = cap;
+      if (hipMemsetAsync(m.status, 0xFF, nch * sizeof(u32), m.comp) != hipSuccess) return from_status(kHipError);
+    }
+    long hr = member_run(m, ins, outs, lo, hi, sets, [&](u64 j, const std::vector<const u64*>& in, const std::vector<u64*>& o, u64 c, u64) -> long {
+      WatchScope scope(watch ? m.status + j : nullptr);
+      return from_status(m.eval.ev->multiply_relin(in[0], in[1], key, o[0], c, m.comp));
+    });
+    if (hr != HIPBFV_S_OK || !watch) return hr;
+    if (hipMemcpyAsync(m.flags, m.status, nch * sizeof(u32), hipMemcpyDeviceToHost, m.comp) != hipSuccess || hipStreamSynchronize(m.comp) != hipSuccess)
+      return from_status(kHipError);
+    for (u64 j = 0; j < nch; j++)
+      if (m.flags[j] != 0xFFFFFFFFu) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "result ciphertext is transparent (input set %llu of the batch)", (unsigned long long)(lo + j * sets + m.flags[j]));
+        return fail(HIPBFV_COR_E_INVALIDOPERATION, msg);
+      }
+    return HIPBFV_S_OK;
+  });
+HIPBFV_END
+
+long hipbfv_Pool_ProgramRun(void* pool, void* program, uint64_t batch, uint64_t num_inputs, const uint32_t* input_kinds,
+                            const uint64_t* const* input_ptrs, const uint64_t* input_strides, void* relin_keys, void* galois_keys,
+                            uint64_t num_outputs, uint64_t* const* outputs) HIPBFV_BEGIN
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  ProgramObj* prog = as<ProgramObj>(program, kMagicProgram);
+  if (!p || !prog || (num_inputs && (!input_kinds || !input_ptrs || !input_strides)) || (num_outputs && !outputs)) return HIPBFV_E_POINTER;
+  for (uint64_t i = 0; i < num_inputs; i++) {
+    if (input_kinds[i] == 2)
+      return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_ProgramRun takes host inputs of kinds 0 and 1 (kind 2, device-resident transformed plaintexts, is not accepted)");
+    if (input_kinds[i] > 2) return fail(HIPBFV_E_INVALIDARG, "unknown input kind");
+  }
+  {
+    std::string err;
+    if (int st = prog->prog.validate(&err)) {
+      const long hr = from_status(st);
+      tls_error = err;
+      return hr;
+    }
+  }
+  if (num_outputs != prog->prog.num_outputs()) return fail(HIPBFV_E_INVALIDARG, "wrong number of output buffers");
+  std::lock_guard<std::mutex> g(p->mu);
+  // the keys the graph needs are checked here, before anything is launched; a key of other parameters counts as absent
+  const std::vector<PoolKey> rk = pool_keys_of(*p, relin_keys, true), gk = pool_keys_of(*p, galois_keys, false);
+  bool need_relin = false, need_galois = false;
+  prog->prog.key_needs(&need_relin, &need_galois);
+  if ((need_relin && rk.empty()) || (need_galois && gk.empty())) return from_status(kNoKey);
+  if (!batch) return HIPBFV_S_OK;
+  for (uint64_t i = 0; i < num_inputs; i++)
+    if (!input_ptrs[i]) return HIPBFV_E_POINTER;
+  for (uint64_t k = 0; k < num_outputs; k++)
+    if (!outputs[k]) return HIPBFV_E_POINTER;
+  const size_t w = p->ct_words();
+  std::vector<PoolIn> ins(num_inputs);
+  std::vector<Span> in_spans;
+  for (uint64_t i = 0; i < num_inputs; i++) {
+    const bool ct = input_kinds[i] == 0;
+    const size_t width = ct ? w : p->n, stride = ct ? w : (size_t)input_strides[i];
+    const Span sp{input_ptrs[i], width, stride, (size_t)batch};
+    const HostMem hk = host_kind(input_ptrs[i], sp.words() * sizeof(u64));
+    if (hk == HostMem::kDevice) return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_ProgramRun takes host memory (device pointers are not accepted)");
+    ins[i] = PoolIn{(const u64*)input_ptrs[i], width, stride, hk == HostMem::kPinned};
+    in_spans.push_back(sp);
+  }
+  std::vector<PoolOut> outs(num_outputs);
+  for (uint64_t k = 0; k < num_outputs; k++) {
+    const Span o = cts(outputs[k], w, batch);
+    for (const Span& in : in_spans)
+      ALIAS_OR_RETURN(o, {in});
+    for (uint64_t l = 0; l < k; l++)
+      ALIAS_OR_RETURN(o, {cts(outputs[l], w, batch)}, false);
+    const HostMem hk = host_kind(outputs[k], o.words() * sizeof(u64));
+    if (hk == HostMem::kDevice) return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_ProgramRun takes host memory (device pointers are not accepted)");
+    outs[k] = PoolOut{(u64*)outputs[k], w, hk == HostMem::kPinned};
+  }
+  std::vector<uint32_t> kinds(input_kinds, input_kinds + num_inputs);
+  const u64 chunk = p->chunk_sets();
+  return pool_dispatch(*p, batch, [&](PoolMember& m, u64 lo, u64 hi) -> long {
+    if (long hr = member_keys(m, rk, gk)) return hr;
+    void* rkh = rk.empty() ? nullptr : &m.relin_view;
+    void* gkh = gk.empty() ? nullptr : &m.galois_view;
+    std::vector<uint64_t> strides(num_inputs), item_of(std::min<u64>(chunk, hi - lo));
+    for (uint64_t i = 0; i < num_inputs; i++) strides[i] = kinds[i] == 0 ? 0 : ins[i].stride ? p->n : 0;
+    return member_run(m, ins, outs, lo, hi, chunk, [&](u64, const std::vector<const u64*>& in, const std::vector<u64*>& o, u64 c, u64 first) -> long {
+      for (u64 i = 0; i < c; i++) item_of[i] = first + i;  // a transparent-result error names the caller's input set
+      std::vector<const uint64_t*> ptrs(in.size());
+      std::vector<uint64_t*> optrs(o.size());
+      for (size_t i = 0; i < in.size(); i++) ptrs[i] = (const uint64_t*)in[i];
+      for (size_t k = 0; k < o.size(); k++) optrs[k] = (uint64_t*)o[k];
+      return program_run_impl(prog, &m.eval, c, num_inputs, kinds.data(), ptrs.data(), strides.data(), 1, &rkh, &gkh, nullptr, num_outputs,
+                              optrs.data(), m.comp, item_of.data());
+    });
+  });
+HIPBFV_END
+
+// dist.py:shard_range, the pool's split of a batch over its members: member `member` of `members` gets input sets [begin, end)
+long hipbfv_debug_pool_shard(uint64_t batch, uint32_t members, uint32_t member, uint64_t* begin, uint64_t* end) HIPBFV_BEGIN
+  if (!begin || !end) return HIPBFV_E_POINTER;
+  if (!members || member >= members) return fail(HIPBFV_E_INVALIDARG, "member index out of range");
+  u64 lo, hi;
+  pool_shard(batch, members, member, &lo, &hi);
+  *begin = lo;
+  *end = hi;
+  return HIPBFV_S_OK;
 HIPBFV_END
 
 }  // extern "C"

@@ -324,6 +324,15 @@ int Program::load_json(const char* text, size_t len, std::string* err) {
   return kOk;
 }
 
+void Program::key_needs(bool* relin, bool* galois) const {
+  *relin = *galois = false;
+  for (const Node& nd : nodes_) {
+    if (nd.op == kOpMultiply) *relin = true;
+    if (nd.op == kOpSwapRows) *galois = true;
+    if ((nd.op == kOpShiftLeft || nd.op == kOpShiftRight) && nd.right >= 0 && (int)nodes_[nd.right].arg != 0) *galois = true;
+  }
+}
+
 int Program::validate(std::string* err) const {
   auto fail = [&](const char* m) {
     if (err) *err = m;

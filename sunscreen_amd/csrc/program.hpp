@@ -70,6 +70,9 @@ class Program {
   int add_edge(int src, int dst, EdgeKind kind);
   int load_json(const char* text, size_t len, std::string* err);
   int validate(std::string* err) const;
+  // which key kinds a run of this (valid) graph needs: a relinearisation key for a ciphertext product, Galois keys for a column
+  // swap or a rotation by a non-zero literal (the device pool checks the keys it is given before it launches anything)
+  void key_needs(bool* relin, bool* galois) const;
   size_t num_nodes() const { return nodes_.size(); }
   size_t num_outputs() const;
   // outputs: one device buffer u64[batch][2][K][N] per OutputCiphertext node, in node-index order (run.rs:343-356)
