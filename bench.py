@@ -6,19 +6,24 @@ ciphertext pairs, n=8192, SEAL default 128-bit parameters (K=4 data primes + 1 s
 t = batching(8192,17) = 114689) -- BASELINE.json configs[2], the configuration the metric is quoted
 on.  Inputs are resident in HBM before the timed region.
 
+A plain run does only what its headline figure needs: set up, warm up, time the K steps, write --dump-outputs if asked, print
+the line (`parity` "skipped", `cpu_baseline` null, no `power`, no `secondary`).  Everything else it measures or checks runs
+only with `--full`: the parity gate against the oracle, the CPU baseline, the power leg and, for the headline configuration,
+the secondary workloads below.  `--no-check`, `--no-cpu`, `--no-power` and `--no-secondary` drop single parts of a --full run.
+
 BASELINE.json's metric names three quantities ("mul+relin ops/sec at n=8192/16384; NTTs/sec") and its `configs` list the
-reference's example programs.  The default run times all of them in one process: the headline line is n=8192 and its
+reference's example programs.  A --full run times all of them in one process: the headline line is n=8192 and its
 `secondary` object carries the n=16384 mul+relin (batch/4 pairs, SEAL default K=8+1), the configs[1] transform workload
 (forward+inverse NTT, n=8192, 3 primes), the north star's literal prime set (n=8192, 3 x 54-bit + special prime), and -- on one
 GPU -- examples/chi_sq at n=16384 (the 1024-input batch of configs[3] and one GPU's 128-set share of it), examples/dot_prod
 (256 sets) and examples/pir over 2^17 entries (128 rows x 1024 columns: one GPU's rows of the 1024 x 1024 database, 128 GiB in transform form), each with its own value, ms_per_step,
 repeats, roofline, cpu_baseline and parity gate (64 items / 8 input sets against the oracle), measured with the same --steps /
 --warmup / --repeats (`--no-secondary` drops them; the NTT workload times at least 100 of its 0.7 ms steps per region; the whole
-default run takes 2-3 minutes).  `--workload ntt|chi_sq|dot_prod|pir|e2e` run one workload alone (same JSON contract).
+--full run takes about a minute).  `--workload ntt|chi_sq|dot_prod|pir|e2e` run one workload alone (same JSON contract).
 
 The CPU oracle appears here in three roles only: client (it generates the keys and the few genuine encryptions the
-parity gate needs), checker (parity gate, after the timed region) and `cpu_baseline` (host cores, OpenMP over the
-batch).  Nothing in the timed region touches it.
+parity gate needs), checker (parity gate, after the timed region, --full) and `cpu_baseline` (host cores, OpenMP over the
+batch, --full).  Nothing in the timed region touches it.
 
 N>1: one process per GPU (torch.distributed, backend nccl = RCCL); every rank processes its own `--batch` items (weak
 scaling, no data-path collective) or, with `--total-batch T`, its shard of T items (strong scaling: BASELINE configs[3]
@@ -34,8 +39,8 @@ Timing: W warmup steps, then untimed steps for about `--settle-ms` (150 ms: the 
 cap these kernels run at; the count is agreed between the ranks and reported as `settle_steps`), then EXACTLY K timed steps,
 split into R = min(`--repeats` (5), K) consecutive regions of K / R steps (sizes differing by at most one), every region between
 two barriers (+ torch.cuda.synchronize) and MAX-reduced over the ranks: `ms_per_step` is the MEDIAN region's time per step and
-`value` the rate at it, `values` lists all R rates and `spread` = (slowest - fastest) / median.  At N = 1 an untimed leg after the measurement samples `rocm-smi` while the steps keep running (`power`:
-package watts, shader clock, cap; `--no-power` skips it).
+`value` the rate at it, `values` lists all R rates and `spread` = (slowest - fastest) / median.  At N = 1 a --full run adds an untimed leg after the measurement
+that samples `rocm-smi` while the steps keep running (`power`: package watts, shader clock, cap; `--no-power` skips it).
 
 `--dump-outputs DIR` writes what the last timed step computed (rank 0's share) as DIR/<name>.npy, float32, at most 64 MB in all
 (dump_outputs).  The inputs come from fixed seeds: the same arguments give the same inputs on every run, so two builds can be
@@ -90,18 +95,21 @@ def parse(argv=None):
                     "2-3 %%, a claim smaller than the spread of its own repeats is noise")
     ap.add_argument("--chunk", type=int, default=0, help="override the executor's chunk size (ops per launch group)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="ops in the CPU-baseline sample (0 = auto)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the parity gate against the oracle, the CPU "
+                    "baseline, the power leg and (headline configuration) the secondary workloads; a plain run only sets up, warms up, times "
+                    "the --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the parity gate")
     ap.add_argument("--settle-ms", type=float, default=150.0, help="keep running untimed steps after the W warmup steps until this much wall time "
                     "has passed (device clocks under the power cap settle in tens of ms; 0 = exactly W warmup steps)")
     ap.add_argument("--no-kernel-events", action="store_true", help="time the regions WITHOUT the HIP events the library records around every kernel launch "
                     "(hipbfv_profile_enable): the line then has no roofline (no per-kernel times) -- the one-off measurement of what the events cost")
-    ap.add_argument("--no-power", dest="power", action="store_false", help="skip the `power` leg (N=1: after the measurement, rocm-smi is sampled for package "
-                    "power and shader clock while the steps keep running, about 3 s)")
+    ap.add_argument("--no-power", dest="power", action="store_false", help="--full: skip the `power` leg (N=1: after the measurement, rocm-smi is sampled for "
+                    "package power and shader clock while the steps keep running, about 3 s)")
     ap.add_argument("--power", dest="power", action="store_true", help=argparse.SUPPRESS)
     ap.set_defaults(power=True)
-    ap.add_argument("--no-secondary", action="store_true", help="headline run only: skip the n=16384 mul+relin and the NTT workload "
-                    "that the default run reports under `secondary`")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the n=16384 mul+relin, the NTT workload and the other workloads "
+                    "a --full run of the headline configuration reports under `secondary`")
     ap.add_argument("--full-line", action="store_true", help="print every field of every secondary workload (the default line keeps the secondary records "
                     "compact and ends in `summary`, so that the tail a driver stores carries every quantity of the metric)")
     ap.add_argument("--check-items", type=int, default=64, help="mulrelin: items compared bit for bit with the oracle (BASELINE.md section 3: >= 64)")
@@ -398,7 +406,7 @@ def dump_outputs(outdir, arrays):
 
 
 def measure(args, env: Env, secondary: bool = False):
-    """Run ONE workload: W warm-up steps, K timed steps between barriers, parity gate, roofline, CPU baseline.
+    """Run ONE workload: W warm-up steps, K timed steps between barriers, roofline; with --full the parity gate, CPU baseline and power leg.
     Returns the JSON object on rank 0, None on the other ranks."""
     import torch
     import torch.distributed as dist
@@ -730,9 +738,10 @@ def measure(args, env: Env, secondary: bool = False):
             assert full.shape[0] == total_items and torch.equal(full[:B], out)
         del full
 
-    # ---- parity gate (after timing so that the timed region is exactly K steps) ----
-    parity = "skipped"
-    if args.workload == "mulrelin" and nkeys > 1 and not args.no_check:
+    # ---- parity gate (--full; after timing so that the timed region is exactly K steps) ----
+    check = args.full and not args.no_check
+    parity = "skipped" if args.full else "skipped (plain run: --full runs the parity gate)"
+    if args.workload == "mulrelin" and nkeys > 1 and check:
         # (1) every client's items decrypt under THAT client's secret key to the slot-wise products
         ok = True
         for c, cl in enumerate(clients):
@@ -758,7 +767,7 @@ def measure(args, env: Env, secondary: bool = False):
                 assert (got[i] == refs[i]).all(), "HIP per-key result differs from the CPU oracle"
         parity = (f"bit-exact vs oracle on {ncheck} items of {len({int(k) for k in key_index[:ncheck]})} clients (each with its own key); all {total_items} "
                   f"results decrypt under their client's secret key to the slot-wise products; all outputs canonical")
-    elif args.workload == "mulrelin" and not args.no_check:
+    elif args.workload == "mulrelin" and check:
         # (1) decrypt-correct on ALL items of every rank (device decryptor, itself bit-exact vs the oracle: tests/test_gpu_client.py)
         dec = ev.decode(ev.decrypt(out, skd), signed=True)
         ok = bool(torch.equal(dec, va * vb))
@@ -779,7 +788,7 @@ def measure(args, env: Env, secondary: bool = False):
             budget = o.noise_budget(got[0], sk)
             assert budget > 0
         parity = f"bit-exact vs oracle on {ncheck} items; all {total_items} results decrypt to the slot-wise products; all outputs canonical"
-    elif args.workload == "pir" and not args.no_check:
+    elif args.workload == "pir" and check:
         if rank == 0:
             res = holder["out"]
             got = to_host(ev.decrypt(res, skd))[0]
@@ -803,7 +812,7 @@ def measure(args, env: Env, secondary: bool = False):
             parity += f"; the {world}-way row-sharded answer equals the single-GPU lookup over the whole database bit for bit"
         else:
             parity += " (matrix-vector and program bits vs the oracle: tests/test_gpu_program.py)"
-    elif args.workload == "e2e" and not args.no_check:
+    elif args.workload == "e2e" and check:
         assert torch.equal(holder["out"], (va * vb) % t), "decoded products differ from the slot-wise products"
         if rank == 0:
             got = to_host(holder["ct"][:2])
@@ -811,7 +820,7 @@ def measure(args, env: Env, secondary: bool = False):
             for i in range(2):
                 assert (pl[i] == o.decrypt(got[i], sk)).all(), "HIP decryption differs from the CPU oracle"
         parity = f"all {B} decoded results equal the slot-wise products mod t; decryption bit-exact vs the oracle on 2 items"
-    elif args.workload in ("chi_sq", "dot_prod") and not args.no_check:
+    elif args.workload in ("chi_sq", "dot_prod") and check:
         if rank == 0 and ncheck:
             from concurrent.futures import ThreadPoolExecutor
 
@@ -835,7 +844,7 @@ def measure(args, env: Env, secondary: bool = False):
                 dec = ev.decode(ev.decrypt(outs_holder[k][:ncheck], skd))
                 assert torch.equal(dec, expect[k] % t), "program output does not decrypt to the expected slot values"
         parity = f"bit-exact vs the oracle graph interpreter on {ncheck} input sets x {nout} outputs; those sets decrypt to the program's slot values"
-    elif args.workload == "ntt" and not args.no_check:
+    elif args.workload == "ntt" and check:
         assert torch.equal(data, ref), "INTT(NTT(x)) != x"
         # forward transform of the first polynomials against the oracle (SEAL NTTTables convention, pinned by the key fixture)
         m = fwd_keep.shape[0]
@@ -945,10 +954,10 @@ def measure(args, env: Env, secondary: bool = False):
         if traffic_note:
             roofline["traffic_note"] = traffic_note
     cpu = None
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         cpu = cpu_baseline(args, O, n, primes, t, small=secondary)
     power = None
-    if args.power and world == 1 and not secondary:
+    if args.full and args.power and world == 1 and not secondary:
         power = power_leg(step, torch.cuda.synchronize)
     line = {
         "metric": metric,
@@ -1009,9 +1018,10 @@ def main():
     import torch.distributed as dist
 
     line = measure(args, env)
-    # BASELINE.json's metric also names n=16384 and NTTs/sec: the default (headline) run times them too, in this process
+    # BASELINE.json's metric also names n=16384 and NTTs/sec: a --full run of the headline configuration times them too, in this process
     headline = args.workload == "mulrelin" and args.n == 8192 and not args.coeff_bits and not args.chunk and args.keys <= 1
-    if headline and not args.no_secondary:
+    secondary = headline and args.full and not args.no_secondary
+    if secondary:
         second = {}
         q4 = max(args.batch // 4, 1)
         jobs = [
@@ -1088,7 +1098,7 @@ def main():
         print(json.dumps(line))
     if dist.is_initialized():
         dist.destroy_process_group()
-    if headline and not args.no_secondary and failed:
+    if secondary and failed:
         sys.exit(1)
 
 
@@ -1107,8 +1117,10 @@ def summary_entry(rec):
     if ratio is None and roof.get("traffic") and roof.get("algorithmic_bytes_per_launch"):
         ratio = round(roof["traffic"] / roof["algorithmic_bytes_per_launch"], 3)
     parity = rec.get("parity", "")
+    # None: the gate did not run (a plain run, or --no-check)
+    ok = None if parity.startswith("skipped") else parity.startswith(("bit-exact", "INTT(NTT(x)) == x", "lookup decrypts", "all "))
     return {"value": rec["value"], "ms_per_step": rec["ms_per_step"], "frac": roof.get("frac"), "whole_op_frac": whole, "traffic_ratio": ratio,
-            "parity_ok": rec.get("parity_ok", parity.startswith(("bit-exact", "INTT(NTT(x)) == x", "lookup decrypts", "all ")))}
+            "parity_ok": rec.get("parity_ok", ok)}
 
 
 def summary_of(line):
@@ -1166,8 +1178,8 @@ def ctx_S(ctx):
 
 def cpu_baseline(args, O, n, primes, t, small=False):
     """The CPU oracle (a port of SEAL's algorithms, NOT SEAL itself -- SEAL's source is absent from the
-    reference tree) timed on this host on a bounded sample of the same workload.  small: the secondary measurements of the
-    default run take a quarter of the sample so that the whole run stays within a minute."""
+    reference tree) timed on this host on a bounded sample of the same workload (--full).  small: the secondary measurements of a
+    --full run take a quarter of the sample so that the whole run stays within a minute."""
     cores = os.cpu_count() or 1
     threads = min(cores, 256)  # all host cores (SURVEY 8d); the sample scales with them so that every thread gets several items
     o = O.Oracle(n, primes, t)

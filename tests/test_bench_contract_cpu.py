@@ -217,3 +217,17 @@ def test_every_summary_workload_has_its_kernel_trace_and_pmc_passes_for_the_tree
         assert doc["source_hash"].get(wkey) == tree, (wkey, doc["source_hash"].get(wkey), tree)
     if "kernel_source_hash" in line:
         assert line["kernel_source_hash"] == tree
+
+
+def test_a_plain_run_leaves_the_checks_and_extra_measurements_to_full():
+    """`bench.py` without --full does only what its headline figure needs; the parity gate, the CPU baseline, the power leg and the
+    secondary workloads run with --full.  A line whose gate did not run says so in its summary (parity_ok None, not False)."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert not bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full
+    assert bench.parse(["--full"]).full
+    rec = {"value": 1.0, "ms_per_step": 1.0}
+    assert bench.summary_entry(dict(rec, parity="skipped (plain run: --full runs the parity gate)"))["parity_ok"] is None
+    assert bench.summary_entry(dict(rec, parity="skipped"))["parity_ok"] is None
+    assert bench.summary_entry(dict(rec, parity="bit-exact vs oracle on 64 items"))["parity_ok"] is True

@@ -32,7 +32,7 @@ def _line(p):
 
 
 def test_bench_gpus_2_spawns_two_ranks_and_reports_them():
-    d = _line(_run(["--gpus", "2", "--no-cpu", "--gather"]))
+    d = _line(_run(["--gpus", "2", "--full", "--no-cpu", "--gather"]))
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
     assert d["config"]["parallelism"] == "batch-sharded x2"
     assert "all 128 results decrypt" in d["parity"] and "bit-exact vs oracle on 8 items" in d["parity"]
@@ -56,7 +56,7 @@ def test_pir_database_sharded_by_row_with_the_cross_gpu_sum():
     decrypts the answer (database[sel_r][sel_c]), compares the decryption with the oracle's, and -- the database being small
     enough for one device -- compares the sharded answer with the single-GPU lookup over the whole database BIT FOR BIT.
     3 ranks over 10 rows: uneven shards (4, 3, 3)."""
-    d = _line(_run(["--gpus", "3", "--workload", "pir", "--pir-rows", "10", "--no-cpu"], base=("--n", "4096", "--batch", "12", "--steps", "2", "--warmup", "1")))
+    d = _line(_run(["--gpus", "3", "--workload", "pir", "--pir-rows", "10", "--full", "--no-cpu"], base=("--n", "4096", "--batch", "12", "--steps", "2", "--warmup", "1")))
     assert d["n_gpus"] == 3 and d["scaling"] == "strong"
     assert "rows sharded x3" in d["config"]["parallelism"] and "gather(dst=0)" in d["config"]["exchange"]
     assert "equals the single-GPU lookup over the whole database bit for bit" in d["parity"]
@@ -66,7 +66,7 @@ def test_pir_database_sharded_by_row_with_the_cross_gpu_sum():
 
 def test_total_batch_is_sharded_over_the_ranks():
     """BASELINE configs[3]: "1024-input batch sharded across 8" -- the strong-scaling form: --total-batch T items in total."""
-    d = _line(_run(["--gpus", "2", "--total-batch", "65", "--no-cpu", "--no-secondary"]))
+    d = _line(_run(["--gpus", "2", "--total-batch", "65", "--full", "--no-cpu", "--no-secondary"]))
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["total_batch"] == 65
     assert d["config"]["batch_per_gpu"] == 33  # rank 0's shard of 65
     assert "all 65 results decrypt" in d["parity"]
@@ -171,7 +171,7 @@ def test_bench_single_rank_with_the_rccl_process_group_initialised():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env.update(HIPBFV_BENCH_FORCE_DIST="1", MASTER_PORT=str(_free_port()))
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "4096", "--batch", "64", "--steps", "2", "--warmup", "1", "--repeats", "2",
-                        "--check-items", "8", "--gpus", "1", "--no-cpu", "--no-power", "--gather"], env=env, capture_output=True, text=True, timeout=900)
+                        "--check-items", "8", "--gpus", "1", "--full", "--no-cpu", "--no-power", "--gather"], env=env, capture_output=True, text=True, timeout=900)
     d = _line(p)
     assert d["n_gpus"] == 1 and d["config"]["collectives"] == "nccl" and d["repeats"] == 2 and len(d["values"]) == 2
     assert "all 64 results decrypt" in d["parity"] and d["result_gather_ms"] > 0

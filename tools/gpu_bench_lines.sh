@@ -4,7 +4,7 @@
 TAG=${1:-lines}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-run() { name=$1; shift; timeout 400 python bench.py "$@" 2>$OUT/$name.err | tail -1 > $OUT/bench_$name.json; python -c "
+run() { name=$1; shift; timeout 400 python bench.py "$@" --full 2>$OUT/$name.err | tail -1 > $OUT/bench_$name.json; python -c "
 import json; d=json.load(open('$OUT/bench_$name.json')); print('$name', d['value'], d['unit'], 'roofline', d['roofline']['frac'], 'traffic', d['roofline']['traffic'], 'cpu', d['cpu_baseline'] and d['cpu_baseline']['value'])"; }
 run mulrelin_n8192 --steps 10 --warmup 2
 run mulrelin_n16384 --n 16384 --batch 1024 --steps 5 --warmup 1

@@ -20,7 +20,7 @@ bash tools/gpu_pmc_report.sh $T mulrelin_n16384_keys1024 --n 16384 --batch 1024 
 bash tools/gpu_pmc_stall.sh $T mulrelin_n8192 > /dev/null 2>&1
 bash tools/gpu_pmc_stall.sh $T mulrelin_n16384 --n 16384 --batch 1024 > /dev/null 2>&1
 bash tools/gpu_pmc_stall.sh $T ntt_n8192 --workload ntt > /dev/null 2>&1
-timeout 600 rocprofv3 --kernel-trace --stats -d $O -o default_bench_trace -- python bench.py --steps 20 --warmup 5 --no-cpu --no-power > $O/default_bench_trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O -o default_bench_trace -- python bench.py --steps 20 --warmup 5 --full --no-cpu --no-power > $O/default_bench_trace.log 2>&1
 python tools/rocprof_summary.py $O/default_bench_trace_results.db > $O/default_bench_kernel_stats.txt 2>/dev/null
 rm -f $O/*.db
 ls $O | wc -l; for k in mulrelin_n8192 mulrelin_n16384 ntt_n8192 mulrelin_n8192_bits54-54-54-56 chi_sq_n16384 dot_prod_n16384 pir_n16384 mulrelin_n8192_keys4096 mulrelin_n16384_keys1024; do python -c "

@@ -4,8 +4,8 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 T=r06_final
 O=gpurun_out/$T; mkdir -p $O
-( time python bench.py --steps 20 --warmup 5 ) > $O/bench_default.json 2> $O/bench_default.err; tail -3 $O/bench_default.err
-python bench.py --steps 20 --warmup 5 --no-cpu > $O/bench_default_run2.json 2> /dev/null
+( time python bench.py --steps 20 --warmup 5 --full ) > $O/bench_default.json 2> $O/bench_default.err; tail -3 $O/bench_default.err
+python bench.py --steps 20 --warmup 5 --full --no-cpu > $O/bench_default_run2.json 2> /dev/null
 python - <<'PY'
 import json
 for f in ("bench_default.json", "bench_default_run2.json"):
