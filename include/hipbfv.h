@@ -507,7 +507,8 @@ long hipbfv_Pool_Create(void *context, const int *devices, uint32_t count, void 
 long hipbfv_Pool_Destroy(void *pool);
 /* input sets per pipeline chunk per member; 0 = the library's choice (default: 2^21 / N, 256 at N = 8192) */
 long hipbfv_Pool_SetChunk(void *pool, uint64_t sets_per_chunk);
-/* one line per member: "member=0 device=0 chunk=256 key_copies=1 keys_cached=1 slot_words=... bounce_words=..."
+/* one line per member: "member=0 device=0 chunk=256 key_copies=1 keys_cached=1 slot_words=... bounce_words=... key_bytes=...
+ * key_evictions=..."
  * (*needed = length + 1 as in hipbfv_Program_Describe; buffer may be NULL) */
 long hipbfv_Pool_Describe(void *pool, char *buffer, uint64_t capacity, uint64_t *needed);
 /* HOST pointers, u64[count][2][K][N]; out = relinearize(a * b); the aliasing rule of hipbfv_batch_multiply_relin */
@@ -517,8 +518,56 @@ long hipbfv_Pool_MultiplyRelin(void *pool, const uint64_t *a, const uint64_t *b,
 long hipbfv_Pool_ProgramRun(void *pool, void *program, uint64_t batch, uint64_t num_inputs, const uint32_t *input_kinds,
                             const uint64_t *const *input_ptrs, const uint64_t *input_strides, void *relin_keys,
                             void *galois_keys, uint64_t num_outputs, uint64_t *const *outputs);
+/* Per-client key sets through the pool: input set i uses key set key_index[i], as in hipbfv_batch_*_keys and
+ * hipbfv_Program_RunKeys, whose argument order these follow (no evaluator, no stream; HOST data pointers; the handle arrays
+ * and key_index are host arrays as there).  One shared key set is num_key_sets = 1 with an all-zero key_index.
+ *  - Bits: input set i gives exactly the words of hipbfv_batch_multiply_relin_keys / hipbfv_batch_rotate_rows_keys /
+ *    hipbfv_batch_rotate_columns_keys / hipbfv_Program_RunKeys over the whole batch on one device -- hence of the single-key
+ *    call with key_sets[key_index[i]] -- whatever the member count, the chunk size, the order of clients in the batch, whether
+ *    the host memory is pinned, and whatever the key-cache bound.
+ *  - Sharding: as above; key_index is sliced with the input sets, which need not be grouped by client.
+ *  - Only referenced sets count: an entry no key_index entry names may be NULL, foreign or lack the key.  A referenced set that
+ *    is NULL, not a key object, of other parameters, or without a key the call needs (the relinearisation key; the direct
+ *    Galois key of `steps` or else every power-of-two key of its NAF chain; what the program's graph needs) is
+ *    HIPBFV_E_INVALIDARG and hipbfv_last_error names the set's index in the CALLER's array; key_index[i] >= num_key_sets
+ *    likewise.  This is decided on the calling thread over the whole batch before any member copies or launches anything:
+ *    outputs are untouched and no key is copied.
+ *  - Per-set decisions stay per set: in RotateRowsKeys a set that holds the direct key uses it and a set without takes the NAF
+ *    chain, both in one call; in ProgramRunKeys input sets whose key sets hold different kinds of keys run as separate runs
+ *    inside the member, as in hipbfv_Program_RunKeys.
+ *  - What a member copies: for every pipeline chunk, the distinct sets the chunk's key_index names become the chunk's own
+ *    handle table and key_index is remapped onto it (hipbfv_debug_pool_keyplan).  A member copies a key buffer only if a set
+ *    of its own shard references it AND the call needs that key: index 0 for MultiplyRelinKeys; the Galois elements the
+ *    rotation reads for that set; for a program the relinearisation key if the graph relinearises and the set's Galois
+ *    elements if it rotates.  Copies are made once and kept while the key buffer lives (or until the bound drops them).
+ *  - hipbfv_Pool_SetKeyCacheBytes: a bound, per member, on the bytes of key copies it keeps; 0 = no bound (the default).  It
+ *    holds from the next call on, for every pool call.  Before a chunk's keys are staged the member drops least-recently-used
+ *    copies that no chunk in flight references until the chunk's keys fit; a chunk whose own keys exceed the bound is
+ *    HIPBFV_E_OUTOFMEMORY, the message giving both byte counts (lower hipbfv_Pool_SetChunk or raise the bound).
+ *    hipbfv_Pool_Describe ends every member line with "key_bytes=... key_evictions=...".
+ *  - Transparent results, failures, serialisation, kind-2 inputs and device pointers: as for the calls above.
+ *  - Aliasing: out == a (out2 == ct2) exactly is allowed as in the batched calls; any other overlap of the host ranges is
+ *    HIPBFV_E_INVALIDARG before anything runs. */
+long hipbfv_Pool_MultiplyRelinKeys(void *pool, const uint64_t *a, const uint64_t *b, void *const *relin_key_sets,
+                                   uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out, uint64_t count);
+long hipbfv_Pool_RotateRowsKeys(void *pool, const uint64_t *ct2, int steps, void *const *galois_key_sets, uint64_t num_key_sets,
+                                const uint32_t *key_index, uint64_t *out2, uint64_t count);
+long hipbfv_Pool_RotateColumnsKeys(void *pool, const uint64_t *ct2, void *const *galois_key_sets, uint64_t num_key_sets,
+                                   const uint32_t *key_index, uint64_t *out2, uint64_t count);
+long hipbfv_Pool_ProgramRunKeys(void *pool, void *program, uint64_t batch, uint64_t num_inputs, const uint32_t *input_kinds,
+                                const uint64_t *const *input_ptrs, const uint64_t *input_strides, uint64_t num_key_sets,
+                                void *const *relin_keys, void *const *galois_keys, const uint32_t *key_index,
+                                uint64_t num_outputs, uint64_t *const *outputs);
+long hipbfv_Pool_SetKeyCacheBytes(void *pool, uint64_t bytes);
 /* the pool's shard rule, host only: member `member` of `members` gets input sets [*begin, *end) of a batch */
 long hipbfv_debug_pool_shard(uint64_t batch, uint32_t members, uint32_t member, uint64_t *begin, uint64_t *end);
+/* the pool's per-chunk key table, host only: for chunk `chunk_no` of member `member`'s shard (`chunk` input sets per chunk, at
+ * most the shard), local_sets[0, *local_count) = the distinct key sets the chunk names, ascending in the caller's numbering
+ * (capacity num_key_sets), and remapped[0, *sets_in_chunk) = the chunk's key_index as indices into local_sets (capacity
+ * `chunk`).  A member, a chunk number or a key index out of range is HIPBFV_E_INVALIDARG. */
+long hipbfv_debug_pool_keyplan(const uint32_t *key_index, uint64_t batch, uint64_t num_key_sets, uint32_t members, uint32_t member,
+                               uint64_t chunk, uint64_t chunk_no, uint32_t *local_sets, uint64_t *local_count,
+                               uint32_t *remapped, uint64_t *sets_in_chunk);
 
 /* Per-kernel timing (HIP events recorded on the launch stream, around every kernel launch):
  * total milliseconds, number of launches and work units (residue polynomials for the NTT kernels,

@@ -640,4 +640,58 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
   }
 };
 
+// The device pool (hipbfv.h, "Device pool"): host-resident batches u64[count][2][K][N] sharded over several GPUs, every input
+// set with its own client's keys (key_index[i] picks the set; an entry no input set names may be nullptr).  `out` may be the
+// first operand itself.  Not part of the reference crate's surface.
+class DevicePool : public detail::Handle<hipbfv_Pool_Destroy, detail::no_copy> {
+ public:
+  DevicePool(const Context& ctx, const std::vector<int>& devices) {
+    check(hipbfv_Pool_Create(ctx.get_handle(), devices.data(), (uint32_t)devices.size(), &h_));
+  }
+  void set_chunk(uint64_t sets_per_chunk) const { check(hipbfv_Pool_SetChunk(h_, sets_per_chunk)); }
+  // bound, per member, on the bytes of key copies it keeps; 0 = no bound
+  void set_key_cache_bytes(uint64_t bytes) const { check(hipbfv_Pool_SetKeyCacheBytes(h_, bytes)); }
+  std::string describe() const {
+    uint64_t needed = 0;
+    check(hipbfv_Pool_Describe(h_, nullptr, 0, &needed));
+    std::string text(needed, '\0');
+    check(hipbfv_Pool_Describe(h_, &text[0], needed, &needed));
+    text.resize(needed ? needed - 1 : 0);
+    return text;
+  }
+  void multiply_relin(const uint64_t* a, const uint64_t* b, const RelinearizationKeys& rk, uint64_t* out, uint64_t count) const {
+    check(hipbfv_Pool_MultiplyRelin(h_, a, b, rk.get_handle(), out, count));
+  }
+  void multiply_relin_keys(const uint64_t* a, const uint64_t* b, const std::vector<const RelinearizationKeys*>& keys,
+                           const std::vector<uint32_t>& key_index, uint64_t* out) const {
+    const std::vector<void*> hs = handles(keys);
+    check(hipbfv_Pool_MultiplyRelinKeys(h_, a, b, hs.data(), hs.size(), key_index.data(), out, key_index.size()));
+  }
+  void rotate_rows_keys(const uint64_t* ct, int steps, const std::vector<const GaloisKeys*>& keys, const std::vector<uint32_t>& key_index,
+                        uint64_t* out) const {
+    const std::vector<void*> hs = handles(keys);
+    check(hipbfv_Pool_RotateRowsKeys(h_, ct, steps, hs.data(), hs.size(), key_index.data(), out, key_index.size()));
+  }
+  void rotate_columns_keys(const uint64_t* ct, const std::vector<const GaloisKeys*>& keys, const std::vector<uint32_t>& key_index,
+                           uint64_t* out) const {
+    const std::vector<void*> hs = handles(keys);
+    check(hipbfv_Pool_RotateColumnsKeys(h_, ct, hs.data(), hs.size(), key_index.data(), out, key_index.size()));
+  }
+  // a rotation batch with one shared key set
+  void rotate_rows(const uint64_t* ct, int steps, const GaloisKeys& gk, uint64_t* out, uint64_t count) const {
+    rotate_rows_keys(ct, steps, {&gk}, std::vector<uint32_t>(count, 0), out);
+  }
+  void rotate_columns(const uint64_t* ct, const GaloisKeys& gk, uint64_t* out, uint64_t count) const {
+    rotate_columns_keys(ct, {&gk}, std::vector<uint32_t>(count, 0), out);
+  }
+
+ private:
+  template <typename K>
+  static std::vector<void*> handles(const std::vector<const K*>& keys) {
+    std::vector<void*> hs;
+    for (const K* k : keys) hs.push_back(k ? k->get_handle() : nullptr);
+    return hs;
+  }
+};
+
 }  // namespace seal_fhe

@@ -4,6 +4,10 @@
 //! "Device pool").  A call splits the batch into contiguous shards, one per member, and returns when every output is in host
 //! memory; each member overlaps its host-to-device copies, its compute and its device-to-host copies.  Input set i gives
 //! exactly the bits of the single-device call on input set i.  Host slices may be pinned or pageable.
+//!
+//! The `_keys` calls serve a batch whose input sets belong to several clients: input set i uses key set `key_index[i]`, in any
+//! order, and a member copies only the keys its own shard names and the call needs ([`DevicePool::set_key_cache_bytes`] bounds
+//! what it keeps).
 use std::ffi::c_void;
 use std::ptr::null_mut;
 
@@ -47,7 +51,12 @@ impl DevicePool {
         check(unsafe { bindgen::hipbfv_Pool_SetChunk(self.handle, sets_per_chunk) })
     }
 
-    /// One line per member: device, chunk, key copies made so far, buffer sizes.
+    /// Bound, per member, on the bytes of key copies it keeps (least recently used copies go first); 0 = no bound (the default).
+    pub fn set_key_cache_bytes(&self, bytes: u64) -> Result<()> {
+        check(unsafe { bindgen::hipbfv_Pool_SetKeyCacheBytes(self.handle, bytes) })
+    }
+
+    /// One line per member: device, chunk, key copies made so far, buffer sizes, bytes of key copies held, copies dropped.
     pub fn describe(&self) -> Result<String> {
         let mut needed = 0u64;
         check(unsafe { bindgen::hipbfv_Pool_Describe(self.handle, null_mut(), 0, &mut needed) })?;
@@ -66,12 +75,73 @@ impl DevicePool {
         check(unsafe { bindgen::hipbfv_Pool_MultiplyRelin(self.handle, a.as_ptr(), b.as_ptr(), rk.get_handle(), out.as_mut_ptr(), count) })
     }
 
+    fn count_of(&self, key_index: &[u32], slices: &[usize]) -> Result<u64> {
+        let count = key_index.len();
+        if slices.iter().any(|&len| len != count * self.ct_words) {
+            return Err(Error::InvalidArgument(format!("slices of {:?} words for {} ciphertexts of {}", slices, count, self.ct_words)));
+        }
+        Ok(count as u64)
+    }
+
+    /// `out[i] = relinearize(a[i] * b[i])` with `keys[key_index[i]]`; an entry of `keys` that no input set names may be `None`.
+    pub fn multiply_relin_keys(
+        &self, a: &[u64], b: &[u64], keys: &[Option<&RelinearizationKeys>], key_index: &[u32], out: &mut [u64],
+    ) -> Result<()> {
+        let count = self.count_of(key_index, &[a.len(), b.len(), out.len()])?;
+        let hs: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(null_mut(), |k| k.get_handle())).collect();
+        check(unsafe {
+            bindgen::hipbfv_Pool_MultiplyRelinKeys(self.handle, a.as_ptr(), b.as_ptr(), hs.as_ptr(), hs.len() as u64, key_index.as_ptr(), out.as_mut_ptr(), count)
+        })
+    }
+
+    /// Rows rotated by `steps` with every input set's own Galois keys: a set that holds the key of `steps` uses it, a set with
+    /// only the power-of-two keys takes the NAF chain, both in one call.
+    pub fn rotate_rows_keys(&self, ct: &[u64], steps: i32, keys: &[Option<&GaloisKeys>], key_index: &[u32], out: &mut [u64]) -> Result<()> {
+        let count = self.count_of(key_index, &[ct.len(), out.len()])?;
+        let hs: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(null_mut(), |k| k.get_handle())).collect();
+        check(unsafe {
+            bindgen::hipbfv_Pool_RotateRowsKeys(self.handle, ct.as_ptr(), steps, hs.as_ptr(), hs.len() as u64, key_index.as_ptr(), out.as_mut_ptr(), count)
+        })
+    }
+
+    pub fn rotate_columns_keys(&self, ct: &[u64], keys: &[Option<&GaloisKeys>], key_index: &[u32], out: &mut [u64]) -> Result<()> {
+        let count = self.count_of(key_index, &[ct.len(), out.len()])?;
+        let hs: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(null_mut(), |k| k.get_handle())).collect();
+        check(unsafe {
+            bindgen::hipbfv_Pool_RotateColumnsKeys(self.handle, ct.as_ptr(), hs.as_ptr(), hs.len() as u64, key_index.as_ptr(), out.as_mut_ptr(), count)
+        })
+    }
+
+    /// A rotation batch with one shared key set.
+    pub fn rotate_rows(&self, ct: &[u64], steps: i32, gk: &GaloisKeys, out: &mut [u64]) -> Result<()> {
+        self.rotate_rows_keys(ct, steps, &[Some(gk)], &vec![0u32; ct.len() / self.ct_words], out)
+    }
+
+    pub fn rotate_columns(&self, ct: &[u64], gk: &GaloisKeys, out: &mut [u64]) -> Result<()> {
+        self.rotate_columns_keys(ct, &[Some(gk)], &vec![0u32; ct.len() / self.ct_words], out)
+    }
+
     /// [`Program::run`] over host memory: one `u64[batch][2][K][N]` output slice per `OutputCiphertext` node, in node order.
     pub fn run(
         &self, program: &Program, batch: u64, inputs: &[HostInput], rk: Option<&RelinearizationKeys>, gk: Option<&GaloisKeys>,
         outputs: &mut [&mut [u64]],
     ) -> Result<()> {
+        self.run_keys(program, batch, inputs, &[rk], &[gk], None, outputs)
+    }
+
+    /// [`Program::run_keys`] over host memory: input set i runs with `rk[key_index[i]]`, `gk[key_index[i]]` (`key_index`
+    /// `None`: the one key set of [`DevicePool::run`]).
+    pub fn run_keys(
+        &self, program: &Program, batch: u64, inputs: &[HostInput], rk: &[Option<&RelinearizationKeys>], gk: &[Option<&GaloisKeys>],
+        key_index: Option<&[u32]>, outputs: &mut [&mut [u64]],
+    ) -> Result<()> {
         let (ct, n, b) = (self.ct_words, self.n, batch as usize);
+        let sets = rk.len().max(gk.len());
+        if let Some(ki) = key_index {
+            if ki.len() != b || sets == 0 {
+                return Err(Error::InvalidArgument(format!("{} key indices for {} input sets over {} key sets", ki.len(), batch, sets)));
+            }
+        }
         for i in inputs {
             let (len, want) = match i {
                 HostInput::Ciphertexts(s) => (s.len(), b * ct),
@@ -92,11 +162,19 @@ impl DevicePool {
             .collect();
         let strides: Vec<u64> = inputs.iter().map(|i| match i { HostInput::Plaintexts(_) => n as u64, _ => 0 }).collect();
         let outs: Vec<*mut u64> = outputs.iter_mut().map(|o| o.as_mut_ptr()).collect();
+        let rks: Vec<*mut c_void> = (0..sets).map(|i| rk.get(i).copied().flatten().map_or(null_mut(), |k| k.get_handle())).collect();
+        let gks: Vec<*mut c_void> = (0..sets).map(|i| gk.get(i).copied().flatten().map_or(null_mut(), |k| k.get_handle())).collect();
         check(unsafe {
-            bindgen::hipbfv_Pool_ProgramRun(
-                self.handle, program.get_handle(), batch, inputs.len() as u64, kinds.as_ptr(), ptrs.as_ptr(), strides.as_ptr(),
-                rk.map_or(null_mut(), |k| k.get_handle()), gk.map_or(null_mut(), |k| k.get_handle()), outs.len() as u64, outs.as_ptr(),
-            )
+            match key_index {
+                None => bindgen::hipbfv_Pool_ProgramRun(
+                    self.handle, program.get_handle(), batch, inputs.len() as u64, kinds.as_ptr(), ptrs.as_ptr(), strides.as_ptr(),
+                    rks.first().copied().unwrap_or(null_mut()), gks.first().copied().unwrap_or(null_mut()), outs.len() as u64, outs.as_ptr(),
+                ),
+                Some(ki) => bindgen::hipbfv_Pool_ProgramRunKeys(
+                    self.handle, program.get_handle(), batch, inputs.len() as u64, kinds.as_ptr(), ptrs.as_ptr(), strides.as_ptr(),
+                    sets as u64, rks.as_ptr(), gks.as_ptr(), ki.as_ptr(), outs.len() as u64, outs.as_ptr(),
+                ),
+            }
         })
     }
 }

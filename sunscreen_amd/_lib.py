@@ -204,7 +204,14 @@ _SIGNATURES = {
     "hipbfv_Pool_Describe": [vp, C.c_char_p, u64, u64p],
     "hipbfv_Pool_MultiplyRelin": [vp, vp, vp, vp, vp, u64],
     "hipbfv_Pool_ProgramRun": [vp, vp, u64, u64, C.POINTER(C.c_uint32), vpp, u64p, vp, vp, u64, vpp],
+    "hipbfv_Pool_MultiplyRelinKeys": [vp, vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64],
+    "hipbfv_Pool_RotateRowsKeys": [vp, vp, C.c_int, vpp, u64, C.POINTER(C.c_uint32), vp, u64],
+    "hipbfv_Pool_RotateColumnsKeys": [vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64],
+    "hipbfv_Pool_ProgramRunKeys": [vp, vp, u64, u64, C.POINTER(C.c_uint32), vpp, u64p, u64, vpp, vpp, C.POINTER(C.c_uint32), u64, vpp],
+    "hipbfv_Pool_SetKeyCacheBytes": [vp, u64],
     "hipbfv_debug_pool_shard": [u64, C.c_uint32, C.c_uint32, u64p, u64p],
+    "hipbfv_debug_pool_keyplan": [C.POINTER(C.c_uint32), u64, u64, C.c_uint32, C.c_uint32, u64, u64, C.POINTER(C.c_uint32), u64p,
+                                  C.POINTER(C.c_uint32), u64p],
     "hipbfv_profile_enable": [vp, C.c_bool],
     "hipbfv_profile_reset": [vp],
     "hipbfv_profile_kernel_count": [C.POINTER(C.c_uint32)],

@@ -12,6 +12,7 @@
 #include <cerrno>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -1928,21 +1929,14 @@ static hipError_t copy_items(u64* stage, const u64* batch_in, u64* batch_out, si
   return hipSuccess;
 }
 
-long hipbfv_batch_rotate_rows_keys(void* h, const uint64_t* ct2, int steps, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
-                                   uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
-  EVAL_OR_RETURN(h);
-  if (!ct2 || !out2) return HIPBFV_E_POINTER;
-  if (!e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
-  KEYSETS_OR_RETURN();
+// hipbfv_batch_rotate_rows_keys past its argument checks (steps != 0, count != 0): every referenced set decides as the single-key
+// call does.  watch2 (the device pool: two device status words, or nullptr to stay in the caller's watch scope): a batch whose
+// sets decide alike is watched in watch2[0]; one that splits has the direct group watched in watch2[0], the chain group in
+// watch2[1], and groups[g] lists the batch items of group g in the order the group's status word counts them.
+static long batch_rotate_rows_keys_impl(EvalObj* e, const u64* ct2, int steps, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
+                                        u64* out2, uint64_t count, hipStream_t s, u32* watch2 = nullptr,
+                                        std::vector<uint64_t>* groups = nullptr) {
   const size_t w = e->ctx->ct_words(2);
-  ALIAS_OR_RETURN(cts(out2, w, count), {cts(ct2, w, count)});
-  hipStream_t s = (hipStream_t)stream;
-  if (steps == 0) {
-    if ((const u64*)ct2 != (u64*)out2 && hipMemcpyAsync(out2, ct2, count * w * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess)
-      return from_status(kHipError);
-    return HIPBFV_S_OK;
-  }
-  if (!count) return HIPBFV_S_OK;
   const u32 elt = e->ev->galois_elt_from_step(steps);
   if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
   // per referenced set, as the single-key call decides: the direct key, or else every key of the NAF chain
@@ -1960,8 +1954,10 @@ long hipbfv_batch_rotate_rows_keys(void* h, const uint64_t* ct2, int steps, void
     }
     (direct[k] ? any_direct : any_naf) = true;
   }
-  if (!(any_direct && any_naf))  // the common case: one call over the caller's buffers
-    return batch_rotate_keys_internal(e, (const u64*)ct2, steps, key_sets, num_sets, key_index, (u64*)out2, count, s);
+  if (!(any_direct && any_naf)) {  // the common case: one call over the caller's buffers
+    WatchScope scope(watch2 ? watch2 : Evaluator::watch_status());
+    return batch_rotate_keys_internal(e, ct2, steps, key_sets, num_sets, key_index, out2, count, s);
+  }
   // the sets disagree: the direct group and the NAF group run apart, each gathered into a compact stage and scattered back
   std::vector<uint64_t> items[2];
   std::vector<uint32_t> kidx[2];
@@ -1976,11 +1972,33 @@ long hipbfv_batch_rotate_rows_keys(void* h, const uint64_t* ct2, int steps, void
   u64* out_stage = in_stage + std::max(items[0].size(), items[1].size()) * w;
   for (int g = 0; g < 2; g++) {
     const uint64_t c = items[g].size();
-    if (copy_items(in_stage, (const u64*)ct2, nullptr, w, w, items[g], s) != hipSuccess) return from_status(kHipError);
-    if (long hr = batch_rotate_keys_internal(e, in_stage, steps, key_sets, num_sets, kidx[g].data(), out_stage, c, s)) return hr;
-    if (copy_items(out_stage, nullptr, (u64*)out2, w, w, items[g], s) != hipSuccess) return from_status(kHipError);
+    if (copy_items(in_stage, ct2, nullptr, w, w, items[g], s) != hipSuccess) return from_status(kHipError);
+    {
+      WatchScope scope(watch2 ? watch2 + g : Evaluator::watch_status());
+      if (long hr = batch_rotate_keys_internal(e, in_stage, steps, key_sets, num_sets, kidx[g].data(), out_stage, c, s)) return hr;
+    }
+    if (copy_items(out_stage, nullptr, out2, w, w, items[g], s) != hipSuccess) return from_status(kHipError);
+    if (groups) groups[g] = std::move(items[g]);
   }
   return HIPBFV_S_OK;
+}
+
+long hipbfv_batch_rotate_rows_keys(void* h, const uint64_t* ct2, int steps, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
+                                   uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!ct2 || !out2) return HIPBFV_E_POINTER;
+  if (!e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
+  KEYSETS_OR_RETURN();
+  const size_t w = e->ctx->ct_words(2);
+  ALIAS_OR_RETURN(cts(out2, w, count), {cts(ct2, w, count)});
+  hipStream_t s = (hipStream_t)stream;
+  if (steps == 0) {
+    if ((const u64*)ct2 != (u64*)out2 && hipMemcpyAsync(out2, ct2, count * w * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess)
+      return from_status(kHipError);
+    return HIPBFV_S_OK;
+  }
+  if (!count) return HIPBFV_S_OK;
+  return batch_rotate_rows_keys_impl(e, (const u64*)ct2, steps, key_sets, num_sets, key_index, (u64*)out2, count, s);
 HIPBFV_END
 
 long hipbfv_batch_rotate_columns_keys(void* h, const uint64_t* ct2, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
@@ -3915,6 +3933,14 @@ long hipbfv_Pool_SetChunk(void* pool, uint64_t sets_per_chunk) HIPBFV_BEGIN
   return HIPBFV_S_OK;
 HIPBFV_END
 
+long hipbfv_Pool_SetKeyCacheBytes(void* pool, uint64_t bytes) HIPBFV_BEGIN
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  if (!p) return HIPBFV_E_POINTER;
+  std::lock_guard<std::mutex> g(p->mu);
+  p->key_cache_bytes = bytes;  // holds from the next call's first chunk on
+  return HIPBFV_S_OK;
+HIPBFV_END
+
 long hipbfv_Pool_Describe(void* pool, char* buffer, uint64_t capacity, uint64_t* needed) HIPBFV_BEGIN
   PoolObj* p = as<PoolObj>(pool, kMagicPool);
   if (!p || !needed) return HIPBFV_E_POINTER;
@@ -3923,9 +3949,11 @@ long hipbfv_Pool_Describe(void* pool, char* buffer, uint64_t capacity, uint64_t*
     std::lock_guard<std::mutex> g(p->mu);
     for (size_t i = 0; i < p->members.size(); i++) {
       const PoolMember& m = *p->members[i];
-      char line[256];
-      snprintf(line, sizeof(line), "member=%zu device=%d chunk=%llu key_copies=%llu keys_cached=%zu slot_words=%zu bounce_words=%zu\n", i, m.device,
-               (unsigned long long)p->chunk_sets(), (unsigned long long)m.key_copies, m.key_copy.size(), m.dev_words, m.bounce_words);
+      char line[384];
+      snprintf(line, sizeof(line),
+               "member=%zu device=%d chunk=%llu key_copies=%llu keys_cached=%zu slot_words=%zu bounce_words=%zu key_bytes=%llu key_evictions=%llu\n", i,
+               m.device, (unsigned long long)p->chunk_sets(), (unsigned long long)m.key_copies, m.key_copy.size(), m.dev_words, m.bounce_words,
+               (unsigned long long)m.key_bytes, (unsigned long long)m.key_evictions);
       text += line;
     }
   }
@@ -3954,58 +3982,188 @@ long hipbfv_Pool_MultiplyRelin(void* pool, const uint64_t* a, const uint64_t* b,
     return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_MultiplyRelin takes host memory (device pointers are not accepted)");
   const std::vector<PoolIn> ins = {{(const u64*)a, w, w, ka == HostMem::kPinned}, {(const u64*)b, w, w, kb == HostMem::kPinned}};
   const std::vector<PoolOut> outs = {{(u64*)out, w, ko == HostMem::kPinned}};
-  const u64 chunk = p->chunk_sets();
+  const u64 chunk = p->chunk_sets(), bound = p->key_cache_bytes;
   const bool watch = g_throw_transparent;
   return pool_dispatch(*p, count, [&](PoolMember& m, u64 lo, u64 hi) -> long {
-    if (long hr = member_keys(m, rk, {})) return hr;
+    if (long hr = member_keys(m, rk, {}, bound)) return hr;
     const u64* key = m.relin_view.find(0);
     const u64 sets = std::min<u64>(chunk, hi - lo);  // member_run's chunk: never more than the shard
     const u64 nch = (hi - lo + sets - 1) / sets;
-    // one watch word per chunk, all read back after the last chunk: no small copy on the compute stream queues behind the
-    // out stream's large ones
-    if (watch) {
-      if (m.status_cap < nch) {
-        if (m.status) (void)hipFree(m.status);
-        m.status = nullptr;
-        m.status_cap = 0;
-        if (hipMalloc((void**)&m.status, nch * sizeof(u32)) != hipSuccess) {
-          (void)hipGetLastError();
-          m.status = nullptr;
-          return from_status(kOutOfMemory);
-        }
-        m.status_cap = nch;
-      }
-      size_t cap = m.flag_cap;
-      if (!grow_pinned((void**)&m.flags, &cap, nch * sizeof(u32))) return from_status(kOutOfMemory);
-      m.flag_cap = cap;
-      if (hipMemsetAsync(m.status, 0xFF, nch * sizeof(u32), m.comp) != hipSuccess) return from_status(kHipError);
-    }
+    if (watch)  // one watch word per chunk
+      if (long hr = member_watch_begin(m, nch)) return hr;
     long hr = member_run(m, ins, outs, lo, hi, sets, [&](u64 j, const std::vector<const u64*>& in, const std::vector<u64*>& o, u64 c, u64) -> long {
       WatchScope scope(watch ? m.status + j : nullptr);
       return from_status(m.eval.ev->multiply_relin(in[0], in[1], key, o[0], c, m.comp));
     });
     if (hr != HIPBFV_S_OK || !watch) return hr;
-    if (hipMemcpyAsync(m.flags, m.status, nch * sizeof(u32), hipMemcpyDeviceToHost, m.comp) != hipSuccess || hipStreamSynchronize(m.comp) != hipSuccess)
-      return from_status(kHipError);
+    if (long hr2 = member_watch_read(m, nch)) return hr2;
     for (u64 j = 0; j < nch; j++)
-      if (m.flags[j] != 0xFFFFFFFFu) {
-        char msg[128];
-        snprintf(msg, sizeof(msg), "result ciphertext is transparent (input set %llu of the batch)", (unsigned long long)(lo + j * sets + m.flags[j]));
-        return fail(HIPBFV_COR_E_INVALIDOPERATION, msg);
-      }
+      if (m.flags[j] != 0xFFFFFFFFu) return pool_transparent(lo + j * sets + m.flags[j]);
     return HIPBFV_S_OK;
   });
 HIPBFV_END
 
-long hipbfv_Pool_ProgramRun(void* pool, void* program, uint64_t batch, uint64_t num_inputs, const uint32_t* input_kinds,
-                            const uint64_t* const* input_ptrs, const uint64_t* input_strides, void* relin_keys, void* galois_keys,
-                            uint64_t num_outputs, uint64_t* const* outputs) HIPBFV_BEGIN
+long hipbfv_Pool_MultiplyRelinKeys(void* pool, const uint64_t* a, const uint64_t* b, void* const* key_sets, uint64_t num_sets,
+                                   const uint32_t* key_index, uint64_t* out, uint64_t count) HIPBFV_BEGIN
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  if (!p) return HIPBFV_E_POINTER;
+  if (count && (!a || !b || !out)) return HIPBFV_E_POINTER;
+  if (!key_sets || !key_index || !num_sets || num_sets > 0xFFFFFFFFull) return HIPBFV_E_POINTER;
+  std::lock_guard<std::mutex> g(p->mu);
+  const size_t w = p->ct_words();
+  ALIAS_OR_RETURN(cts(out, w, count), {cts(a, w, count), cts(b, w, count)});
+  PoolSetKeys all;
+  if (long hr = pool_set_keys(*p, key_sets, nullptr, num_sets, key_index, count,
+                              [](KeysObj* r, KeysObj*, std::vector<PoolKey>* need, std::vector<PoolKey>*) {
+                                PoolKey k;
+                                if (!r || !pool_key_of(r, 0, &k)) return false;
+                                need->push_back(k);
+                                return true;
+                              },
+                              &all))
+    return hr;
+  if (!count) return HIPBFV_S_OK;
+  const size_t bytes = count * w * sizeof(u64);
+  bool pa, pb, po;
+  if (!pool_host_operand(a, bytes, &pa) || !pool_host_operand(b, bytes, &pb) || !pool_host_operand(out, bytes, &po))
+    return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_MultiplyRelinKeys takes host memory (device pointers are not accepted)");
+  const std::vector<PoolIn> ins = {{(const u64*)a, w, w, pa}, {(const u64*)b, w, w, pb}};
+  const std::vector<PoolOut> outs = {{(u64*)out, w, po}};
+  const u64 chunk = p->chunk_sets(), bound = p->key_cache_bytes;
+  const bool watch = g_throw_transparent;
+  return pool_dispatch(*p, count, [&](PoolMember& m, u64 lo, u64 hi) -> long {
+    const u64 sets = std::min<u64>(chunk, hi - lo);
+    const u64 nch = (hi - lo + sets - 1) / sets;
+    if (watch)
+      if (long hr = member_watch_begin(m, nch)) return hr;
+    PoolChunkKeys ck;
+    std::vector<const u64*> tab;
+    long hr = member_run(m, ins, outs, lo, hi, sets, [&](u64 j, const std::vector<const u64*>& in, const std::vector<u64*>& o, u64 c, u64 first) -> long {
+      if (long hr = member_chunk_keys(m, all, key_index + first, c, bound, &ck)) return hr;
+      const KeySel sel = keys_sel(ck.relin.data(), ck.relin.size(), ck.index.data(), c, &m.eval, 0, tab);
+      if (!sel.present()) return fail(HIPBFV_E_UNEXPECTED, "a chunk's key table lacks a relinearisation key");
+      WatchScope scope(watch ? m.status + j : nullptr);
+      return from_status(m.eval.ev->multiply_relin(in[0], in[1], sel, o[0], c, m.comp));
+    });
+    if (hr != HIPBFV_S_OK || !watch) return hr;
+    if (long hr2 = member_watch_read(m, nch)) return hr2;
+    for (u64 j = 0; j < nch; j++)
+      if (m.flags[j] != 0xFFFFFFFFu) return pool_transparent(lo + j * sets + m.flags[j]);
+    return HIPBFV_S_OK;
+  });
+HIPBFV_END
+
+// The two rotation batches: `elt` != 0 is one Galois automorphism for every set (the column rotation), otherwise a row rotation by
+// `steps` whose referenced sets decide one by one between the direct key and the NAF chain
+static long pool_rotate_keys(const char* name, void* pool, const uint64_t* ct2, int steps, bool columns, void* const* key_sets, uint64_t num_sets,
+                             const uint32_t* key_index, uint64_t* out2, uint64_t count) {
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  if (!p) return HIPBFV_E_POINTER;
+  if (count && (!ct2 || !out2)) return HIPBFV_E_POINTER;
+  if (!key_sets || !key_index || !num_sets || num_sets > 0xFFFFFFFFull) return HIPBFV_E_POINTER;
+  std::lock_guard<std::mutex> g(p->mu);
+  const PoolMember& m0 = *p->members[0];
+  if (!m0.ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
+  const size_t w = p->ct_words();
+  ALIAS_OR_RETURN(cts(out2, w, count), {cts(ct2, w, count)});
+  const Evaluator& ev0 = *m0.eval.ev;  // galois_elt_from_step: host arithmetic on the parameters
+  const u32 elt = columns ? 2 * p->n - 1 : steps ? ev0.galois_elt_from_step(steps) : 1;
+  if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
+  const bool copy_only = !columns && steps == 0;  // the identity: no key is read
+  const std::vector<int> naf = columns || copy_only ? std::vector<int>() : naf_parts(steps);
+  PoolSetKeys all;
+  if (long hr = pool_set_keys(*p, nullptr, key_sets, num_sets, key_index, count,
+                              [&](KeysObj*, KeysObj* gk, std::vector<PoolKey>*, std::vector<PoolKey>* need) {
+                                if (copy_only) return true;
+                                PoolKey k;
+                                if (!gk) return false;
+                                if (pool_key_of(gk, (elt - 1) >> 1, &k)) {  // the direct key: the only one this set's rotation reads
+                                  need->push_back(k);
+                                  return true;
+                                }
+                                if (naf.size() < 2) return false;
+                                for (int part : naf) {
+                                  if (naf_skip(part, p->n)) continue;
+                                  if (!pool_key_of(gk, (ev0.galois_elt_from_step(part) - 1) >> 1, &k)) return false;
+                                  need->push_back(k);
+                                }
+                                return true;
+                              },
+                              &all))
+    return hr;
+  if (!count) return HIPBFV_S_OK;
+  const size_t bytes = count * w * sizeof(u64);
+  bool pi, po;
+  if (!pool_host_operand(ct2, bytes, &pi) || !pool_host_operand(out2, bytes, &po)) {
+    const std::string msg = std::string(name) + " takes host memory (device pointers are not accepted)";
+    return fail(HIPBFV_E_INVALIDARG, msg.c_str());
+  }
+  const std::vector<PoolIn> ins = {{(const u64*)ct2, w, w, pi}};
+  const std::vector<PoolOut> outs = {{(u64*)out2, w, po}};
+  const u64 chunk = p->chunk_sets(), bound = p->key_cache_bytes;
+  const bool watch = g_throw_transparent && !copy_only;
+  return pool_dispatch(*p, count, [&](PoolMember& m, u64 lo, u64 hi) -> long {
+    const u64 sets = std::min<u64>(chunk, hi - lo);
+    const u64 nch = (hi - lo + sets - 1) / sets;
+    if (watch)  // two watch words per chunk: a row rotation may split the chunk into a direct and a chain group
+      if (long hr = member_watch_begin(m, 2 * nch)) return hr;
+    PoolChunkKeys ck;
+    std::vector<const u64*> tab;
+    std::map<u64, std::array<std::vector<uint64_t>, 2>> split;  // chunk -> the chunk items of its two groups
+    long hr = member_run(m, ins, outs, lo, hi, sets, [&](u64 j, const std::vector<const u64*>& in, const std::vector<u64*>& o, u64 c, u64 first) -> long {
+      if (copy_only)
+        return hipMemcpyAsync(o[0], in[0], c * w * sizeof(u64), hipMemcpyDeviceToDevice, m.comp) == hipSuccess ? HIPBFV_S_OK : from_status(kHipError);
+      if (long hr = member_chunk_keys(m, all, key_index + first, c, bound, &ck)) return hr;
+      if (columns) {
+        const KeySel sel = keys_sel(ck.galois.data(), ck.galois.size(), ck.index.data(), c, &m.eval, (elt - 1) >> 1, tab);
+        if (!sel.present()) return fail(HIPBFV_E_UNEXPECTED, "a chunk's key table lacks a Galois key");
+        WatchScope scope(watch ? m.status + 2 * j : nullptr);
+        return from_status(m.eval.ev->apply_galois(in[0], elt, sel, o[0], c, m.comp));
+      }
+      std::vector<uint64_t> groups[2];
+      if (long hr = batch_rotate_rows_keys_impl(&m.eval, in[0], steps, ck.galois.data(), ck.galois.size(), ck.index.data(), o[0], c, m.comp,
+                                                watch ? m.status + 2 * j : nullptr, groups))
+        return hr;
+      if (!groups[0].empty() || !groups[1].empty()) split[j] = {std::move(groups[0]), std::move(groups[1])};
+      return HIPBFV_S_OK;
+    });
+    if (hr != HIPBFV_S_OK || !watch) return hr;
+    if (long hr2 = member_watch_read(m, 2 * nch)) return hr2;
+    for (u64 j = 0; j < nch; j++) {
+      u64 bad = ~(u64)0;
+      auto sp = split.find(j);
+      for (int g = 0; g < 2; g++) {
+        const u32 f = m.flags[2 * j + g];
+        if (f != 0xFFFFFFFFu) bad = std::min<u64>(bad, sp == split.end() ? f : sp->second[g][f]);
+      }
+      if (bad != ~(u64)0) return pool_transparent(lo + j * sets + bad);
+    }
+    return HIPBFV_S_OK;
+  });
+}
+
+long hipbfv_Pool_RotateRowsKeys(void* pool, const uint64_t* ct2, int steps, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
+                                uint64_t* out2, uint64_t count) HIPBFV_BEGIN
+  return pool_rotate_keys("hipbfv_Pool_RotateRowsKeys", pool, ct2, steps, false, key_sets, num_sets, key_index, out2, count);
+HIPBFV_END
+
+long hipbfv_Pool_RotateColumnsKeys(void* pool, const uint64_t* ct2, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index, uint64_t* out2,
+                                   uint64_t count) HIPBFV_BEGIN
+  return pool_rotate_keys("hipbfv_Pool_RotateColumnsKeys", pool, ct2, 0, true, key_sets, num_sets, key_index, out2, count);
+HIPBFV_END
+
+// hipbfv_Pool_ProgramRun (key_index == nullptr: one key set, every buffer of its two handles goes to every member) and
+// hipbfv_Pool_ProgramRunKeys (input set i runs with the keys of set key_index[i]; a member copies what its chunks name)
+static long pool_program_run(const char* name, void* pool, void* program, uint64_t batch, uint64_t num_inputs, const uint32_t* input_kinds,
+                             const uint64_t* const* input_ptrs, const uint64_t* input_strides, uint64_t num_key_sets, void* const* relin_keys,
+                             void* const* galois_keys, const uint32_t* key_index, uint64_t num_outputs, uint64_t* const* outputs) {
   PoolObj* p = as<PoolObj>(pool, kMagicPool);
   ProgramObj* prog = as<ProgramObj>(program, kMagicProgram);
   if (!p || !prog || (num_inputs && (!input_kinds || !input_ptrs || !input_strides)) || (num_outputs && !outputs)) return HIPBFV_E_POINTER;
+  const std::string me(name);
   for (uint64_t i = 0; i < num_inputs; i++) {
     if (input_kinds[i] == 2)
-      return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_ProgramRun takes host inputs of kinds 0 and 1 (kind 2, device-resident transformed plaintexts, is not accepted)");
+      return fail(HIPBFV_E_INVALIDARG, (me + " takes host inputs of kinds 0 and 1 (kind 2, device-resident transformed plaintexts, is not accepted)").c_str());
     if (input_kinds[i] > 2) return fail(HIPBFV_E_INVALIDARG, "unknown input kind");
   }
   {
@@ -4019,25 +4177,47 @@ long hipbfv_Pool_ProgramRun(void* pool, void* program, uint64_t batch, uint64_t 
   if (num_outputs != prog->prog.num_outputs()) return fail(HIPBFV_E_INVALIDARG, "wrong number of output buffers");
   std::lock_guard<std::mutex> g(p->mu);
   // the keys the graph needs are checked here, before anything is launched; a key of other parameters counts as absent
-  const std::vector<PoolKey> rk = pool_keys_of(*p, relin_keys, true), gk = pool_keys_of(*p, galois_keys, false);
   bool need_relin = false, need_galois = false;
   prog->prog.key_needs(&need_relin, &need_galois);
-  if ((need_relin && rk.empty()) || (need_galois && gk.empty())) return from_status(kNoKey);
+  std::vector<PoolKey> rk, gk;
+  PoolSetKeys all;
+  if (!key_index) {
+    rk = pool_keys_of(*p, relin_keys[0], true);
+    gk = pool_keys_of(*p, galois_keys[0], false);
+    if ((need_relin && rk.empty()) || (need_galois && gk.empty())) return from_status(kNoKey);
+  } else if (long hr = pool_set_keys(*p, relin_keys, galois_keys, num_key_sets, key_index, batch,
+                                     [&](KeysObj* r, KeysObj* gs, std::vector<PoolKey>* rneed, std::vector<PoolKey>* gneed) {
+                                       PoolKey k;
+                                       if (need_relin) {
+                                         if (!r || !pool_key_of(r, 0, &k)) return false;
+                                         rneed->push_back(k);
+                                       }
+                                       if (need_galois) {  // every element the set holds: the graph's rotations choose among them
+                                         if (gs)
+                                           for (auto& kv : gs->keys)
+                                             if (pool_key_of(gs, kv.first, &k)) gneed->push_back(k);
+                                         if (gneed->empty()) return false;
+                                       }
+                                       return true;
+                                     },
+                                     &all))
+    return hr;
   if (!batch) return HIPBFV_S_OK;
   for (uint64_t i = 0; i < num_inputs; i++)
     if (!input_ptrs[i]) return HIPBFV_E_POINTER;
   for (uint64_t k = 0; k < num_outputs; k++)
     if (!outputs[k]) return HIPBFV_E_POINTER;
   const size_t w = p->ct_words();
+  const std::string not_host = me + " takes host memory (device pointers are not accepted)";
   std::vector<PoolIn> ins(num_inputs);
   std::vector<Span> in_spans;
   for (uint64_t i = 0; i < num_inputs; i++) {
     const bool ct = input_kinds[i] == 0;
     const size_t width = ct ? w : p->n, stride = ct ? w : (size_t)input_strides[i];
     const Span sp{input_ptrs[i], width, stride, (size_t)batch};
-    const HostMem hk = host_kind(input_ptrs[i], sp.words() * sizeof(u64));
-    if (hk == HostMem::kDevice) return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_ProgramRun takes host memory (device pointers are not accepted)");
-    ins[i] = PoolIn{(const u64*)input_ptrs[i], width, stride, hk == HostMem::kPinned};
+    bool pinned;
+    if (!pool_host_operand(input_ptrs[i], sp.words() * sizeof(u64), &pinned)) return fail(HIPBFV_E_INVALIDARG, not_host.c_str());
+    ins[i] = PoolIn{(const u64*)input_ptrs[i], width, stride, pinned};
     in_spans.push_back(sp);
   }
   std::vector<PoolOut> outs(num_outputs);
@@ -4047,16 +4227,18 @@ long hipbfv_Pool_ProgramRun(void* pool, void* program, uint64_t batch, uint64_t 
       ALIAS_OR_RETURN(o, {in});
     for (uint64_t l = 0; l < k; l++)
       ALIAS_OR_RETURN(o, {cts(outputs[l], w, batch)}, false);
-    const HostMem hk = host_kind(outputs[k], o.words() * sizeof(u64));
-    if (hk == HostMem::kDevice) return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_ProgramRun takes host memory (device pointers are not accepted)");
-    outs[k] = PoolOut{(u64*)outputs[k], w, hk == HostMem::kPinned};
+    bool pinned;
+    if (!pool_host_operand(outputs[k], o.words() * sizeof(u64), &pinned)) return fail(HIPBFV_E_INVALIDARG, not_host.c_str());
+    outs[k] = PoolOut{(u64*)outputs[k], w, pinned};
   }
   std::vector<uint32_t> kinds(input_kinds, input_kinds + num_inputs);
-  const u64 chunk = p->chunk_sets();
+  const u64 chunk = p->chunk_sets(), bound = p->key_cache_bytes;
   return pool_dispatch(*p, batch, [&](PoolMember& m, u64 lo, u64 hi) -> long {
-    if (long hr = member_keys(m, rk, gk)) return hr;
+    if (!key_index)
+      if (long hr = member_keys(m, rk, gk, bound)) return hr;
     void* rkh = rk.empty() ? nullptr : &m.relin_view;
     void* gkh = gk.empty() ? nullptr : &m.galois_view;
+    PoolChunkKeys ck;
     std::vector<uint64_t> strides(num_inputs), item_of(std::min<u64>(chunk, hi - lo));
     for (uint64_t i = 0; i < num_inputs; i++) strides[i] = kinds[i] == 0 ? 0 : ins[i].stride ? p->n : 0;
     return member_run(m, ins, outs, lo, hi, chunk, [&](u64, const std::vector<const u64*>& in, const std::vector<u64*>& o, u64 c, u64 first) -> long {
@@ -4065,10 +4247,29 @@ long hipbfv_Pool_ProgramRun(void* pool, void* program, uint64_t batch, uint64_t 
       std::vector<uint64_t*> optrs(o.size());
       for (size_t i = 0; i < in.size(); i++) ptrs[i] = (const uint64_t*)in[i];
       for (size_t k = 0; k < o.size(); k++) optrs[k] = (uint64_t*)o[k];
-      return program_run_impl(prog, &m.eval, c, num_inputs, kinds.data(), ptrs.data(), strides.data(), 1, &rkh, &gkh, nullptr, num_outputs,
-                              optrs.data(), m.comp, item_of.data());
+      if (!key_index)
+        return program_run_impl(prog, &m.eval, c, num_inputs, kinds.data(), ptrs.data(), strides.data(), 1, &rkh, &gkh, nullptr, num_outputs,
+                                optrs.data(), m.comp, item_of.data());
+      if (long hr = member_chunk_keys(m, all, key_index + first, c, bound, &ck)) return hr;
+      return program_run_impl(prog, &m.eval, c, num_inputs, kinds.data(), ptrs.data(), strides.data(), ck.sets.size(), ck.relin.data(),
+                              ck.galois.data(), ck.index.data(), num_outputs, optrs.data(), m.comp, item_of.data());
     });
   });
+}
+
+long hipbfv_Pool_ProgramRun(void* pool, void* program, uint64_t batch, uint64_t num_inputs, const uint32_t* input_kinds,
+                            const uint64_t* const* input_ptrs, const uint64_t* input_strides, void* relin_keys, void* galois_keys,
+                            uint64_t num_outputs, uint64_t* const* outputs) HIPBFV_BEGIN
+  return pool_program_run("hipbfv_Pool_ProgramRun", pool, program, batch, num_inputs, input_kinds, input_ptrs, input_strides, 1, &relin_keys,
+                          &galois_keys, nullptr, num_outputs, outputs);
+HIPBFV_END
+
+long hipbfv_Pool_ProgramRunKeys(void* pool, void* program, uint64_t batch, uint64_t num_inputs, const uint32_t* input_kinds,
+                                const uint64_t* const* input_ptrs, const uint64_t* input_strides, uint64_t num_key_sets, void* const* relin_keys,
+                                void* const* galois_keys, const uint32_t* key_index, uint64_t num_outputs, uint64_t* const* outputs) HIPBFV_BEGIN
+  if (!num_key_sets || !key_index || num_key_sets > 0xFFFFFFFFull) return HIPBFV_E_POINTER;
+  return pool_program_run("hipbfv_Pool_ProgramRunKeys", pool, program, batch, num_inputs, input_kinds, input_ptrs, input_strides, num_key_sets,
+                          relin_keys, galois_keys, key_index, num_outputs, outputs);
 HIPBFV_END
 
 // dist.py:shard_range, the pool's split of a batch over its members: member `member` of `members` gets input sets [begin, end)
@@ -4079,6 +4280,29 @@ long hipbfv_debug_pool_shard(uint64_t batch, uint32_t members, uint32_t member, 
   pool_shard(batch, members, member, &lo, &hi);
   *begin = lo;
   *end = hi;
+  return HIPBFV_S_OK;
+HIPBFV_END
+
+// The key table of one pipeline chunk, host only: chunk `chunk_no` of member `member`'s shard, `chunk` input sets per chunk (never
+// more than the shard, as the pool runs it) -- the pool's own pool_keyplan
+long hipbfv_debug_pool_keyplan(const uint32_t* key_index, uint64_t batch, uint64_t num_key_sets, uint32_t members, uint32_t member, uint64_t chunk,
+                               uint64_t chunk_no, uint32_t* local_sets, uint64_t* local_count, uint32_t* remapped, uint64_t* sets_in_chunk) HIPBFV_BEGIN
+  if (!key_index || !local_sets || !local_count || !remapped || !sets_in_chunk) return HIPBFV_E_POINTER;
+  if (!members || member >= members) return fail(HIPBFV_E_INVALIDARG, "member index out of range");
+  if (!chunk) return fail(HIPBFV_E_INVALIDARG, "a chunk has at least one input set");
+  for (uint64_t i = 0; i < batch; i++)
+    if (key_index[i] >= num_key_sets) return fail(HIPBFV_E_INVALIDARG, "key_index names a key set that was not given");
+  u64 lo, hi;
+  pool_shard(batch, members, member, &lo, &hi);
+  const u64 sets = std::min<u64>(chunk, hi - lo);
+  if (!sets || chunk_no >= (hi - lo + sets - 1) / sets) return fail(HIPBFV_E_INVALIDARG, "chunk number out of range");
+  const u64 first = lo + chunk_no * sets, c = std::min<u64>(sets, hi - first);
+  std::vector<uint32_t> ls, idx;
+  pool_keyplan(key_index + first, c, &ls, &idx);
+  std::copy(ls.begin(), ls.end(), local_sets);
+  std::copy(idx.begin(), idx.end(), remapped);
+  *local_count = ls.size();
+  *sets_in_chunk = c;
   return HIPBFV_S_OK;
 HIPBFV_END
 

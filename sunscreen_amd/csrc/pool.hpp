@@ -4,10 +4,15 @@
 //
 // A pool is a list of members.  A member is one device with its own Context (built from the pool's parameters), Evaluator,
 // three streams (in / compute / out), three pipeline slots of device memory, pinned bounce buffers for pageable host memory,
-// a cache of key copies and ONE worker thread that sets its device once and does all of the member's HIP work: every
+// a cache of key copies (optionally bounded: hipbfv_Pool_SetKeyCacheBytes) and ONE worker thread that sets its device once and does all of the member's HIP work: every
 // thread-local cache it touches (program_plan.cpp's stream tables and TableArenas, the evaluator's watch scope) stays on
 // that device.  A call shards the batch as sunscreen_amd/dist.py:shard_range does, hands every non-empty shard to its
 // member's worker and waits for all of them.  No new kernel: each member runs the library's own launch sequences.
+//
+// Per-client key sets (hipbfv_Pool_*Keys): the calling thread validates every referenced set over the whole batch and lists,
+// per set, the key buffers the call needs (PoolSetKeys).  On the member, every chunk gets its own key table (pool_keyplan: the
+// distinct sets of the chunk, key_index remapped onto them), the member copies just those sets' needed buffers
+// (member_stage_keys) and hands the library's per-key entry points views of its own context (member_chunk_keys).
 #pragma once
 
 namespace {
@@ -65,6 +70,43 @@ struct PoolKey {
   size_t words;
 };
 
+// What a call needs of every key set of the caller's array (empty for a set no input set names), read on the calling thread
+struct PoolSetKeys {
+  std::vector<std::vector<PoolKey>> relin, galois;  // [caller's set]
+};
+
+// A member's copy of one key buffer
+struct PoolKeyCopy {
+  u64* dev;
+  size_t bytes;
+  u64 tick;  // member's key_tick when a chunk last referenced it (least recently used goes first)
+};
+
+// A key handle of the member's context whose buffers the key cache owns: nothing goes to g_buffers when it dies
+struct PoolKeyView : KeysObj {
+  ~PoolKeyView() override {
+    keys.clear();
+    stamps.clear();
+  }
+};
+
+// The key table of one chunk: the distinct sets key_index[0, count) names, ascending in the caller's numbering, and the
+// chunk's key_index remapped onto them (hipbfv_debug_pool_keyplan shows exactly this)
+void pool_keyplan(const uint32_t* key_index, u64 count, std::vector<uint32_t>* sets, std::vector<uint32_t>* remapped) {
+  sets->assign(key_index, key_index + count);
+  std::sort(sets->begin(), sets->end());
+  sets->erase(std::unique(sets->begin(), sets->end()), sets->end());
+  remapped->resize(count);
+  for (u64 i = 0; i < count; i++)
+    (*remapped)[i] = (uint32_t)(std::lower_bound(sets->begin(), sets->end(), key_index[i]) - sets->begin());
+}
+
+// A chunk's keys as the per-key entry points take them: handles of the member's context and the remapped key_index
+struct PoolChunkKeys {
+  std::vector<uint32_t> sets, index;
+  std::vector<void*> relin, galois;  // [local set]; NULL where the call needs no such key of the set
+};
+
 struct PoolMember {
   int device = 0;
   std::shared_ptr<Context> ctx;  // not counted in g_live_contexts: hipbfv_set_device does not see pool members
@@ -81,9 +123,10 @@ struct PoolMember {
   size_t status_cap = 0;         // words
   u32* flags = nullptr;          // pinned: their host copy
   size_t flag_cap = 0;
-  std::map<u64, u64*> key_copy;  // key stamp -> this member's copy (hipMalloc'd here, never from g_buffers)
-  u64 key_copies = 0;
+  std::map<u64, PoolKeyCopy> key_copy;  // key stamp -> this member's copy (hipMalloc'd here, never from g_buffers)
+  u64 key_copies = 0, key_bytes = 0, key_evictions = 0, key_tick = 0;
   KeysObj relin_view, galois_view;  // the call's keys as handles of this member's context (buffers owned by key_copy)
+  std::vector<std::unique_ptr<PoolKeyView>> set_relin, set_galois;  // the current chunk's key table ([local set], reused)
   // the worker thread and its one-job mailbox
   std::thread thread;
   std::mutex mu;
@@ -147,6 +190,7 @@ struct PoolObj : Obj {
   std::vector<u64> primes;
   std::vector<std::unique_ptr<PoolMember>> members;
   u64 chunk = 0;  // 0 = pool_default_chunk
+  u64 key_cache_bytes = 0;  // per member; 0 = no bound
   std::mutex mu;  // one call at a time
   PoolObj() : Obj(kMagicPool) {}
   u64 chunk_sets() const { return chunk ? chunk : pool_default_chunk(n); }
@@ -184,8 +228,11 @@ void member_release(PoolMember& m) {
   if (m.shared) (void)hipFree(m.shared);
   if (m.status) (void)hipFree(m.status);
   if (m.flags) (void)hipHostFree(m.flags);
-  for (auto& kv : m.key_copy) (void)hipFree(kv.second);
+  for (auto& kv : m.key_copy) (void)hipFree(kv.second.dev);
   m.key_copy.clear();
+  m.key_bytes = 0;
+  m.set_relin.clear();
+  m.set_galois.clear();
   m.relin_view.keys.clear();  // the views own nothing: KeysObj's destructor must not hand these to g_buffers
   m.galois_view.keys.clear();
   for (hipStream_t s : {m.in, m.comp, m.out})
@@ -227,48 +274,120 @@ bool grow_pinned(void** p, size_t* cap, size_t bytes) {
   return true;
 }
 
-// The member's copies of the call's keys (a device-to-device copy on the same device, a peer copy across devices), made on
-// first use and kept while the key buffer lives; copies of buffers that no longer live are dropped first.
-long member_keys(PoolMember& m, const std::vector<PoolKey>& relin, const std::vector<PoolKey>& galois) {
+// The member's copies of `need` (a device-to-device copy on the same device, a peer copy across devices), made on first use
+// and kept while the key buffer lives; copies of buffers that no longer live are dropped first.  With a bound (bytes, 0 = none)
+// the least recently used copies that `need` does not name are dropped until `need` fits -- after the compute stream has
+// drained, so no chunk in flight still reads them; a working set above the bound is E_OUTOFMEMORY.  `wait`: the copies have
+// landed on return (otherwise they are ordered before whatever is launched on `s` next).
+long member_stage_keys(PoolMember& m, const std::vector<PoolKey>& need, u64 bound, hipStream_t s, bool wait) {
   for (auto it = m.key_copy.begin(); it != m.key_copy.end();) {
     if (key_stamp_live(it->first)) {
       ++it;
       continue;
     }
-    (void)hipFree(it->second);
+    (void)hipFree(it->second.dev);
+    m.key_bytes -= it->second.bytes;
     it = m.key_copy.erase(it);
   }
-  auto copy_of = [&](const PoolKey& k) -> u64* {
-    auto it = m.key_copy.find(k.stamp);
-    if (it != m.key_copy.end()) return it->second;
+  const u64 now = ++m.key_tick;
+  size_t working = 0, missing = 0;
+  std::vector<const PoolKey*> todo;
+  {
+    std::set<u64> seen;
+    for (const PoolKey& k : need) {
+      if (!seen.insert(k.stamp).second) continue;
+      const size_t bytes = k.words * sizeof(u64);
+      working += bytes;
+      auto it = m.key_copy.find(k.stamp);
+      if (it != m.key_copy.end()) {
+        it->second.tick = now;
+        continue;
+      }
+      missing += bytes;
+      todo.push_back(&k);
+    }
+  }
+  if (bound && working > bound) {
+    char msg[256];
+    snprintf(msg, sizeof(msg),
+             "the keys of one chunk take %llu bytes, the member's key cache is bounded at %llu bytes (lower hipbfv_Pool_SetChunk or raise "
+             "hipbfv_Pool_SetKeyCacheBytes)",
+             (unsigned long long)working, (unsigned long long)bound);
+    return fail(HIPBFV_E_OUTOFMEMORY, msg);
+  }
+  if (bound && m.key_bytes + missing > bound) {
+    if (hipStreamSynchronize(m.comp) != hipSuccess) return from_status(kHipError);
+    while (m.key_bytes + missing > bound) {
+      auto victim = m.key_copy.end();
+      for (auto it = m.key_copy.begin(); it != m.key_copy.end(); ++it)
+        if (it->second.tick != now && (victim == m.key_copy.end() || it->second.tick < victim->second.tick)) victim = it;
+      if (victim == m.key_copy.end()) break;  // cannot happen: everything else is the working set, which fits
+      (void)hipFree(victim->second.dev);
+      m.key_bytes -= victim->second.bytes;
+      m.key_evictions++;
+      m.key_copy.erase(victim);
+    }
+  }
+  for (const PoolKey* k : todo) {
     u64* d = nullptr;
-    const size_t bytes = k.words * sizeof(u64);
+    const size_t bytes = k->words * sizeof(u64);
     if (hipMalloc((void**)&d, bytes) != hipSuccess) {
       (void)hipGetLastError();
-      return nullptr;
+      return from_status(kOutOfMemory);
     }
-    const hipError_t e = k.src_device == m.device ? hipMemcpyAsync(d, k.src, bytes, hipMemcpyDeviceToDevice, m.in)
-                                                  : hipMemcpyPeerAsync(d, m.device, k.src, k.src_device, bytes, m.in);
-    if (e != hipSuccess || hipStreamSynchronize(m.in) != hipSuccess) {
+    const hipError_t e = k->src_device == m.device ? hipMemcpyAsync(d, k->src, bytes, hipMemcpyDeviceToDevice, s)
+                                                   : hipMemcpyPeerAsync(d, m.device, k->src, k->src_device, bytes, s);
+    if (e != hipSuccess || (wait && hipStreamSynchronize(s) != hipSuccess)) {
       (void)hipGetLastError();
       (void)hipFree(d);
-      return nullptr;
+      return from_status(kOutOfMemory);
     }
     m.key_copies++;
-    m.key_copy[k.stamp] = d;
-    return d;
-  };
+    m.key_bytes += bytes;
+    m.key_copy[k->stamp] = PoolKeyCopy{d, bytes, now};
+  }
+  return HIPBFV_S_OK;
+}
+
+// The single-key calls: every buffer of the call's two handles, as the member's relin_view / galois_view
+long member_keys(PoolMember& m, const std::vector<PoolKey>& relin, const std::vector<PoolKey>& galois, u64 bound) {
+  std::vector<PoolKey> need(relin);
+  need.insert(need.end(), galois.begin(), galois.end());
   m.relin_view.keys.clear();
   m.galois_view.keys.clear();
-  for (const PoolKey& k : relin) {
-    u64* d = copy_of(k);
-    if (!d) return from_status(kOutOfMemory);
-    m.relin_view.keys[k.index] = d;
+  if (long hr = member_stage_keys(m, need, bound, m.in, true)) return hr;
+  for (const PoolKey& k : relin) m.relin_view.keys[k.index] = m.key_copy[k.stamp].dev;
+  for (const PoolKey& k : galois) m.galois_view.keys[k.index] = m.key_copy[k.stamp].dev;
+  return HIPBFV_S_OK;
+}
+
+// The key table of the chunk whose input sets name key_index[0, count): the member's copies of what the call needs of the
+// chunk's distinct sets (copied on the compute stream, ahead of the chunk's kernels: no host synchronisation in the pipeline)
+// behind handles of the member's context
+long member_chunk_keys(PoolMember& m, const PoolSetKeys& all, const uint32_t* key_index, u64 count, u64 bound, PoolChunkKeys* ck) {
+  pool_keyplan(key_index, count, &ck->sets, &ck->index);
+  std::vector<PoolKey> need;
+  for (uint32_t set : ck->sets) {
+    need.insert(need.end(), all.relin[set].begin(), all.relin[set].end());
+    need.insert(need.end(), all.galois[set].begin(), all.galois[set].end());
   }
-  for (const PoolKey& k : galois) {
-    u64* d = copy_of(k);
-    if (!d) return from_status(kOutOfMemory);
-    m.galois_view.keys[k.index] = d;
+  if (long hr = member_stage_keys(m, need, bound, m.comp, false)) return hr;
+  const size_t nl = ck->sets.size();
+  while (m.set_relin.size() < nl) {
+    m.set_relin.emplace_back(new PoolKeyView());
+    m.set_galois.emplace_back(new PoolKeyView());
+    m.set_relin.back()->ctx = m.set_galois.back()->ctx = m.ctx;
+  }
+  ck->relin.assign(nl, nullptr);
+  ck->galois.assign(nl, nullptr);
+  for (size_t l = 0; l < nl; l++) {
+    const uint32_t set = ck->sets[l];
+    m.set_relin[l]->keys.clear();
+    m.set_galois[l]->keys.clear();
+    for (const PoolKey& k : all.relin[set]) m.set_relin[l]->keys[k.index] = m.key_copy[k.stamp].dev;
+    for (const PoolKey& k : all.galois[set]) m.set_galois[l]->keys[k.index] = m.key_copy[k.stamp].dev;
+    if (!all.relin[set].empty()) ck->relin[l] = m.set_relin[l].get();
+    if (!all.galois[set].empty()) ck->galois[l] = m.set_galois[l].get();
   }
   return HIPBFV_S_OK;
 }
@@ -430,11 +549,26 @@ long pool_dispatch(PoolObj& p, u64 batch, const std::function<long(PoolMember&, 
   return first;
 }
 
+// A key handle whose context has the pool's parameters (nullptr for NULL, a foreign object or other parameters)
+KeysObj* pool_keyset(const PoolObj& p, void* handle) {
+  KeysObj* k = as<KeysObj>(handle, kMagicKeys);
+  return k && k->ctx && p.same_params(*k->ctx) ? k : nullptr;
+}
+
+// Key `index` of such a handle; false if it does not hold it
+bool pool_key_of(KeysObj* k, u32 index, PoolKey* out) {
+  auto kv = k->keys.find(index);
+  auto st = k->stamps.find(index);
+  if (kv == k->keys.end() || st == k->stamps.end()) return false;
+  *out = PoolKey{index, st->second, kv->second, k->ctx->device(), k->ctx->key_words()};
+  return true;
+}
+
 // The key buffers of a handle whose context has the pool's parameters (nothing for NULL, a foreign object or other parameters)
 std::vector<PoolKey> pool_keys_of(const PoolObj& p, void* handle, bool relin_only) {
   std::vector<PoolKey> out;
-  KeysObj* k = as<KeysObj>(handle, kMagicKeys);
-  if (!k || !k->ctx || !p.same_params(*k->ctx)) return out;
+  KeysObj* k = pool_keyset(p, handle);
+  if (!k) return out;
   for (auto& kv : k->keys) {
     if (relin_only && kv.first != 0) continue;
     auto st = k->stamps.find(kv.first);
@@ -442,6 +576,80 @@ std::vector<PoolKey> pool_keys_of(const PoolObj& p, void* handle, bool relin_onl
     out.push_back(PoolKey{kv.first, st->second, kv.second, k->ctx->device(), k->ctx->key_words()});
   }
   return out;
+}
+
+// ---- per-client key sets: on the calling thread ----
+// What the call needs of one referenced set (its relinearisation and Galois handles, nullptr where the caller gave none):
+// appends the buffers, false if the set lacks one
+using PoolNeeds = std::function<bool(KeysObj*, KeysObj*, std::vector<PoolKey>*, std::vector<PoolKey>*)>;
+
+// Pre-flight over the whole batch, before any member copies or launches anything: key_index in range, every referenced handle a
+// key object of the pool's parameters holding what `needs` asks of it -- E_INVALIDARG naming the set's index in the caller's array
+long pool_set_keys(const PoolObj& p, void* const* relin_sets, void* const* galois_sets, u64 num_sets, const uint32_t* key_index, u64 count,
+                   const PoolNeeds& needs, PoolSetKeys* all) {
+  for (u64 i = 0; i < count; i++)
+    if (key_index[i] >= num_sets) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "key_index[%llu] names key set %u, but only %llu key sets were given", (unsigned long long)i, key_index[i],
+               (unsigned long long)num_sets);
+      return fail(HIPBFV_E_INVALIDARG, msg);
+    }
+  all->relin.assign(num_sets, {});
+  all->galois.assign(num_sets, {});
+  const std::vector<char> used = referenced_sets(key_index, count, num_sets);
+  for (u64 k = 0; k < num_sets; k++) {
+    if (!used[k]) continue;
+    KeysObj* ko[2] = {nullptr, nullptr};
+    int a = 0;
+    for (void* const* arr : {relin_sets, galois_sets}) {
+      void* h = arr ? arr[k] : nullptr;
+      if (h && !(ko[a] = pool_keyset(p, h))) return no_key_in_set(k);  // not a key object, or of other parameters
+      a++;
+    }
+    if (!needs(ko[0], ko[1], &all->relin[k], &all->galois[k])) return no_key_in_set(k);
+  }
+  return HIPBFV_S_OK;
+}
+
+// ---- the transparent-result watch of a call: `words` device status words, all read back after the last chunk (no small copy on
+// the compute stream queues behind the out stream's large ones) ----
+long member_watch_begin(PoolMember& m, u64 words) {
+  if (m.status_cap < words) {
+    if (m.status) (void)hipFree(m.status);
+    m.status = nullptr;
+    m.status_cap = 0;
+    if (hipMalloc((void**)&m.status, words * sizeof(u32)) != hipSuccess) {
+      (void)hipGetLastError();
+      m.status = nullptr;
+      return from_status(kOutOfMemory);
+    }
+    m.status_cap = words;
+  }
+  size_t cap = m.flag_cap;
+  if (!grow_pinned((void**)&m.flags, &cap, words * sizeof(u32))) return from_status(kOutOfMemory);
+  m.flag_cap = cap;
+  if (hipMemsetAsync(m.status, 0xFF, words * sizeof(u32), m.comp) != hipSuccess) return from_status(kHipError);
+  return HIPBFV_S_OK;
+}
+
+// m.flags[0, words) = the status words (0xFFFFFFFF: nothing transparent)
+long member_watch_read(PoolMember& m, u64 words) {
+  if (hipMemcpyAsync(m.flags, m.status, words * sizeof(u32), hipMemcpyDeviceToHost, m.comp) != hipSuccess || hipStreamSynchronize(m.comp) != hipSuccess)
+    return from_status(kHipError);
+  return HIPBFV_S_OK;
+}
+
+long pool_transparent(u64 set) {
+  char msg[128];
+  snprintf(msg, sizeof(msg), "result ciphertext is transparent (input set %llu of the batch)", (unsigned long long)set);
+  return fail(HIPBFV_COR_E_INVALIDOPERATION, msg);
+}
+
+// A host operand of a pool call: pinned or pageable; false for device memory
+bool pool_host_operand(const void* p, size_t bytes, bool* pinned) {
+  const HostMem k = host_kind(p, bytes);
+  *pinned = k == HostMem::kPinned;
+  return k != HostMem::kDevice;
 }
 
 void pool_destroy(PoolObj* p) {

@@ -70,6 +70,10 @@ class DevicePool:
         """Input sets per pipeline chunk per member; 0 = the library's choice."""
         _check(_lib.load().hipbfv_Pool_SetChunk(self._h, int(sets_per_chunk)))
 
+    def set_key_cache_bytes(self, nbytes: int) -> None:
+        """Bound, per member, on the bytes of key copies it keeps (least recently used copies go first); 0 = no bound."""
+        _check(_lib.load().hipbfv_Pool_SetKeyCacheBytes(self._h, int(nbytes)))
+
     def describe(self) -> str:
         need = C.c_uint64()
         _check(_lib.load().hipbfv_Pool_Describe(self._h, None, 0, C.byref(need)))
@@ -95,10 +99,58 @@ class DevicePool:
         _check(_lib.load().hipbfv_Pool_MultiplyRelin(self._h, pa, pb, relin_keys.get_handle(), po, batch))
         return _as_u64(out)
 
-    def run(self, program, inputs, relin_keys: RelinearizationKeys | None = None, galois_keys: GaloisKeys | None = None,
-            outputs=None) -> list[np.ndarray]:
+    # ---- per-client key sets: input set i uses key_sets[key_index[i]]; a member copies only what its own chunks name ----
+    @staticmethod
+    def _key_sets(key_sets, key_index, count: int):
+        # a None entry is a NULL handle: allowed for a set no input set names
+        handles = (C.c_void_p * len(key_sets))(*[k.get_handle() if k is not None else None for k in key_sets])
+        idx = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint32))
+        assert idx.shape == (count,), (idx.shape, count)
+        return handles, len(key_sets), idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx
+
+    def _one_ct(self, ct):
+        ptr, _, shape, keep = _host(ct)
+        assert len(shape) == 4 and tuple(shape[1:]) == (2, self.K, self.n), shape
+        return ptr, shape[0], keep
+
+    def multiply_relin_keys(self, a, b, key_sets: Sequence[RelinearizationKeys | None], key_index, out=None) -> np.ndarray:
+        """relinearize(a * b) with key_sets[key_index[i]] for pair i (key_index: `batch` host integers, in any order)."""
+        pa, batch, ka = self._one_ct(a)
+        pb, batch_b, kb = self._one_ct(b)
+        assert batch == batch_b, (batch, batch_b)
+        out, po = self._out(out, batch)
+        hs, n, ip, _keep = self._key_sets(key_sets, key_index, batch)
+        _check(_lib.load().hipbfv_Pool_MultiplyRelinKeys(self._h, pa, pb, hs, n, ip, po, batch))
+        return _as_u64(out)
+
+    def rotate_rows_keys(self, ct, steps: int, key_sets: Sequence[GaloisKeys | None], key_index, out=None) -> np.ndarray:
+        """Every ciphertext's rows rotated by `steps` with its own client's Galois keys: a set that holds the key of `steps` uses
+        it, a set that holds only power-of-two keys takes the NAF chain, both in one call.  `out` may be `ct` itself."""
+        pc, batch, kc = self._one_ct(ct)
+        out, po = self._out(out, batch)
+        hs, n, ip, _keep = self._key_sets(key_sets, key_index, batch)
+        _check(_lib.load().hipbfv_Pool_RotateRowsKeys(self._h, pc, int(steps), hs, n, ip, po, batch))
+        return _as_u64(out)
+
+    def rotate_columns_keys(self, ct, key_sets: Sequence[GaloisKeys | None], key_index, out=None) -> np.ndarray:
+        pc, batch, kc = self._one_ct(ct)
+        out, po = self._out(out, batch)
+        hs, n, ip, _keep = self._key_sets(key_sets, key_index, batch)
+        _check(_lib.load().hipbfv_Pool_RotateColumnsKeys(self._h, pc, hs, n, ip, po, batch))
+        return _as_u64(out)
+
+    def rotate_rows(self, ct, steps: int, galois_keys: GaloisKeys, out=None) -> np.ndarray:
+        """A rotation batch with one shared key set (one key set, an all-zero key_index)."""
+        return self.rotate_rows_keys(ct, steps, [galois_keys], np.zeros(_host(ct)[2][0], dtype=np.uint32), out)
+
+    def rotate_columns(self, ct, galois_keys: GaloisKeys, out=None) -> np.ndarray:
+        return self.rotate_columns_keys(ct, [galois_keys], np.zeros(_host(ct)[2][0], dtype=np.uint32), out)
+
+    def run(self, program, inputs, relin_keys=None, galois_keys=None, outputs=None, key_index=None) -> list[np.ndarray]:
         """hipbfv_Program_Run's contract over host memory: inputs[i] is a ciphertext batch u64[batch][2][K][N], per-set
-        plaintexts u64[batch][N] or one shared plaintext u64[N]; returns one host array u64[batch][2][K][N] per output."""
+        plaintexts u64[batch][N] or one shared plaintext u64[N]; returns one host array u64[batch][2][K][N] per output.
+        key_index (optional, `batch` host integers): one key set per client -- relin_keys / galois_keys are then SEQUENCES of key
+        objects (an entry may be None) and input set i runs with relin_keys[key_index[i]], galois_keys[key_index[i]]."""
         hosts = [_host(x) for x in inputs]
         batch = None
         for _, _, shape, _ in hosts:
@@ -124,6 +176,16 @@ class DevicePool:
         assert len(outputs) == n_out
         outs = [self._out(o, batch) for o in outputs]
         optrs = (C.c_void_p * n_out)(*[p for _, p in outs])
+        if key_index is not None:
+            nsets = max(len(relin_keys) if relin_keys is not None else 0, len(galois_keys) if galois_keys is not None else 0)
+            assert nsets > 0, "key_index needs sequences of key sets"
+            rks = list(relin_keys) if relin_keys is not None else [None] * nsets
+            gks = list(galois_keys) if galois_keys is not None else [None] * nsets
+            assert len(rks) == len(gks) == nsets, (len(rks), len(gks))
+            rh, _, ip, _keep = self._key_sets(rks, key_index, batch)
+            gh, _, _, _ = self._key_sets(gks, key_index, batch)
+            _check(_lib.load().hipbfv_Pool_ProgramRunKeys(self._h, program._h, batch, n_in, kinds, ptrs, strides, nsets, rh, gh, ip, n_out, optrs))
+            return [_as_u64(o) for o, _ in outs]
         rk = relin_keys.get_handle() if relin_keys is not None else None
         gk = galois_keys.get_handle() if galois_keys is not None else None
         _check(_lib.load().hipbfv_Pool_ProgramRun(self._h, program._h, batch, n_in, kinds, ptrs, strides, rk, gk, n_out, optrs))
@@ -135,3 +197,15 @@ def shard(batch: int, members: int, member: int) -> tuple[int, int]:
     lo, hi = C.c_uint64(), C.c_uint64()
     _check(_lib.load().hipbfv_debug_pool_shard(batch, members, member, C.byref(lo), C.byref(hi)))
     return lo.value, hi.value
+
+
+def keyplan(key_index, num_key_sets: int, members: int, member: int, chunk: int, chunk_no: int) -> tuple[list[int], list[int]]:
+    """The library's key table of one pipeline chunk (host only): the distinct key sets that chunk `chunk_no` of member
+    `member`'s shard names, ascending, and the chunk's key_index remapped onto them."""
+    idx = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint32))
+    local = (C.c_uint32 * max(1, num_key_sets))()
+    remapped = (C.c_uint32 * max(1, chunk))()
+    nl, nc = C.c_uint64(), C.c_uint64()
+    _check(_lib.load().hipbfv_debug_pool_keyplan(idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size, num_key_sets, members, member, chunk,
+                                                 chunk_no, local, C.byref(nl), remapped, C.byref(nc)))
+    return list(local[: nl.value]), list(remapped[: nc.value])

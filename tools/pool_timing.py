@@ -8,6 +8,11 @@ Legs (every rate counts the whole synchronous call: host-to-device copies, compu
   chi_sq      -- hipbfv_Pool_ProgramRun of sunscreen_amd/workloads.py:chi_sq_optimized at n = 16384 from pageable host memory,
                  members [0] and [0, 0] (what a second member on the same link does), beside the resident rate of
                  FheProgram.run on the same batch (inputs and outputs in HBM, for scale)
+  per_key     -- hipbfv_Pool_MultiplyRelinKeys at n = 8192 (batch 2048, chunks of 256, pinned, one member): (a) the single-key
+                 hipbfv_Pool_MultiplyRelin and (b) one key set per 64 input sets with warm key copies, the two arms alternating
+                 in one process, best of 5 whole calls each; (c) the first, cold call of (b), key copies included; (d) one key
+                 set per input set (2048 relinearisation keys).  Gate: (b) >= 0.90 x (a) of the same run; (c) and (d) are
+                 reported without one.
   bits_equal  -- whether every pool result above equals the single-device call word for word
 Only the library is used (its own key generator; operands are uniform canonical residues: valid ciphertext bit patterns).
 Prints one JSON object."""
@@ -80,6 +85,65 @@ def mulrelin(n, batch, chunk):
     }
 
 
+def per_key(n, batch, chunk, per_set):
+    import torch
+
+    from sunscreen_amd import DevicePool
+    from sunscreen_amd.batch import BatchEvaluator, to_device, to_host
+    from sunscreen_amd.seal import KeyGenerator
+
+    ctx, primes, rk = _context(n)
+    K = ctx.K
+    a = _residues(n, primes, K, batch, 1)
+    b = _residues(n, primes, K, batch, 2)
+    shape = (batch, 2, K, n)
+    pa, pb, po = (torch.empty(shape, dtype=torch.int64, pin_memory=True) for _ in range(3))
+    pa.numpy()[:] = a.view(np.int64)
+    pb.numpy()[:] = b.view(np.int64)
+    got = po.numpy().view(np.uint64)
+    ev = BatchEvaluator(ctx)
+    da, db = to_device(a), to_device(b)
+
+    def keys(count):
+        return [KeyGenerator(ctx, seed=100 + i).create_relinearization_keys() for i in range(count)]
+
+    res = {"n": n, "batch": batch, "chunk": chunk, "K": K, "sets_per_key": per_set, "gate": 0.90}
+    sets = keys(batch // per_set)
+    index = (np.arange(batch) // per_set).astype(np.uint32)
+    ref = to_host(ev.multiply_relin_keys(da, db, sets, index))
+    pool = DevicePool(ctx, [0])
+    pool.set_chunk(chunk)
+    t0 = time.perf_counter()
+    pool.multiply_relin_keys(pa, pb, sets, index, out=po)  # (c): slot buffers, key copies and all
+    t_cold = time.perf_counter() - t0
+    eq = bool((got == ref).all())
+    pool.multiply_relin(pa, pb, rk, out=po)  # the single-key arm's warm-up
+    t_single = t_keys = float("inf")
+    for _ in range(REPS):  # the arms alternate: both see the same clocks and the same neighbours on the link
+        t0 = time.perf_counter()
+        pool.multiply_relin(pa, pb, rk, out=po)
+        t_single = min(t_single, time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        pool.multiply_relin_keys(pa, pb, sets, index, out=po)
+        t_keys = min(t_keys, time.perf_counter() - t0)
+    eq = eq and bool((got == ref).all())
+    # (d): one key set per input set, in the same pool
+    sets_each = keys(batch)
+    index = np.arange(batch, dtype=np.uint32)
+    ref = to_host(ev.multiply_relin_keys(da, db, sets_each, index))
+    t_each = _best(lambda: pool.multiply_relin_keys(pa, pb, sets_each, index, out=po))
+    eq = eq and bool((got == ref).all())
+    pool.close()
+    res.update({
+        "single_key_ops_per_s": round(batch / t_single, 1), "per_key_warm_ops_per_s": round(batch / t_keys, 1),
+        "per_key_cold_ops_per_s": round(batch / t_cold, 1), "key_per_set_ops_per_s": round(batch / t_each, 1),
+        "single_key_ms": round(t_single * 1e3, 2), "per_key_warm_ms": round(t_keys * 1e3, 2), "per_key_cold_ms": round(t_cold * 1e3, 2),
+        "key_per_set_ms": round(t_each * 1e3, 2), "warm_over_single": round(t_single / t_keys, 4),
+        "gate_met": bool(t_single / t_keys >= 0.90), "bits_equal": eq,
+    })
+    return res
+
+
 def chi_sq(n, batch, chunk):
     import torch
 
@@ -115,21 +179,44 @@ def chi_sq(n, batch, chunk):
     return res
 
 
+LEGS = ("mulrelin", "per_key", "chi_sq")
+
+
 def main():
+    only = sys.argv[1:]  # leg names; none = every leg, each in a process of its own
+    if not only:
+        # A pool made after another pool of the same process has been destroyed ran the same call about 25 % slower (r07: 37 K
+        # against 49.6 K mul+relin/s; cause not found), so every leg is measured as a server would run it: in a fresh process.
+        import subprocess
+
+        out = {"tool": "pool_timing", "reps": REPS}
+        for leg in LEGS:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), leg], capture_output=True, text=True, timeout=900)
+            if r.returncode != 0:
+                sys.stderr.write(r.stderr)
+                sys.exit(f"leg {leg} failed with status {r.returncode}")
+            part = json.loads(r.stdout.strip().splitlines()[-1])
+            out.setdefault("device", part["device"])
+            out[leg] = part[leg]
+        out["bits_equal"] = all(r["bits_equal"] for r in out["mulrelin"] + [out["per_key"], out["chi_sq"]])
+        print(json.dumps(out))
+        return
+
     import torch
 
     from sunscreen_amd import _lib
 
     _lib.load().hipbfv_set_device(0)
     torch.cuda.set_device(0)
-    out = {
-        "tool": "pool_timing",
-        "device": torch.cuda.get_device_name(0),
-        "reps": REPS,
-        "mulrelin": [mulrelin(8192, 2048, 256), mulrelin(16384, 1024, 128)],
-        "chi_sq": chi_sq(16384, 1024, 128),
-    }
-    out["bits_equal"] = all(r["bits_equal"] for r in out["mulrelin"]) and out["chi_sq"]["bits_equal"]
+    out = {"tool": "pool_timing", "device": torch.cuda.get_device_name(0), "reps": REPS}
+    if "mulrelin" in only:
+        out["mulrelin"] = [mulrelin(8192, 2048, 256), mulrelin(16384, 1024, 128)]
+    if "per_key" in only:
+        out["per_key"] = per_key(8192, 2048, 256, 64)
+    if "chi_sq" in only:
+        out["chi_sq"] = chi_sq(16384, 1024, 128)
+    legs = out.get("mulrelin", []) + [out[k] for k in ("per_key", "chi_sq") if k in out]
+    out["bits_equal"] = all(r["bits_equal"] for r in legs)
     print(json.dumps(out))
 
 
