@@ -305,7 +305,7 @@ uint32_t ora_galois_elt_from_step(const ora_ctx *c, int step)
 {
     const uint32_t n = c->n, m = 2 * n;
     if (step == 0) return m - 1;
-    uint32_t pos = (uint32_t)(step < 0 ? -step : step);
+    uint32_t pos = step < 0 ? 0u - (uint32_t)step : (uint32_t)step; /* (INT_MIN: -step would overflow) */
     if (pos >= (n >> 1)) return 0;
     uint32_t s = step < 0 ? (n >> 1) - pos : pos;
     uint64_t e = 1;

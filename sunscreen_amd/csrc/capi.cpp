@@ -1648,6 +1648,8 @@ static long rotate_common(void* h, void* a, bool columns, int steps, void* keys,
   if (x->size != 2) return fail(HIPBFV_E_INVALIDARG, "encrypted size must be 2");
   if (k->ctx && !in_chain(k->ctx, e->ctx.get())) return fail(HIPBFV_E_INVALIDARG, "galois_keys is not valid for encryption parameters");
   if (columns) return galois_handle(e, x, 2 * e->ctx->n() - 1, k, d);
+  // a refused step leaves the destination as it was: checked before the destination takes the copy
+  if (steps && !e->ev->galois_elt_from_step(steps)) return fail(HIPBFV_E_INVALIDARG, "step count too large");
   if (d != x) {  // work on a copy in the destination so that the NAF chain can run in place
     u64* buf = g_buffers.get(x->words);
     if (!buf) return from_status(kOutOfMemory);
