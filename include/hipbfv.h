@@ -318,6 +318,22 @@ long hipbfv_batch_rotate_rows(void *evaluator, const uint64_t *ct2, int steps, v
                               uint64_t count, void *stream);
 long hipbfv_batch_rotate_columns(void *evaluator, const uint64_t *ct2, void *galois_keys, uint64_t *out2,
                                  uint64_t count, void *stream);
+/* Mixed-step rotation batches: item i by its OWN Galois element / step (a server that batches many clients' rotations, the
+ * diagonals of a matrix-vector product, the baby and giant steps of a sum), one key set for the call.  galois_elts / steps are
+ * HOST arrays of `count` entries, read before the call returns.
+ *  - apply_galois_items: every element odd and below 2 N; element 1 copies the item; every other element's key must be held.
+ *  - rotate_rows_items: item i has exactly the bits of hipbfv_batch_rotate_rows called with steps[i] on that item alone, so
+ *    every distinct step decides as SEAL's rotate_internal does: step 0 copies, a step whose element's key is held rotates
+ *    through it, any other step runs its NAF chain of power-of-two keys (together with the other items of that step).
+ * All the items that rotate through a key of their own share ONE key-switch launch sequence: the kernels take the automorphism
+ * and the key per item, and walk the items in element order, so that an element's key rows are shared in one XCD's L2.  Items
+ * need not be grouped by step.  A refused element or step (|step| >= N/2) and a missing key (a chain's included) fail the
+ * whole call with HIPBFV_E_INVALIDARG before anything is launched or written; hipbfv_last_error names the first such item
+ * ("item <index>: ...").  Aliasing as above: out2 may be exactly ct2, any other overlap is refused. */
+long hipbfv_batch_apply_galois_items(void *evaluator, const uint64_t *ct2, const uint32_t *galois_elts, void *galois_keys,
+                                     uint64_t *out2, uint64_t count, void *stream);
+long hipbfv_batch_rotate_rows_items(void *evaluator, const uint64_t *ct2, const int32_t *steps, void *galois_keys,
+                                    uint64_t *out2, uint64_t count, void *stream);
 /* Per-key batches (multi-tenant serving).  The reference hands the keys over with every call
  * (sunscreen_runtime/src/run.rs:100-105: `relin_keys: &Option<&RelinearizationKeys>`, `galois_keys: &Option<&GaloisKeys>`;
  * runtime.rs:310-327), so a server that batches the calls of many clients holds one key set per client.  These are the
@@ -568,6 +584,12 @@ long hipbfv_debug_pool_shard(uint64_t batch, uint32_t members, uint32_t member, 
 long hipbfv_debug_pool_keyplan(const uint32_t *key_index, uint64_t batch, uint64_t num_key_sets, uint32_t members, uint32_t member,
                                uint64_t chunk, uint64_t chunk_no, uint32_t *local_sets, uint64_t *local_count,
                                uint32_t *remapped, uint64_t *sets_in_chunk);
+/* Host only: what hipbfv_batch_rotate_rows_items does with `steps` at degree n over a key set that holds exactly the keys of the
+ * elements present_elts -- kind[i]: 0 the item is copied, 1 it goes into the mixed launch (group[i] = its Galois element), 2 it
+ * joins NAF chain group group[i] (groups numbered in the order their step first appears; *chain_groups of them).  Fails as the
+ * call would (a refused step, a missing key; the message names the item). */
+long hipbfv_debug_rotate_items_plan(uint64_t n, const int32_t *steps, uint64_t count, const uint32_t *present_elts,
+                                    uint64_t num_present, int32_t *kind, uint32_t *group, uint64_t *chain_groups);
 
 /* Per-kernel timing (HIP events recorded on the launch stream, around every kernel launch):
  * total milliseconds, number of launches and work units (residue polynomials for the NTT kernels,

@@ -638,6 +638,14 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
   void rotate_columns_inplace(Ciphertext& a, const GaloisKeys& gk) const {
     check(Evaluator_RotateColumns(h_, a.get_handle(), gk.get_handle(), a.get_handle(), nullptr));
   }
+  // Mixed-step rotation batches on device buffers u64[count][2][K][N] (hipbfv.h): item i by its own Galois element / step in one
+  // key-switch pass; `out` may be `ct` itself.  Not part of the reference crate's surface.
+  void apply_galois_items(const uint64_t* ct, const std::vector<uint32_t>& galois_elts, const GaloisKeys& gk, uint64_t* out, void* stream = nullptr) const {
+    check(hipbfv_batch_apply_galois_items(h_, ct, galois_elts.data(), gk.get_handle(), out, galois_elts.size(), stream));
+  }
+  void rotate_rows_items(const uint64_t* ct, const std::vector<int32_t>& steps, const GaloisKeys& gk, uint64_t* out, void* stream = nullptr) const {
+    check(hipbfv_batch_rotate_rows_items(h_, ct, steps.data(), gk.get_handle(), out, steps.size(), stream));
+  }
 };
 
 // The device pool (hipbfv.h, "Device pool"): host-resident batches u64[count][2][K][N] sharded over several GPUs, every input

@@ -78,6 +78,23 @@ impl<'e> BatchEvaluator<'e> {
     pub fn rotate_columns(&self, a: DeviceBatch, gk: &GaloisKeys, out: DeviceBatch) -> Result<()> {
         check(unsafe { bindgen::hipbfv_batch_rotate_columns(self.h(), a.ptr, gk.get_handle(), out.ptr, a.count, self.stream) })
     }
+    // ---- mixed-step rotation batches: item i by its own element / step in one key-switch pass (include/hipbfv.h) ----
+    fn per_item_ok(len: usize, count: u64, what: &str) -> Result<()> {
+        if len as u64 != count {
+            return Err(crate::Error::InvalidArgument(format!("{} {} for {} items", len, what, count)));
+        }
+        Ok(())
+    }
+    pub fn apply_galois_items(&self, a: DeviceBatch, galois_elts: &[u32], gk: &GaloisKeys, out: DeviceBatch) -> Result<()> {
+        same_count(&a, &out)?;
+        Self::per_item_ok(galois_elts.len(), a.count, "Galois elements")?;
+        check(unsafe { bindgen::hipbfv_batch_apply_galois_items(self.h(), a.ptr, galois_elts.as_ptr(), gk.get_handle(), out.ptr, a.count, self.stream) })
+    }
+    pub fn rotate_rows_items(&self, a: DeviceBatch, steps: &[i32], gk: &GaloisKeys, out: DeviceBatch) -> Result<()> {
+        same_count(&a, &out)?;
+        Self::per_item_ok(steps.len(), a.count, "steps")?;
+        check(unsafe { bindgen::hipbfv_batch_rotate_rows_items(self.h(), a.ptr, steps.as_ptr(), gk.get_handle(), out.ptr, a.count, self.stream) })
+    }
     // ---- per-key batches ----
     // The reference hands the keys over with every call (`sunscreen_runtime/src/run.rs:100-105`: `relin_keys:
     // &Option<&RelinearizationKeys>`, `galois_keys: &Option<&GaloisKeys>`; `runtime.rs:310-327`): a server that batches the

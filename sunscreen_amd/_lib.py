@@ -117,6 +117,8 @@ _SIGNATURES = {
     "hipbfv_batch_multiply_relin": [vp, vp, vp, vp, vp, u64, vp],
     "hipbfv_batch_apply_galois": [vp, vp, C.c_uint32, vp, vp, u64, vp],
     "hipbfv_batch_rotate_rows": [vp, vp, C.c_int, vp, vp, u64, vp],
+    "hipbfv_batch_apply_galois_items": [vp, vp, C.POINTER(C.c_uint32), vp, vp, u64, vp],
+    "hipbfv_batch_rotate_rows_items": [vp, vp, C.POINTER(C.c_int32), vp, vp, u64, vp],
     "hipbfv_batch_rotate_columns": [vp, vp, vp, vp, u64, vp],
     "hipbfv_batch_relinearize_keys": [vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64, vp],
     "hipbfv_batch_multiply_relin_keys": [vp, vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64, vp],
@@ -212,6 +214,7 @@ _SIGNATURES = {
     "hipbfv_debug_pool_shard": [u64, C.c_uint32, C.c_uint32, u64p, u64p],
     "hipbfv_debug_pool_keyplan": [C.POINTER(C.c_uint32), u64, u64, C.c_uint32, C.c_uint32, u64, u64, C.POINTER(C.c_uint32), u64p,
                                   C.POINTER(C.c_uint32), u64p],
+    "hipbfv_debug_rotate_items_plan": [u64, C.POINTER(C.c_int32), u64, C.POINTER(C.c_uint32), u64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), u64p],
     "hipbfv_profile_enable": [vp, C.c_bool],
     "hipbfv_profile_reset": [vp],
     "hipbfv_profile_kernel_count": [C.POINTER(C.c_uint32)],

@@ -133,6 +133,28 @@ class BatchEvaluator:
         _check(_lib.load().hipbfv_batch_rotate_columns(self._h, _ptr(ct), gk.get_handle(), _ptr(out), ct.shape[0], _stream()))
         return out
 
+    # ---- mixed-step rotation batches: item i by its own element / step, one key-switch pass (include/hipbfv.h) ----
+    def apply_galois_items(self, ct: torch.Tensor, galois_elts, gk: GaloisKeys, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Item i by galois_elts[i] (`count` host integers, odd and below 2 N; 1 copies the item)."""
+        self._shape_ok(ct, 2)
+        out = out if out is not None else self._new(ct.shape[0], 2, ct)
+        elts = np.ascontiguousarray(np.asarray(galois_elts, dtype=np.uint32))
+        assert elts.shape == (ct.shape[0],), (elts.shape, ct.shape[0])
+        _check(_lib.load().hipbfv_batch_apply_galois_items(self._h, _ptr(ct), elts.ctypes.data_as(C.POINTER(C.c_uint32)), gk.get_handle(), _ptr(out),
+                                                           ct.shape[0], _stream()))
+        return out
+
+    def rotate_rows_items(self, ct: torch.Tensor, steps, gk: GaloisKeys, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Item i rotated by steps[i] (`count` host integers): the bits of rotate_rows(ct[i:i+1], steps[i], gk).  The steps whose
+        own key gk holds share one launch sequence; step 0 copies; the others run their NAF chains, grouped by step."""
+        self._shape_ok(ct, 2)
+        out = out if out is not None else self._new(ct.shape[0], 2, ct)
+        st = np.ascontiguousarray(np.asarray(steps, dtype=np.int32))
+        assert st.shape == (ct.shape[0],), (st.shape, ct.shape[0])
+        _check(_lib.load().hipbfv_batch_rotate_rows_items(self._h, _ptr(ct), st.ctypes.data_as(C.POINTER(C.c_int32)), gk.get_handle(), _ptr(out),
+                                                          ct.shape[0], _stream()))
+        return out
+
     # ---- per-key batches (multi-tenant: the reference passes the keys per call, sunscreen_runtime/src/run.rs:100-105) ----
     @staticmethod
     def _key_sets(key_sets, key_index, count: int):
@@ -323,3 +345,17 @@ class BatchEvaluator:
         assert data.dim() == 2 and data.shape[1] == self.n
         _check(_lib.load().hipbfv_batch_ntt(self._h, _ptr(data), data.shape[0], nprimes, inverse, _stream()))
         return data
+
+
+def rotate_items_plan(n: int, steps, present_elts) -> tuple[list[int], list[int], int]:
+    """The library's plan for rotate_rows_items (host only): per item its kind (0 copied, 1 in the mixed launch, 2 in a NAF chain
+    group) and its group (kind 1: the Galois element, kind 2: the chain group), and the number of chain groups -- at degree n,
+    over a key set that holds exactly the keys of present_elts."""
+    st = np.ascontiguousarray(np.asarray(steps, dtype=np.int32))
+    pe = np.ascontiguousarray(np.asarray(present_elts, dtype=np.uint32))
+    kind = (C.c_int32 * max(1, st.size))()
+    group = (C.c_uint32 * max(1, st.size))()
+    ng = C.c_uint64()
+    _check(_lib.load().hipbfv_debug_rotate_items_plan(n, st.ctypes.data_as(C.POINTER(C.c_int32)), st.size, pe.ctypes.data_as(C.POINTER(C.c_uint32)), pe.size,
+                                                      kind, group, C.byref(ng)))
+    return list(kind[: st.size]), list(group[: st.size]), ng.value

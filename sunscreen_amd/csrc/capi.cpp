@@ -27,6 +27,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <functional>
 #include <thread>
 #include <vector>
 
@@ -2008,6 +2009,126 @@ long hipbfv_batch_rotate_columns_keys(void* h, const uint64_t* ct2, void* const*
   EVAL_OR_RETURN(h);
   if (!e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
   return hipbfv_batch_apply_galois_keys(h, ct2, 2 * e->ctx->n() - 1, key_sets, num_sets, key_index, out2, count, stream);
+HIPBFV_END
+
+// ---- mixed-step rotation batches: item i by its own step / element (include/hipbfv.h) ----
+// What hipbfv_batch_rotate_rows_items does with every item, decided once per distinct step as hipbfv_batch_rotate_rows decides
+// for a whole batch (SEAL's rotate_internal): step 0 copies; a step whose element's key is held rotates through it -- those
+// items share ONE launch sequence (Evaluator::apply_galois_items); any other step runs its NAF chain, together with the items
+// of the same step.  Host only (hipbfv_debug_rotate_items_plan shows it).
+struct RotateItemsPlan {
+  enum Kind : int32_t { kCopy = 0, kDirect = 1, kChain = 2 };
+  std::vector<int32_t> kind;               // per item
+  std::vector<uint32_t> group;             // per item: kDirect: the Galois element, kChain: the chain group, kCopy: 0
+  std::vector<int> chain_step;             // per chain group (groups are numbered in the order their step first appears)
+  std::vector<std::vector<uint64_t>> chain_items;
+};
+static long item_error(uint64_t item, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "item %llu: %s", (unsigned long long)item, what);
+  return fail(HIPBFV_E_INVALIDARG, msg);
+}
+// has(element): the key set holds that element's key.  Fails, naming the first offending item, on a step of n/2 rows or more and
+// on a step with neither its own key nor every key of its chain.
+static long plan_rotate_items(u32 n, const int32_t* steps, uint64_t count, const std::function<bool(u32)>& has, RotateItemsPlan* plan) {
+  plan->kind.assign(count, RotateItemsPlan::kCopy);
+  plan->group.assign(count, 0);
+  std::vector<std::pair<int, std::pair<int32_t, uint32_t>>> seen;  // step -> (kind, group)
+  for (uint64_t i = 0; i < count; i++) {
+    const int step = steps[i];
+    if (step == 0) continue;
+    auto it = std::find_if(seen.begin(), seen.end(), [&](const auto& e) { return e.first == step; });
+    if (it == seen.end()) {
+      const u32 elt = Evaluator::galois_elt_from_step(n, step);
+      if (!elt) return item_error(i, "step count too large");
+      std::pair<int32_t, uint32_t> what{RotateItemsPlan::kDirect, elt};
+      if (!has(elt)) {
+        const std::vector<int> naf = naf_parts(step);
+        bool chain = naf.size() > 1;
+        for (int part : naf) chain = chain && (naf_skip(part, n) || has(Evaluator::galois_elt_from_step(n, part)));
+        if (!chain) return item_error(i, "required key-switching key is not present");
+        what = {RotateItemsPlan::kChain, (uint32_t)plan->chain_step.size()};
+        plan->chain_step.push_back(step);
+        plan->chain_items.emplace_back();
+      }
+      seen.emplace_back(step, what);
+      it = seen.end() - 1;
+    }
+    plan->kind[i] = it->second.first;
+    plan->group[i] = it->second.second;
+    if (it->second.first == RotateItemsPlan::kChain) plan->chain_items[it->second.second].push_back(i);
+  }
+  return HIPBFV_S_OK;
+}
+
+long hipbfv_batch_apply_galois_items(void* h, const uint64_t* ct2, const uint32_t* elts, void* keys, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!ct2 || !out2 || (!elts && count)) return HIPBFV_E_POINTER;
+  ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct2, e->ctx->ct_words(2), count)});
+  std::vector<const u64*> key(count, nullptr);
+  for (uint64_t i = 0; i < count; i++) {
+    if (!(elts[i] & 1) || elts[i] >= 2 * e->ctx->n()) return item_error(i, "the Galois element must be odd and below 2 N");
+    if (elts[i] == 1) continue;
+    const uint64_t same = std::find(elts, elts + i, elts[i]) - elts;  // (one look-up per distinct element)
+    if (!(key[i] = same < i ? key[same] : key_or_null(keys, e, (elts[i] - 1) >> 1))) return item_error(i, "required key-switching key is not present");
+  }
+  return from_status(e->ev->apply_galois_items((const u64*)ct2, elts, key.data(), (u64*)out2, count, (hipStream_t)stream));
+HIPBFV_END
+
+long hipbfv_batch_rotate_rows_items(void* h, const uint64_t* ct2, const int32_t* steps, void* keys, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!ct2 || !out2 || (!steps && count)) return HIPBFV_E_POINTER;
+  if (!e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
+  const size_t w = e->ctx->ct_words(2);
+  ALIAS_OR_RETURN(cts(out2, w, count), {cts(ct2, w, count)});
+  if (!count) return HIPBFV_S_OK;
+  hipStream_t s = (hipStream_t)stream;
+  RotateItemsPlan plan;
+  if (long hr = plan_rotate_items(e->ctx->n(), steps, count, [&](u32 elt) { return key_or_null(keys, e, (elt - 1) >> 1) != nullptr; }, &plan)) return hr;
+  // copies and direct keys: one pass over the caller's buffers, the chain items left out of it
+  std::vector<u32> elts(count);
+  std::vector<const u64*> key(count, nullptr);
+  for (uint64_t i = 0; i < count; i++) {
+    elts[i] = plan.kind[i] == RotateItemsPlan::kCopy ? 1u : plan.kind[i] == RotateItemsPlan::kDirect ? plan.group[i] : 0u;
+    if (plan.kind[i] == RotateItemsPlan::kDirect) key[i] = key_or_null(keys, e, (elts[i] - 1) >> 1);
+  }
+  u32* const watch = Evaluator::watch_status();
+  WatchScope quiet(nullptr);  // (the chain groups count their own items: the results are noted once, when all are in place)
+  if (int rc = e->ev->apply_galois_items((const u64*)ct2, elts.data(), key.data(), (u64*)out2, count, s, false)) return from_status(rc);
+  if (!plan.chain_step.empty()) {
+    // a chain group: its items in a compact stage, hipbfv_batch_rotate_rows' own chain over the stage, the results to their places
+    size_t largest = 0;
+    for (const auto& items : plan.chain_items) largest = std::max(largest, items.size());
+    ScratchGuard sg(e->ev->scratch(), 2 * largest * w * sizeof(u64), s);
+    if (!sg.p) return from_status(kOutOfMemory);
+    u64* in_stage = (u64*)sg.p;
+    u64* out_stage = in_stage + largest * w;
+    for (size_t g = 0; g < plan.chain_step.size(); g++) {
+      const std::vector<uint64_t>& items = plan.chain_items[g];
+      if (copy_items(in_stage, (const u64*)ct2, nullptr, w, w, items, s) != hipSuccess) return from_status(kHipError);
+      if (long hr = batch_rotate_internal(e, in_stage, plan.chain_step[g], keys, out_stage, items.size(), s)) return hr;
+      if (copy_items(out_stage, nullptr, (u64*)out2, w, w, items, s) != hipSuccess) return from_status(kHipError);
+    }
+  }
+  WatchScope noted(watch);
+  return from_status(e->ev->note_result((const u64*)out2, 2, e->ctx->K(), count, s));
+HIPBFV_END
+
+// The plan of hipbfv_batch_rotate_rows_items for `steps` at degree n over a key set that holds exactly the keys of `present_elts`:
+// kind[i] 0 = copied, 1 = in the mixed launch (group[i]: its Galois element), 2 = in a NAF chain group (group[i]: which).  Host only.
+long hipbfv_debug_rotate_items_plan(uint64_t n, const int32_t* steps, uint64_t count, const uint32_t* present_elts, uint64_t num_present, int32_t* kind,
+                                    uint32_t* group, uint64_t* chain_groups) HIPBFV_BEGIN
+  if ((!steps || !kind || !group) && count) return HIPBFV_E_POINTER;
+  if ((!present_elts && num_present) || !chain_groups) return HIPBFV_E_POINTER;
+  if (n < 4 || n > (1u << 20) || (n & (n - 1))) return fail(HIPBFV_E_INVALIDARG, "the degree must be a power of two");
+  RotateItemsPlan plan;
+  if (long hr = plan_rotate_items((u32)n, steps, count, [&](u32 elt) { return std::find(present_elts, present_elts + num_present, elt) != present_elts + num_present; },
+                                  &plan))
+    return hr;
+  std::copy(plan.kind.begin(), plan.kind.end(), kind);
+  std::copy(plan.group.begin(), plan.group.end(), group);
+  *chain_groups = plan.chain_step.size();
+  return HIPBFV_S_OK;
 HIPBFV_END
 
 long hipbfv_batch_add(void* h, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t size, uint64_t count, void* stream) HIPBFV_BEGIN

@@ -288,8 +288,10 @@ int Evaluator::take_status(u32* status_dev, u32* first_bad, hipStream_t s) {
   return kOk;
 }
 
-u32 Evaluator::galois_elt_from_step(int step) const {
-  const u32 n = ctx_->n(), m = 2 * n;
+u32 Evaluator::galois_elt_from_step(int step) const { return galois_elt_from_step(ctx_->n(), step); }
+
+u32 Evaluator::galois_elt_from_step(u32 n, int step) {
+  const u32 m = 2 * n;
   if (step == 0) return m - 1;
   const u32 pos = (u32)(step < 0 ? -(long)step : (long)step);
   if (pos >= (n >> 1)) return 0;
@@ -387,15 +389,16 @@ Evaluator::KeyMapLease::~KeyMapLease() {
 // Device tables of a per-item key selection (KeySel): the key pointer table and, for every chunk of the call, the chunk's items
 // sorted by key index (stable: items of one key keep their order).  One pinned staging block and one H2D copy per call; both
 // buffers go back to their pools behind the call's last launch.
-int Evaluator::stage_keymap(const KeySel& sel, size_t count, size_t chunk, hipStream_t s, KeyMapLease& lease) {
+int Evaluator::stage_keymap(const KeySel& sel, size_t count, size_t chunk, hipStream_t s, KeyMapLease& lease, const u32* item_words) {
   if (!sel.per_item()) return kOk;
   if (!sel.nkeys || !sel.index || !sel.period || !count || !chunk) return kInvalidArg;
   for (u32 k = 0; k < sel.nkeys; k++)
     if (!sel.keys[k]) return kNoKey;
   for (size_t i = 0; i < sel.period; i++)
-    if (sel.index[i] >= sel.nkeys) return kInvalidArg;
+    if (sel.index[i] >= sel.nkeys && !(item_words && sel.index[i] == kKeyNone)) return kInvalidArg;
   const size_t tab_bytes = ((size_t)sel.nkeys * sizeof(u64*) + 15) & ~(size_t)15;
-  const size_t bytes = tab_bytes + count * sizeof(uint2);
+  const size_t order_bytes = count * sizeof(uint2);
+  const size_t bytes = tab_bytes + order_bytes + (item_words ? count * sizeof(u32) : 0);
   lease.ev = this;
   lease.s = s;
   lease.host = pinned_.acquire(bytes);
@@ -405,21 +408,26 @@ int Evaluator::stage_keymap(const KeySel& sel, size_t count, size_t chunk, hipSt
   const u64** tab = reinterpret_cast<const u64**>(lease.host);
   for (u32 k = 0; k < sel.nkeys; k++) tab[k] = sel.keys[k];
   uint2* order = reinterpret_cast<uint2*>(static_cast<unsigned char*>(lease.host) + tab_bytes);
-  std::vector<u32> start(sel.nkeys + 1);
+  std::vector<u32> start(sel.nkeys + 2);  // (one bucket per key and a last one for the items without a key)
   for (size_t off = 0; off < count; off += chunk) {
     const size_t c = std::min(chunk, count - off);
     // counting sort of the chunk's items by key index
     std::fill(start.begin(), start.end(), 0u);
-    for (size_t i = 0; i < c; i++) start[sel.index[(sel.first + off + i) % sel.period] + 1]++;
-    for (u32 k = 0; k < sel.nkeys; k++) start[k + 1] += start[k];
+    for (size_t i = 0; i < c; i++) start[std::min(sel.index[(sel.first + off + i) % sel.period], sel.nkeys) + 1]++;
+    for (u32 k = 0; k <= sel.nkeys; k++) start[k + 1] += start[k];
     for (size_t i = 0; i < c; i++) {
       const u32 k = sel.index[(sel.first + off + i) % sel.period];
-      order[off + start[k]++] = make_uint2((u32)i, k);
+      if (k < sel.nkeys)
+        order[off + start[k]++] = make_uint2((u32)i, k);
+      else
+        order[off + start[sel.nkeys]++] = make_uint2(0xFFFFFFFFu, 0u);
     }
   }
+  if (item_words) std::copy(item_words, item_words + count, reinterpret_cast<u32*>(static_cast<unsigned char*>(lease.host) + tab_bytes + order_bytes));
   HB_CHECK(hipMemcpyAsync(lease.dev, lease.host, bytes, hipMemcpyHostToDevice, s));
   lease.km.keys = reinterpret_cast<const u64* const*>(lease.dev);
   lease.km.order = reinterpret_cast<const uint2*>(static_cast<unsigned char*>(lease.dev) + tab_bytes);
+  if (item_words) lease.words = reinterpret_cast<const u32*>(static_cast<unsigned char*>(lease.dev) + tab_bytes + order_bytes);
   return kOk;
 }
 
@@ -431,7 +439,7 @@ bool Evaluator::ks_split_for(size_t count) const {
 
 // out2[op] = base[op] (masked) + modDown( sum_J NTT(target_J) (.) key[J] ); scratch >= count * ks_scratch_words()
 int Evaluator::key_switch(const u64* target, size_t tstride, const u64* key, const u64* base, size_t bstride, u32 base_mask,
-                          u64* out2, size_t count, u64* scratch, hipStream_t s, const u64* extra, KeyMap km, u32 ginv) {
+                          u64* out2, size_t count, u64* scratch, hipStream_t s, const u64* extra, KeyMap km, u32 ginv, const u32* ginv_tab) {
   const DevCtx& h = ctx_->host();
   const u32 n = h.n, K = h.K, KK = h.KK;
   u64* T = scratch;
@@ -439,14 +447,14 @@ int Evaluator::key_switch(const u64* target, size_t tstride, const u64* key, con
   std::vector<u32> mods;
   for (u32 i = 0; i < KK; i++) mods.push_back(i);
   const bool split_ok = ks_split_for(count);
-  if (ginv && !split_ok) return kInvalidArg;  // (apply_galois rotates into a copy for the whole-polynomial kernels)
+  if ((ginv || ginv_tab) && !split_ok) return kInvalidArg;  // (apply_galois rotates into a copy for the whole-polynomial kernels)
   if (split_ok) {
     // head / middle / tail split transforms (kernels_split.hip): 3 launches (4 when FP64- and integer-policy key primes are
     // mixed: one middle kernel per policy), no whole-polynomial NTT round trips
     const bool mixed = h.ks_ni != 0;
-    HB_LAUNCH(kKernKsHead, count, launch_ks_head(ctx_->dev(), h.tw_fwd, h.logn, (int)h.pack_ks, mixed, K, target, tstride, T, count, s, ginv));
+    HB_LAUNCH(kKernKsHead, count, launch_ks_head(ctx_->dev(), h.tw_fwd, h.logn, (int)h.pack_ks, mixed, K, target, tstride, T, count, s, ginv, ginv_tab));
     HB_LAUNCH(kKernKsMid, count, launch_ks_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, h, T, key, ACC, count, s, km));
-    HB_LAUNCH(kKernKsTail, count, launch_ks_tail(ctx_->dev(), h.tw_inv, h.logn, (int)h.pack_ks, mixed, ACC, base, bstride, base_mask, extra, out2, count, s, ginv));
+    HB_LAUNCH(kKernKsTail, count, launch_ks_tail(ctx_->dev(), h.tw_inv, h.logn, (int)h.pack_ks, mixed, ACC, base, bstride, base_mask, extra, out2, count, s, ginv, ginv_tab));
     return kOk;
   }
   HB_LAUNCH(kKernKsDecompose, count, launch_ks_decompose(ctx_->dev(), n, K, target, tstride, T, count, s));
@@ -559,16 +567,20 @@ int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64*
   return note_result(out2, 2, h.K, count, s);
 }
 
+// g^{-1} mod 2n (Newton iteration, g odd)
+static u32 galois_inverse(u32 elt, u32 n) {
+  u64 inv = 1;
+  for (int i = 0; i < 6; i++) inv = inv * (2 - (u64)elt * inv);
+  return (u32)(inv & (2 * n - 1));
+}
+
 int Evaluator::apply_galois(const u64* ct2, u32 elt, const KeySel& key, u64* out2, size_t count, hipStream_t s, const u64* addend) {
   const DevCtx& h = ctx_->host();
   const u32 n = h.n, K = h.K;
   if (!(elt & 1) || elt >= 2 * n) return kInvalidArg;
   if (h.KK < 2 || !key.present()) return kNoKey;
   if (h.logn > 15) return kUnsupported;
-  // g^{-1} mod 2n (Newton iteration, g odd)
-  u64 inv = 1;
-  for (int i = 0; i < 6; i++) inv = inv * (2 - (u64)elt * inv);
-  const u32 ginv = (u32)(inv & (2 * n - 1));
+  const u32 ginv = galois_inverse(elt, n);
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, 65535 / ((size_t)h.KK * K)));
   const size_t rot_words = (size_t)2 * K * n;
   const size_t cc = std::min(chunk, count);
@@ -599,6 +611,110 @@ int Evaluator::apply_galois(const u64* ct2, u32 elt, const KeySel& key, u64* out
     if (rc) return rc;
   }
   return note_result(out2, 2, K, count, s);
+}
+
+// Item i by its own element elts[i].  Where apply_galois would read the automorphism through the key switch, ONE head / middle / tail
+// sequence per chunk serves every element: the head and the tail take item i's g^-1 from a device table (kernels_split.hip GinvArg), the
+// middle kernel takes item i's key through the KeyMap -- one entry of the key table per distinct element, the walk sorted by element, so
+// that the items of one element share its key rows in an XCD's L2 as the items of one client do.  Copied and left-out items stay in the
+// grid (their workgroups leave at once): the chunk keeps the caller's item numbering, no gather.  Elsewhere (in place, the
+// whole-polynomial kernels, N outside 4096 ... 16384, HIPBFV_NO_FUSED_GALOIS) the items are grouped by element and every group goes
+// through apply_galois on a compact stage; the bits are the same.
+int Evaluator::apply_galois_items(const u64* ct2, const u32* elts, const u64* const* keys, u64* out2, size_t count, hipStream_t s, bool watch) {
+  const DevCtx& h = ctx_->host();
+  const u32 n = h.n, K = h.K;
+  if (!count) return kOk;
+  if (!elts) return kInvalidArg;
+  // distinct elements > 1 in order of first appearance; kidx[i]: item i's entry, kKeyNone for a copied or left-out item
+  std::vector<u32> delt, kidx(count, kKeyNone);
+  std::vector<const u64*> dkey;
+  for (size_t i = 0; i < count; i++) {
+    const u32 e = elts[i];
+    if (e <= 1) continue;
+    if (!(e & 1) || e >= 2 * n) return kInvalidArg;
+    if (h.KK < 2 || !keys || !keys[i]) return kNoKey;
+    const size_t d = std::find(delt.begin(), delt.end(), e) - delt.begin();
+    if (d == delt.size()) delt.push_back(e), dkey.push_back(keys[i]);
+    kidx[i] = (u32)d;
+  }
+  if (h.logn > 15) return kUnsupported;
+  const size_t rot_words = (size_t)2 * K * n;
+  if (ct2 != out2) {  // element 1: runs of neighbouring items, one copy each
+    for (size_t i = 0; i < count;) {
+      size_t r = 0;
+      while (i + r < count && elts[i + r] == 1) r++;
+      if (r) HB_CHECK(launch_copy_words(ct2 + i * rot_words, out2 + i * rot_words, r * rot_words, s));
+      i += r ? r : 1;
+    }
+  }
+  if (delt.empty()) return watch ? note_result(out2, 2, K, count, s) : (int)kOk;
+  const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, 65535 / ((size_t)h.KK * K)));
+  const size_t cc = std::min(chunk, count);
+  const size_t last = count % chunk ? count % chunk : cc;
+  const bool fused = fuse_galois_ && ct2 != out2 && h.logn >= 12 && h.logn <= 14 && ks_split_for(cc) && ks_split_for(last);
+  if (fused) {
+    std::vector<u32> ginv(count);
+    for (size_t i = 0; i < count; i++) ginv[i] = kidx[i] == kKeyNone ? kGinvSkip : galois_inverse(elts[i], n);
+    KeySel sel;
+    sel.keys = dkey.data();
+    sel.nkeys = (u32)dkey.size();
+    sel.index = kidx.data();
+    sel.period = count;
+    KeyMapLease kl;
+    if (int rc = stage_keymap(sel, count, chunk, s, kl, ginv.data())) return rc;
+    ScratchGuard sg(pool_, cc * ks_scratch_words() * sizeof(u64), s);
+    if (!sg.p) return kOutOfMemory;
+    for (size_t off = 0; off < count; off += chunk) {
+      const size_t c = std::min(chunk, count - off);
+      if (std::all_of(kidx.begin() + off, kidx.begin() + off + c, [](u32 k) { return k == kKeyNone; })) continue;
+      const u64* in = ct2 + off * rot_words;
+      int rc = key_switch(in + (size_t)K * n, rot_words, nullptr, in, rot_words, 1u, out2 + off * rot_words, c, (u64*)sg.p, s, nullptr, kl.at(off), 0, kl.words + off);
+      if (rc) return rc;
+    }
+    return watch ? note_result(out2, 2, K, count, s) : (int)kOk;
+  }
+  // grouped: per element, the group's items gathered into a compact stage, rotated by the uniform path, scattered to their places
+  // (a group that is the whole call needs no stage).  The tables of item addresses live in pinned memory the device reads directly.
+  {
+    WatchScope quiet(nullptr);  // the groups' own item numbers mean nothing to the caller: the results are noted once, below
+    if (delt.size() == 1 && std::all_of(kidx.begin(), kidx.end(), [](u32 k) { return k == 0; })) {
+      if (int rc = apply_galois(ct2, delt[0], dkey[0], out2, count, s)) return rc;
+    } else {
+      const size_t sub = std::min<size_t>(chunk_ops_, 32768);  // items per stage (and per gather / scatter grid)
+      struct Pinned {
+        PinnedPool& pool;
+        hipStream_t s;
+        void* p;
+        ~Pinned() {
+          if (p) pool.release(p, s);
+        }
+      } tabs{pinned_, s, pinned_.acquire(2 * count * sizeof(u64*))};
+      if (!tabs.p) return kOutOfMemory;
+      const u64** src = static_cast<const u64**>(tabs.p);
+      u64** dst = static_cast<u64**>(tabs.p) + count;
+      size_t filled = 0, largest = 0;
+      std::vector<size_t> first(delt.size() + 1, 0);
+      for (size_t d = 0; d < delt.size(); d++) {
+        for (size_t i = 0; i < count; i++)
+          if (kidx[i] == d) src[filled] = ct2 + i * rot_words, dst[filled] = out2 + i * rot_words, filled++;
+        first[d + 1] = filled;
+        largest = std::max(largest, std::min(sub, filled - first[d]));
+      }
+      ScratchGuard sg(pool_, 2 * largest * rot_words * sizeof(u64), s);
+      if (!sg.p) return kOutOfMemory;
+      u64* in_stage = (u64*)sg.p;
+      u64* out_stage = in_stage + largest * rot_words;
+      for (size_t d = 0; d < delt.size(); d++) {
+        for (size_t off = first[d]; off < first[d + 1]; off += sub) {
+          const size_t c = std::min(sub, first[d + 1] - off);
+          HB_CHECK(launch_gather_items(src + off, in_stage, rot_words, c, s));
+          if (int rc = apply_galois(in_stage, delt[d], dkey[d], out_stage, c, s)) return rc;
+          HB_CHECK(launch_scatter_items(out_stage, dst + off, rot_words, c, s));
+        }
+      }
+    }
+  }
+  return watch ? note_result(out2, 2, K, count, s) : (int)kOk;
 }
 
 static int eltwise_chunks(Profiler& prof_, const DevCtx* dev, u32 n, u32 K, const u64* a, const u64* b, u64* out, size_t residue_polys, int mode,

@@ -196,6 +196,11 @@ class Evaluator {
   bool member_tail_ok(size_t count) const;
   // out2 = (sigma_g(c0), 0) + switch_key(sigma_g(c1), key)
   int apply_galois(const u64* ct2, u32 galois_elt, const KeySel& key, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr);
+  // every item by its OWN Galois element in one key-switch pass (mixed-step rotation batches): elts / keys are HOST arrays of `count`
+  // entries, keys[i] the device key of elts[i] (not read for the elements 0 and 1).  Element 1: the item is copied.  Element 0
+  // (callers inside the library only: items another pass produces): the item is left out, out2[i] is not written.  Everything
+  // is validated before the first launch.  watch = false: the caller notes the results itself (it fills the left-out items first).
+  int apply_galois_items(const u64* ct2, const u32* elts, const u64* const* keys, u64* out2, size_t count, hipStream_t s, bool watch = true);
   int mod_switch_next(const u64* ct, u32 size, u64* out, size_t count, hipStream_t s);  // out has K-1 residues per polynomial
   int add(const u64* a, const u64* b, u64* out, u32 size, size_t count, hipStream_t s);
   int sub(const u64* a, const u64* b, u64* out, u32 size, size_t count, hipStream_t s);
@@ -243,12 +248,14 @@ class Evaluator {
   int ntt(u64* data, size_t polys, u32 nprimes, bool inverse, hipStream_t s);
 
   u32 galois_elt_from_step(int step) const;  // 0 if |step| >= n/2
+  static u32 galois_elt_from_step(u32 n, int step);
   size_t chunk_ops() const { return chunk_ops_; }
   void set_chunk_ops(size_t c) { chunk_ops_ = c ? c : 1; }
 
  private:
   int key_switch(const u64* target, size_t tstride, const u64* key, const u64* base, size_t bstride, u32 base_mask, u64* out2,
-                 size_t count, u64* scratch, hipStream_t s, const u64* extra = nullptr, KeyMap km = KeyMap{}, u32 ginv = 0);
+                 size_t count, u64* scratch, hipStream_t s, const u64* extra = nullptr, KeyMap km = KeyMap{}, u32 ginv = 0,
+                 const u32* ginv_tab = nullptr);
   bool ks_split_for(size_t count) const;  // key_switch takes the head / middle / tail kernels for a batch of this size
   size_t ks_scratch_words() const;
   // the device tables of a per-item key selection for one call: `order` holds, for every chunk of `chunk` items, the chunk's items
@@ -259,10 +266,15 @@ class Evaluator {
     void* dev = nullptr;
     void* host = nullptr;
     KeyMap km;
+    const u32* words = nullptr;  // device copy of stage_keymap's item_words
     KeyMap at(size_t off) const { return km.keys ? KeyMap{km.keys, km.order + off} : KeyMap{}; }
     ~KeyMapLease();
   };
-  int stage_keymap(const KeySel& sel, size_t count, size_t chunk, hipStream_t s, KeyMapLease& lease);
+  // item_words (optional): one u32 per item of the call, staged behind the tables with the same copy (the per-item g^-1 of
+  // apply_galois_items).  With it an index of kKeyNone is allowed: the item takes no key -- it is listed last in its chunk's order, as
+  // item 0xFFFFFFFF, which the middle kernels drop.
+  static constexpr u32 kKeyNone = 0xFFFFFFFFu;
+  int stage_keymap(const KeySel& sel, size_t count, size_t chunk, hipStream_t s, KeyMapLease& lease, const u32* item_words = nullptr);
   PinnedPool pinned_;
   Context* ctx_;
   u32* status_dev_ = nullptr;

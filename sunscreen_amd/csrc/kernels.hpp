@@ -56,13 +56,17 @@ hipError_t launch_ntt_split(const DevCtx* ctx, const MulOp* tw, u32 logn, u64* d
 // 4-byte aligned and readable up to the next word boundary (the DevCtx members are; the launchers refuse anything else)
 // ginv != 0 (launch_ks_head, launch_ks_tail): a rotation's key switch -- the target / the base polynomials are sigma_g(.) for g = ginv^-1 mod 2N,
 // read through the automorphism instead of from a rotated copy (base and out2 must not alias then)
+// ginv_tab != nullptr (N = 4096 ... 16384): a device table u32[ops] with item i's own g^-1 in place of the scalar -- 0: no automorphism for
+// that item, kGinvSkip: the item is not part of the launch (its T rows and its output stay untouched; the KeyMap of the middle launch
+// lists it with an item index >= ops, which that kernel drops)
+constexpr u32 kGinvSkip = 0xFFFFFFFFu;
 hipError_t launch_ks_head(const DevCtx* ctx, const MulOp* twf, u32 logn, int pack, bool mixed, u32 K, const u64* target, size_t tstride, u64* T, size_t ops, hipStream_t s,
-                          u32 ginv = 0);
+                          u32 ginv = 0, const u32* ginv_tab = nullptr);
 // h: the host copy of *ctx (its residue lists' counts: ks_nd 8-byte FP64 rows, ks_ndp packed FP64 rows, ks_ni integer rows)
 hipError_t launch_ks_mid(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, u32 logn, const DevCtx& h, const u64* T, const u64* key, u64* ACC, size_t ops,
                          hipStream_t s, KeyMap km = KeyMap{});
 hipError_t launch_ks_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, int pack, bool mixed, const u64* ACC, const u64* base, size_t bstride, u32 base_mask, const u64* extra, u64* out2,
-                          size_t ops, hipStream_t s, u32 ginv = 0);
+                          size_t ops, hipStream_t s, u32 ginv = 0, const u32* ginv_tab = nullptr);
 // split BEHZ multiply (2 x 2 -> 3), K <= 4
 // Per-member operands of a MERGED multiply launch (graph executor): item i of the launch is item (first + i) % per of member
 // (first + i) / per, whose two factors are read where they are (u64[per][2][K][N] each; b == a for a squaring launch) -- no gather

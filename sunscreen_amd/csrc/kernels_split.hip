@@ -878,6 +878,25 @@ __device__ __forceinline__ u64 galois_gather(BufRsrc r, u32 soff, u32 j, u32 gin
   return (i2 & N) && w ? q - w : w;
 }
 
+// The automorphism argument of the key-switch head / tail.  TAB = false: one g^-1 for the whole launch, the scalar launch argument
+// every uniform caller passes (0 = no automorphism) -- those instantiations are what they were before the table existed.
+// TAB = true: a device table with one entry per item of the launch (mixed-step rotation batches, Evaluator::apply_galois_items):
+// 0 = no automorphism for that item, kGinvSkip = the item is not part of this launch (its workgroups leave at once).  The item
+// index is workgroup-uniform, so the entry arrives through the scalar unit.  Whether the launch takes the XCD row order is a
+// property of the LAUNCH (a table launch always does): a per-item test would send the workgroups of one grid through two index maps.
+template <bool TAB>
+struct GinvArg {
+  using type = u32;
+  static __device__ __forceinline__ bool launch_gathers(u32 g) { return g != 0u; }
+  static __device__ __forceinline__ u32 of(u32 g, u32) { return g; }
+};
+template <>
+struct GinvArg<true> {
+  using type = const u32*;
+  static __device__ __forceinline__ bool launch_gathers(const u32*) { return true; }
+  static __device__ __forceinline__ u32 of(const u32* __restrict__ tab, u32 op) { return tab[op]; }
+};
+
 __device__ __forceinline__ bool residue_is_f64(const DevMod& dm) { return dm.use_f64 && dm.split_ok; }
 template <class A, int NC>
 __device__ __forceinline__ void head_fwd(const A& ar, typename A::V (&v)[NC], const typename A::Tw* __restrict__ tw);
@@ -911,14 +930,15 @@ __device__ __forceinline__ void ks_head_store(const DevCtx* __restrict__ ctx, co
 // branch is wave-uniform.  MIXED = false is the all-FP64 kernel (every SEAL default parameter set).
 // -------------------------------------------------------------------------------------------------
 // PACK: DevCtx::pack_ks (0: 8-byte rows, 1: every row 48-bit packed, 2: per key prime, DevCtx::ks_row_mask)
-template <int L, int PACK, bool MIXED>
+template <int L, int PACK, bool MIXED, bool TAB = false>
 __global__ __launch_bounds__(kHeadThreads) void ks_head_kernel(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twf_base,
-                                                               const u64* __restrict__ target, size_t tstride, double* __restrict__ T, u32 ginv) {
+                                                               const u64* __restrict__ target, size_t tstride, double* __restrict__ T,
+                                                               typename GinvArg<TAB>::type ginv_arg) {
   using G = EdgeGeom<L>;
   constexpr int NC = G::HEAD_NC;
   constexpr u32 N = 1u << L;
   u32 bx = blockIdx.x, J = blockIdx.y, op = blockIdx.z;
-  if (KS_XCD_ROWS && ginv) {
+  if (KS_XCD_ROWS && GinvArg<TAB>::launch_gathers(ginv_arg)) {
     // r06 s32: a rotation's head GATHERS its digit row through the automorphism -- every workgroup of a row touches lines all over the
     // row.  Workgroups go to the 8 XCDs round robin in dispatch order (x fastest), so the TB workgroups of one row landed on TB different
     // XCDs and every one of their L2s fetched the row from HBM: 4.9 MB read per item at N = 16384 where 1.05 MB is compulsory
@@ -930,6 +950,8 @@ __global__ __launch_bounds__(kHeadThreads) void ks_head_kernel(const DevCtx* __r
       bx = q % TB, J = row % gridDim.y, op = row / gridDim.y;
     }
   }
+  const u32 ginv = GinvArg<TAB>::of(ginv_arg, op);
+  if (TAB && ginv == kGinvSkip) return;
   const u32 t = bx * kHeadThreads + threadIdx.x;
   const u32 K = ctx->K, KK = ctx->KK;
   const u64* src = target + (size_t)op * tstride + (size_t)J * N;
@@ -1314,20 +1336,23 @@ __device__ __forceinline__ void tail_special_d(const DevCtx* __restrict__ ctx, c
 }
 
 // MIXED: rows of ACC that belong to integer-policy key primes hold lazy u64 values in [0, 2q) (ks_mid_int_kernel)
-template <int L, bool PACK, bool MIXED>
+template <int L, bool PACK, bool MIXED, bool TAB = false>
 __global__ __launch_bounds__(kHeadThreads) void ks_tail_kernel(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base,
                                                                const double* __restrict__ ACC, const u64* __restrict__ base, size_t bstride,
-                                                               u32 base_mask, const u64* __restrict__ extra, u64* __restrict__ out, u32 ginv) {
+                                                               u32 base_mask, const u64* __restrict__ extra, u64* __restrict__ out,
+                                                               typename GinvArg<TAB>::type ginv_arg) {
   using G = EdgeGeom<L>;
   constexpr u32 N = 1u << L;
   u32 bx = blockIdx.x, c = blockIdx.y, op = blockIdx.z;
-  if (KS_XCD_ROWS && ginv) {  // a rotation's tail gathers sigma_g(c0): the workgroups of one (polynomial, item) on one XCD (ks_head_kernel)
+  if (KS_XCD_ROWS && GinvArg<TAB>::launch_gathers(ginv_arg)) {  // a rotation's tail gathers sigma_g(c0): the workgroups of one (polynomial, item) on one XCD (ks_head_kernel)
     const u32 TB = gridDim.x, R = gridDim.y * gridDim.z;
     if ((R & 7u) == 0u) {
       const u32 d = blockIdx.x + TB * (blockIdx.y + gridDim.y * blockIdx.z), q = d >> 3, row = (q / TB) * 8u + (d & 7u);
       bx = q % TB, c = row % gridDim.y, op = row / gridDim.y;
     }
   }
+  const u32 ginv = GinvArg<TAB>::of(ginv_arg, op);
+  if (TAB && ginv == kGinvSkip) return;
   const u32 t = bx * kHeadThreads + threadIdx.x;
   const u32 K = ctx->K, KK = ctx->KK;
   const double* acc = ACC + ((size_t)op * 2 + c) * KK * N;
@@ -2830,29 +2855,45 @@ hipError_t launch_ntt_split(const DevCtx* ctx, const MulOp* tw, u32 logn, u64* d
     default: return hipErrorInvalidValue;    \
   }
 
-template <int L>
-static hipError_t ks_head_t(const DevCtx* ctx, const MulOp* twf, int pack, bool mixed, u32 K, const u64* target, size_t tstride, u64* T, size_t ops, hipStream_t s,
-                            u32 ginv) {
+template <int L, bool TAB>
+static hipError_t ks_head_g(const DevCtx* ctx, const MulOp* twf, int pack, bool mixed, u32 K, const u64* target, size_t tstride, u64* T, size_t ops, hipStream_t s,
+                            typename GinvArg<TAB>::type ginv) {
   const dim3 grid(EdgeGeom<L>::HEAD_THREADS / kHeadThreads, K, (unsigned)ops);
   if constexpr (L == 15) {
     if (!mixed) return hipErrorInvalidValue;
-    ks_head_kernel<L, 0, true><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
+    ks_head_kernel<L, 0, true, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
     return hipGetLastError();
   } else if (mixed)
-    ks_head_kernel<L, 0, true><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
+    ks_head_kernel<L, 0, true, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
   else if (pack == 2) {
-    if constexpr (L >= 13) ks_head_kernel<L, 2, false><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
+    if constexpr (L >= 13) ks_head_kernel<L, 2, false, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
     else return hipErrorInvalidValue;  // (context.cpp: beside pack_mul == 2 only)
   } else if (pack)
-    ks_head_kernel<L, 1, false><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
+    ks_head_kernel<L, 1, false, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
   else
-    ks_head_kernel<L, 0, false><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
+    ks_head_kernel<L, 0, false, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twf, target, tstride, reinterpret_cast<double*>(T), ginv);
   return hipGetLastError();
+}
+template <int L>
+static hipError_t ks_head_t(const DevCtx* ctx, const MulOp* twf, int pack, bool mixed, u32 K, const u64* target, size_t tstride, u64* T, size_t ops, hipStream_t s,
+                            u32 ginv) {
+  return ks_head_g<L, false>(ctx, twf, pack, mixed, K, target, tstride, T, ops, s, ginv);
+}
+// per-item automorphisms (GinvArg): N = 4096 ... 16384 (Evaluator::apply_galois_items groups the items by element elsewhere)
+template <int L>
+static hipError_t ks_head_tab_t(const DevCtx* ctx, const MulOp* twf, int pack, bool mixed, u32 K, const u64* target, size_t tstride, u64* T, size_t ops, hipStream_t s,
+                                const u32* ginv_tab) {
+  if constexpr (L == 15) return hipErrorInvalidValue;
+  else return ks_head_g<L, true>(ctx, twf, pack, mixed, K, target, tstride, T, ops, s, ginv_tab);
 }
 // pack: DevCtx::pack_ks of the context behind `ctx` (48-bit packed intermediates, see nat_load); mixed: DevCtx::ks_ni != 0
 // ginv != 0: the target is sigma_g(target) for the Galois element g = ginv^-1 mod 2N, read through the automorphism
+// ginv_tab != nullptr: one g^-1 per item instead (device, u32[ops]; 0: no automorphism, kGinvSkip: the item is left out)
 hipError_t launch_ks_head(const DevCtx* ctx, const MulOp* twf, u32 logn, int pack, bool mixed, u32 K, const u64* target, size_t tstride, u64* T, size_t ops, hipStream_t s,
-                          u32 ginv) {
+                          u32 ginv, const u32* ginv_tab) {
+  if (ginv_tab) {
+    KS_DISPATCH(ks_head_tab_t, ctx, twf, pack, mixed, K, target, tstride, T, ops, s, ginv_tab)
+  }
   KS_DISPATCH(ks_head_t, ctx, twf, pack, mixed, K, target, tstride, T, ops, s, ginv)
 }
 
@@ -2893,25 +2934,40 @@ hipError_t launch_ks_mid(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, 
   KS_DISPATCH(ks_mid_t, ctx, twf, twi, h.pack_ks == 1, ctx->ks_res_d, h.ks_nd, ctx->ks_res_dp, h.ks_ndp, ctx->ks_res_i, h.ks_ni, T, key, ACC, ops, s, km)
 }
 
-template <int L>
-static hipError_t ks_tail_t(const DevCtx* ctx, const MulOp* twi, int pack_ks, bool mixed, const u64* ACC, const u64* base, size_t bstride, u32 base_mask,
-                            const u64* extra, u64* out2, size_t ops, hipStream_t s, u32 ginv) {
+template <int L, bool TAB>
+static hipError_t ks_tail_g(const DevCtx* ctx, const MulOp* twi, int pack_ks, bool mixed, const u64* ACC, const u64* base, size_t bstride, u32 base_mask,
+                            const u64* extra, u64* out2, size_t ops, hipStream_t s, typename GinvArg<TAB>::type ginv) {
   const dim3 grid((1u << L) / 4 / kHeadThreads, 2, (unsigned)ops);
   if constexpr (L == 15) {
     if (!mixed) return hipErrorInvalidValue;
-    ks_tail_kernel<L, false, true><<<grid, kHeadThreads, 0, s>>>(ctx, twi, reinterpret_cast<const double*>(ACC), base, bstride, base_mask, extra, out2, ginv);
+    ks_tail_kernel<L, false, true, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twi, reinterpret_cast<const double*>(ACC), base, bstride, base_mask, extra, out2, ginv);
     return hipGetLastError();
   } else if (mixed)
-    ks_tail_kernel<L, false, true><<<grid, kHeadThreads, 0, s>>>(ctx, twi, reinterpret_cast<const double*>(ACC), base, bstride, base_mask, extra, out2, ginv);
+    ks_tail_kernel<L, false, true, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twi, reinterpret_cast<const double*>(ACC), base, bstride, base_mask, extra, out2, ginv);
   else if (pack_ks == 1)  // (2 = per key prime: the rows of T only, the accumulator rows are doubles)
-    ks_tail_kernel<L, true, false><<<grid, kHeadThreads, 0, s>>>(ctx, twi, reinterpret_cast<const double*>(ACC), base, bstride, base_mask, extra, out2, ginv);
+    ks_tail_kernel<L, true, false, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twi, reinterpret_cast<const double*>(ACC), base, bstride, base_mask, extra, out2, ginv);
   else
-    ks_tail_kernel<L, false, false><<<grid, kHeadThreads, 0, s>>>(ctx, twi, reinterpret_cast<const double*>(ACC), base, bstride, base_mask, extra, out2, ginv);
+    ks_tail_kernel<L, false, false, TAB><<<grid, kHeadThreads, 0, s>>>(ctx, twi, reinterpret_cast<const double*>(ACC), base, bstride, base_mask, extra, out2, ginv);
   return hipGetLastError();
 }
-// extra: optional ciphertexts u64[ops][2][K][N] added to the result; ginv != 0: the base polynomials are read through sigma_g (launch_ks_head)
+template <int L>
+static hipError_t ks_tail_t(const DevCtx* ctx, const MulOp* twi, int pack_ks, bool mixed, const u64* ACC, const u64* base, size_t bstride, u32 base_mask,
+                            const u64* extra, u64* out2, size_t ops, hipStream_t s, u32 ginv) {
+  return ks_tail_g<L, false>(ctx, twi, pack_ks, mixed, ACC, base, bstride, base_mask, extra, out2, ops, s, ginv);
+}
+template <int L>
+static hipError_t ks_tail_tab_t(const DevCtx* ctx, const MulOp* twi, int pack_ks, bool mixed, const u64* ACC, const u64* base, size_t bstride, u32 base_mask,
+                                const u64* extra, u64* out2, size_t ops, hipStream_t s, const u32* ginv_tab) {
+  if constexpr (L == 15) return hipErrorInvalidValue;
+  else return ks_tail_g<L, true>(ctx, twi, pack_ks, mixed, ACC, base, bstride, base_mask, extra, out2, ops, s, ginv_tab);
+}
+// extra: optional ciphertexts u64[ops][2][K][N] added to the result; ginv != 0: the base polynomials are read through sigma_g (launch_ks_head);
+// ginv_tab != nullptr: per item, as launch_ks_head reads it
 hipError_t launch_ks_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, int pack_ks, bool mixed, const u64* ACC, const u64* base, size_t bstride, u32 base_mask,
-                          const u64* extra, u64* out2, size_t ops, hipStream_t s, u32 ginv) {
+                          const u64* extra, u64* out2, size_t ops, hipStream_t s, u32 ginv, const u32* ginv_tab) {
+  if (ginv_tab) {
+    KS_DISPATCH(ks_tail_tab_t, ctx, twi, pack_ks, mixed, ACC, base, bstride, base_mask, extra, out2, ops, s, ginv_tab)
+  }
   KS_DISPATCH(ks_tail_t, ctx, twi, pack_ks, mixed, ACC, base, bstride, base_mask, extra, out2, ops, s, ginv)
 }
 
