@@ -362,6 +362,35 @@ long hipbfv_batch_rotate_rows_keys(void *evaluator, const uint64_t *ct2, int ste
 long hipbfv_batch_rotate_columns_keys(void *evaluator, const uint64_t *ct2, void *const *galois_key_sets,
                                       uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t count,
                                       void *stream);
+/* Mixed-step rotation batches with one key set per client: the two families above at once.  Item i is rotated by its own
+ * steps[i] (galois_elts[i]) through key set key_index[i] -- the ready queue of a multi-tenant server, as it stands, in ONE call.
+ * steps / galois_elts / key_index and the handle array are HOST arrays, read before the call returns.
+ *  - Bits: item i has exactly the words of hipbfv_batch_rotate_rows(..., steps[i], key_sets[key_index[i]], ...) called on that
+ *    item alone (apply_galois_items_keys: of hipbfv_batch_apply_galois with galois_elts[i]), whoever else is in the batch and
+ *    whatever the order of the items.
+ *  - Decisions stay per (set, step): step 0 / element 1 copies the item; a set that holds the step's direct key rotates through
+ *    it; a set without it takes the NAF chain of power-of-two keys (SEAL's rotate_internal; the part of n/2 rows is skipped).
+ *    Two clients with the same step may decide differently within one call.
+ *  - Launches: ALL items that rotate through a direct key -- every client, every step -- share one key-switch launch sequence
+ *    per chunk; its key table has one entry per (element, set) pair and is walked in that order.  All chain items of the call
+ *    are gathered once and share their rounds: round r rotates every unfinished item by the r-th part of its own chain through
+ *    its own client's key in one launch sequence, so the call runs as many rounds as its longest chain has parts
+ *    (hipbfv_debug_rotate_items_keys_plan).
+ *  - Only referenced sets count.  A set is referenced only by an item that needs a key: items that copy reference nothing, and
+ *    their set may be NULL or foreign.  key_index[i] >= num_key_sets is refused for every item, copied ones included.
+ *  - Refusals are HIPBFV_E_INVALIDARG: |step| >= N/2; an even or too large element; a referenced set that is NULL, not a key
+ *    object, of another context, or that lacks the direct key and also a key of the chain.  Every refusal comes before anything
+ *    is launched, copied or written, and hipbfv_last_error reads "item <i>: key set <k>: ..." for the first offending item, k in
+ *    the caller's numbering.
+ *  - Aliasing as above: out2 may be exactly ct2, any other overlap is refused.  Parameters without batching give
+ *    COR_E_INVALIDOPERATION for the row rotations; count == 0 returns S_OK.  Transparent results are recorded as in the sibling
+ *    calls (hipbfv_batch_status), under the caller's item numbers. */
+long hipbfv_batch_apply_galois_items_keys(void *evaluator, const uint64_t *ct2, const uint32_t *galois_elts,
+                                          void *const *galois_key_sets, uint64_t num_key_sets, const uint32_t *key_index,
+                                          uint64_t *out2, uint64_t count, void *stream);
+long hipbfv_batch_rotate_rows_items_keys(void *evaluator, const uint64_t *ct2, const int32_t *steps,
+                                         void *const *galois_key_sets, uint64_t num_key_sets, const uint32_t *key_index,
+                                         uint64_t *out2, uint64_t count, void *stream);
 long hipbfv_batch_add(void *evaluator, const uint64_t *a, const uint64_t *b, uint64_t *out, uint64_t size,
                       uint64_t count, void *stream);
 long hipbfv_batch_sub(void *evaluator, const uint64_t *a, const uint64_t *b, uint64_t *out, uint64_t size,
@@ -575,6 +604,17 @@ long hipbfv_Pool_ProgramRunKeys(void *pool, void *program, uint64_t batch, uint6
                                 void *const *relin_keys, void *const *galois_keys, const uint32_t *key_index,
                                 uint64_t num_outputs, uint64_t *const *outputs);
 long hipbfv_Pool_SetKeyCacheBytes(void *pool, uint64_t bytes);
+/* hipbfv_batch_rotate_rows_items_keys through the pool: input set i by steps[i] with key set key_index[i] (HOST data pointers and
+ * host arrays, no evaluator, no stream).  Input set i has exactly the words of the one-device call -- hence of
+ * hipbfv_batch_rotate_rows on that set alone with its client's keys -- whatever the member count, the chunk size, the order of the
+ * clients, the kind of host memory and the key-cache bound.  steps and key_index are sliced with the input sets.  Every refusal
+ * of the one-device call (same text: "item <i>: key set <k>: ...", i the index in the whole batch, k in the caller's array; "of
+ * another context" reads "other encryption parameters" here) is decided on the calling thread over the whole batch before any
+ * member copies a key or launches anything.  A member copies, per chunk, only the Galois keys the chunk's own (set, step) pairs
+ * read: the direct key, or the chain's.  The key-cache bound, eviction, transparent results (the message names the batch-wide
+ * index), aliasing, failures and serialisation are those of the calls above. */
+long hipbfv_Pool_RotateRowsItemsKeys(void *pool, const uint64_t *ct2, const int32_t *steps, void *const *galois_key_sets,
+                                     uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t count);
 /* the pool's shard rule, host only: member `member` of `members` gets input sets [*begin, *end) of a batch */
 long hipbfv_debug_pool_shard(uint64_t batch, uint32_t members, uint32_t member, uint64_t *begin, uint64_t *end);
 /* the pool's per-chunk key table, host only: for chunk `chunk_no` of member `member`'s shard (`chunk` input sets per chunk, at
@@ -590,6 +630,15 @@ long hipbfv_debug_pool_keyplan(const uint32_t *key_index, uint64_t batch, uint64
  * call would (a refused step, a missing key; the message names the item). */
 long hipbfv_debug_rotate_items_plan(uint64_t n, const int32_t *steps, uint64_t count, const uint32_t *present_elts,
                                     uint64_t num_present, int32_t *kind, uint32_t *group, uint64_t *chain_groups);
+/* Host only: what hipbfv_batch_rotate_rows_items_keys does with (steps, key_index) at degree n where key set k holds exactly the
+ * keys of the elements present_elts[present_offsets[k], present_offsets[k + 1]) (num_key_sets + 1 offsets).  kind[i]: 0 the item
+ * is copied, 1 it goes into the mixed launch through entry table_entry[i] of its key table (*table_entries entries, numbered by
+ * (element, set)), 2 it runs a NAF chain of chain_rounds_of_item[i] rounds (0 for the other kinds).  *rounds: the rounds the call
+ * runs, the longest chain's.  Fails as the call would; the message names the item and the set. */
+long hipbfv_debug_rotate_items_keys_plan(uint64_t n, const int32_t *steps, const uint32_t *key_index, uint64_t count,
+                                         uint64_t num_key_sets, const uint32_t *present_elts, const uint64_t *present_offsets,
+                                         int32_t *kind, uint32_t *table_entry, uint32_t *chain_rounds_of_item,
+                                         uint64_t *table_entries, uint64_t *rounds);
 
 /* Per-kernel timing (HIP events recorded on the launch stream, around every kernel launch):
  * total milliseconds, number of launches and work units (residue polynomials for the NTT kernels,

@@ -646,6 +646,22 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
   void rotate_rows_items(const uint64_t* ct, const std::vector<int32_t>& steps, const GaloisKeys& gk, uint64_t* out, void* stream = nullptr) const {
     check(hipbfv_batch_rotate_rows_items(h_, ct, steps.data(), gk.get_handle(), out, steps.size(), stream));
   }
+  // ... with one key set per client: item i by its own element / step through keys[key_index[i]].  An entry of `keys` that no rotating
+  // item names may be nullptr.
+  void apply_galois_items_keys(const uint64_t* ct, const std::vector<uint32_t>& galois_elts, const std::vector<const GaloisKeys*>& keys,
+                               const std::vector<uint32_t>& key_index, uint64_t* out, void* stream = nullptr) const {
+    std::vector<void*> hs;
+    for (const GaloisKeys* k : keys) hs.push_back(k ? k->get_handle() : nullptr);
+    if (galois_elts.size() != key_index.size()) throw std::invalid_argument("one Galois element and one key index per item");
+    check(hipbfv_batch_apply_galois_items_keys(h_, ct, galois_elts.data(), hs.data(), hs.size(), key_index.data(), out, key_index.size(), stream));
+  }
+  void rotate_rows_items_keys(const uint64_t* ct, const std::vector<int32_t>& steps, const std::vector<const GaloisKeys*>& keys,
+                              const std::vector<uint32_t>& key_index, uint64_t* out, void* stream = nullptr) const {
+    std::vector<void*> hs;
+    for (const GaloisKeys* k : keys) hs.push_back(k ? k->get_handle() : nullptr);
+    if (steps.size() != key_index.size()) throw std::invalid_argument("one step and one key index per item");
+    check(hipbfv_batch_rotate_rows_items_keys(h_, ct, steps.data(), hs.data(), hs.size(), key_index.data(), out, key_index.size(), stream));
+  }
 };
 
 // The device pool (hipbfv.h, "Device pool"): host-resident batches u64[count][2][K][N] sharded over several GPUs, every input
@@ -684,6 +700,13 @@ class DevicePool : public detail::Handle<hipbfv_Pool_Destroy, detail::no_copy> {
                            uint64_t* out) const {
     const std::vector<void*> hs = handles(keys);
     check(hipbfv_Pool_RotateColumnsKeys(h_, ct, hs.data(), hs.size(), key_index.data(), out, key_index.size()));
+  }
+  // input set i by steps[i] with keys[key_index[i]] (hipbfv_Pool_RotateRowsItemsKeys)
+  void rotate_rows_items_keys(const uint64_t* ct, const std::vector<int32_t>& steps, const std::vector<const GaloisKeys*>& keys,
+                              const std::vector<uint32_t>& key_index, uint64_t* out) const {
+    const std::vector<void*> hs = handles(keys);
+    if (steps.size() != key_index.size()) throw std::invalid_argument("one step and one key index per input set");
+    check(hipbfv_Pool_RotateRowsItemsKeys(h_, ct, steps.data(), hs.data(), hs.size(), key_index.data(), out, key_index.size()));
   }
   // a rotation batch with one shared key set
   void rotate_rows(const uint64_t* ct, int steps, const GaloisKeys& gk, uint64_t* out, uint64_t count) const {

@@ -138,6 +138,26 @@ impl<'e> BatchEvaluator<'e> {
             bindgen::hipbfv_batch_rotate_columns_keys(self.h(), a.ptr, handles.as_ptr(), handles.len() as u64, key_index.as_ptr(), out.ptr, a.count, self.stream)
         })
     }
+    // ---- mixed-step rotation batches with one key set per client: item i by its own element / step through `keys[key_index[i]]`;
+    // an entry of `keys` that no rotating item names may be `None` ----
+    pub fn apply_galois_items_keys(&self, a: DeviceBatch, galois_elts: &[u32], keys: &[Option<&GaloisKeys>], key_index: &[u32], out: DeviceBatch) -> Result<()> {
+        same_count(&a, &out)?;
+        Self::per_item_ok(galois_elts.len(), a.count, "Galois elements")?;
+        Self::key_index_ok(key_index, keys.len(), a.count)?;
+        let handles: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(std::ptr::null_mut(), |k| k.get_handle())).collect();
+        check(unsafe {
+            bindgen::hipbfv_batch_apply_galois_items_keys(self.h(), a.ptr, galois_elts.as_ptr(), handles.as_ptr(), handles.len() as u64, key_index.as_ptr(), out.ptr, a.count, self.stream)
+        })
+    }
+    pub fn rotate_rows_items_keys(&self, a: DeviceBatch, steps: &[i32], keys: &[Option<&GaloisKeys>], key_index: &[u32], out: DeviceBatch) -> Result<()> {
+        same_count(&a, &out)?;
+        Self::per_item_ok(steps.len(), a.count, "steps")?;
+        Self::key_index_ok(key_index, keys.len(), a.count)?;
+        let handles: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(std::ptr::null_mut(), |k| k.get_handle())).collect();
+        check(unsafe {
+            bindgen::hipbfv_batch_rotate_rows_items_keys(self.h(), a.ptr, steps.as_ptr(), handles.as_ptr(), handles.len() as u64, key_index.as_ptr(), out.ptr, a.count, self.stream)
+        })
+    }
     pub fn add(&self, a: DeviceBatch, b: DeviceBatch, out: DeviceBatch) -> Result<()> {
         same_count(&a, &b)?;
         same_count(&a, &out)?;

@@ -104,6 +104,19 @@ impl DevicePool {
         })
     }
 
+    /// Input set `i` rotated by `steps[i]` with `keys[key_index[i]]`: every (set, step) pair decides between the direct key and the
+    /// NAF chain on its own, all in one call.
+    pub fn rotate_rows_items_keys(&self, ct: &[u64], steps: &[i32], keys: &[Option<&GaloisKeys>], key_index: &[u32], out: &mut [u64]) -> Result<()> {
+        let count = self.count_of(key_index, &[ct.len(), out.len()])?;
+        if steps.len() as u64 != count {
+            return Err(crate::Error::InvalidArgument(format!("{} steps for {} input sets", steps.len(), count)));
+        }
+        let hs: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(null_mut(), |k| k.get_handle())).collect();
+        check(unsafe {
+            bindgen::hipbfv_Pool_RotateRowsItemsKeys(self.handle, ct.as_ptr(), steps.as_ptr(), hs.as_ptr(), hs.len() as u64, key_index.as_ptr(), out.as_mut_ptr(), count)
+        })
+    }
+
     pub fn rotate_columns_keys(&self, ct: &[u64], keys: &[Option<&GaloisKeys>], key_index: &[u32], out: &mut [u64]) -> Result<()> {
         let count = self.count_of(key_index, &[ct.len(), out.len()])?;
         let hs: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(null_mut(), |k| k.get_handle())).collect();

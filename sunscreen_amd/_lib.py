@@ -214,6 +214,11 @@ _SIGNATURES = {
     "hipbfv_debug_pool_shard": [u64, C.c_uint32, C.c_uint32, u64p, u64p],
     "hipbfv_debug_pool_keyplan": [C.POINTER(C.c_uint32), u64, u64, C.c_uint32, C.c_uint32, u64, u64, C.POINTER(C.c_uint32), u64p,
                                   C.POINTER(C.c_uint32), u64p],
+    "hipbfv_batch_apply_galois_items_keys": [vp, vp, C.POINTER(C.c_uint32), vpp, u64, C.POINTER(C.c_uint32), vp, u64, vp],
+    "hipbfv_batch_rotate_rows_items_keys": [vp, vp, C.POINTER(C.c_int32), vpp, u64, C.POINTER(C.c_uint32), vp, u64, vp],
+    "hipbfv_Pool_RotateRowsItemsKeys": [vp, vp, C.POINTER(C.c_int32), vpp, u64, C.POINTER(C.c_uint32), vp, u64],
+    "hipbfv_debug_rotate_items_keys_plan": [u64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), u64, u64, C.POINTER(C.c_uint32), u64p,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64p, u64p],
     "hipbfv_debug_rotate_items_plan": [u64, C.POINTER(C.c_int32), u64, C.POINTER(C.c_uint32), u64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), u64p],
     "hipbfv_profile_enable": [vp, C.c_bool],
     "hipbfv_profile_reset": [vp],

@@ -204,6 +204,33 @@ class BatchEvaluator:
         _check(_lib.load().hipbfv_batch_rotate_columns_keys(self._h, _ptr(ct), hs, n, ip, _ptr(out), ct.shape[0], _stream()))
         return out
 
+    # ---- mixed-step rotation batches with one key set per client (include/hipbfv.h) ----
+    def apply_galois_items_keys(self, ct: torch.Tensor, galois_elts, key_sets: Sequence[GaloisKeys | None], key_index,
+                                out: torch.Tensor | None = None) -> torch.Tensor:
+        """Item i by galois_elts[i] through key_sets[key_index[i]].  An item of element 1 is copied and references no set."""
+        self._shape_ok(ct, 2)
+        out = out if out is not None else self._new(ct.shape[0], 2, ct)
+        elts = np.ascontiguousarray(np.asarray(galois_elts, dtype=np.uint32))
+        assert elts.shape == (ct.shape[0],), (elts.shape, ct.shape[0])
+        hs, n, ip, _keep = self._key_sets(key_sets, key_index, ct.shape[0])
+        _check(_lib.load().hipbfv_batch_apply_galois_items_keys(self._h, _ptr(ct), elts.ctypes.data_as(C.POINTER(C.c_uint32)), hs, n, ip, _ptr(out),
+                                                                ct.shape[0], _stream()))
+        return out
+
+    def rotate_rows_items_keys(self, ct: torch.Tensor, steps, key_sets: Sequence[GaloisKeys | None], key_index,
+                               out: torch.Tensor | None = None) -> torch.Tensor:
+        """Item i rotated by steps[i] with key_sets[key_index[i]]: the bits of rotate_rows(ct[i:i+1], steps[i], that set).  Every
+        (set, step) pair decides on its own between a copy, the direct key and the NAF chain; all direct items share one launch
+        sequence, all chain items share their rounds."""
+        self._shape_ok(ct, 2)
+        out = out if out is not None else self._new(ct.shape[0], 2, ct)
+        st = np.ascontiguousarray(np.asarray(steps, dtype=np.int32))
+        assert st.shape == (ct.shape[0],), (st.shape, ct.shape[0])
+        hs, n, ip, _keep = self._key_sets(key_sets, key_index, ct.shape[0])
+        _check(_lib.load().hipbfv_batch_rotate_rows_items_keys(self._h, _ptr(ct), st.ctypes.data_as(C.POINTER(C.c_int32)), hs, n, ip, _ptr(out),
+                                                               ct.shape[0], _stream()))
+        return out
+
     # ---- a5 ----
     def add(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         self._shape_ok(a)
@@ -359,3 +386,25 @@ def rotate_items_plan(n: int, steps, present_elts) -> tuple[list[int], list[int]
     _check(_lib.load().hipbfv_debug_rotate_items_plan(n, st.ctypes.data_as(C.POINTER(C.c_int32)), st.size, pe.ctypes.data_as(C.POINTER(C.c_uint32)), pe.size,
                                                       kind, group, C.byref(ng)))
     return list(kind[: st.size]), list(group[: st.size]), ng.value
+
+
+def rotate_items_keys_plan(n: int, steps, key_index, present_sets) -> tuple[list[int], list[int], list[int], int, int]:
+    """The library's plan for rotate_rows_items_keys (host only) at degree n, where key set k holds exactly the keys of the Galois
+    elements present_sets[k]: per item its kind (0 copied, 1 in the mixed launch, 2 in a NAF chain), its entry of the mixed
+    launch's key table (kind 1; entries are numbered by (element, set)) and its chain's rounds (kind 2); then the number of
+    table entries and the rounds the call runs (the longest chain's)."""
+    st = np.ascontiguousarray(np.asarray(steps, dtype=np.int32))
+    ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint32))
+    assert st.shape == ki.shape and st.ndim == 1, (st.shape, ki.shape)
+    offsets = np.zeros(len(present_sets) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(p) for p in present_sets])
+    pe = np.ascontiguousarray(np.asarray([e for p in present_sets for e in p], dtype=np.uint32))
+    kind = (C.c_int32 * max(1, st.size))()
+    entry = (C.c_uint32 * max(1, st.size))()
+    rounds_of = (C.c_uint32 * max(1, st.size))()
+    entries, rounds = C.c_uint64(), C.c_uint64()
+    _check(_lib.load().hipbfv_debug_rotate_items_keys_plan(n, st.ctypes.data_as(C.POINTER(C.c_int32)), ki.ctypes.data_as(C.POINTER(C.c_uint32)), st.size,
+                                                           len(present_sets), pe.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                           offsets.ctypes.data_as(C.POINTER(C.c_uint64)), kind, entry, rounds_of, C.byref(entries),
+                                                           C.byref(rounds)))
+    return list(kind[: st.size]), list(entry[: st.size]), list(rounds_of[: st.size]), entries.value, rounds.value

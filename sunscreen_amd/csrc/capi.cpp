@@ -2131,6 +2131,190 @@ long hipbfv_debug_rotate_items_plan(uint64_t n, const int32_t* steps, uint64_t c
   return HIPBFV_S_OK;
 HIPBFV_END
 
+// ---- mixed-step rotation batches with one key set per client (include/hipbfv.h) ----
+// What hipbfv_batch_rotate_rows_items_keys / hipbfv_batch_apply_galois_items_keys do with every item, decided once per distinct
+// (key set, step) pair as hipbfv_batch_rotate_rows decides for a whole batch over that set: step 0 / element 1 copies (the set is
+// not looked at); a set that holds the step's direct key rotates through it -- ALL such items of the call, whatever their client
+// and step, share one launch sequence whose key table has one entry per (element, set) pair, numbered in that order; a set
+// without it takes the NAF chain, and all chain items of the call share their rounds (Evaluator::apply_galois_rounds).  Host only
+// (hipbfv_debug_rotate_items_keys_plan shows it).
+struct ItemsKeysPlan {
+  static constexpr uint32_t kNone = 0xFFFFFFFFu;
+  struct Decision {
+    uint32_t set;
+    int32_t kind;                 // RotateItemsPlan::kDirect or kChain
+    uint32_t elt;                 // the step's own Galois element
+    std::vector<uint32_t> chain;  // kChain: the elements of the chain's parts, in order, the skipped n/2 part left out
+    uint32_t entry;               // kDirect: the entry of the mixed launch's key table
+  };
+  std::vector<Decision> dec;
+  std::vector<uint32_t> of;  // per item: its decision, kNone for a copied item
+  uint64_t entries = 0, rounds = 0;
+};
+static long item_set_error(uint64_t item, uint64_t set, const char* what) {
+  char msg[200];
+  snprintf(msg, sizeof(msg), "item %llu: key set %llu: %s", (unsigned long long)item, (unsigned long long)set, what);
+  return fail(HIPBFV_E_INVALIDARG, msg);
+}
+// steps (row rotations) or elts (Galois elements), one of the two.  usable(set): nullptr, or why the set cannot be read;
+// has(set, element): the set holds that element's key -- both asked of referenced sets only.  Fails on the first offending item.
+static long plan_items_keys(u32 n, const int32_t* steps, const uint32_t* elts, const uint32_t* key_index, uint64_t count, uint64_t num_sets,
+                            const std::function<const char*(uint32_t)>& usable, const std::function<bool(uint32_t, u32)>& has, ItemsKeysPlan* plan) {
+  plan->of.assign(count, ItemsKeysPlan::kNone);
+  std::map<std::pair<uint32_t, int64_t>, uint32_t> seen;  // (set, step or element) -> decision
+  for (uint64_t i = 0; i < count; i++) {
+    const uint32_t k = key_index[i];
+    if (k >= num_sets) return item_set_error(i, k, "key_index names a key set that was not given");
+    u32 elt;
+    int step = 0;
+    if (steps) {
+      if (!(step = steps[i])) continue;
+      if (!(elt = Evaluator::galois_elt_from_step(n, step))) return item_set_error(i, k, "step count too large");
+    } else {
+      elt = elts[i];
+      if (!(elt & 1) || elt >= 2 * n) return item_set_error(i, k, "the Galois element must be odd and below 2 N");
+      if (elt == 1) continue;
+    }
+    const std::pair<uint32_t, int64_t> what{k, steps ? (int64_t)step : (int64_t)elt};
+    auto it = seen.find(what);
+    if (it == seen.end()) {
+      if (const char* why = usable(k)) return item_set_error(i, k, why);
+      ItemsKeysPlan::Decision d{k, RotateItemsPlan::kDirect, elt, {}, 0};
+      if (!has(k, elt)) {
+        const std::vector<int> naf = steps ? naf_parts(step) : std::vector<int>();
+        bool chain = naf.size() > 1;
+        for (int part : naf) {
+          if (!chain || naf_skip(part, n)) continue;
+          const u32 e = Evaluator::galois_elt_from_step(n, part);
+          if ((chain = has(k, e))) d.chain.push_back(e);
+        }
+        if (!chain) return item_set_error(i, k, "the set does not hold the required key-switching key");
+        d.kind = RotateItemsPlan::kChain;
+        plan->rounds = std::max<uint64_t>(plan->rounds, d.chain.size());
+      }
+      it = seen.emplace(what, (uint32_t)plan->dec.size()).first;
+      plan->dec.push_back(std::move(d));
+    }
+    plan->of[i] = it->second;
+  }
+  std::map<std::pair<u32, uint32_t>, uint32_t> entry;  // (element, set): the table's order
+  for (const auto& d : plan->dec)
+    if (d.kind == RotateItemsPlan::kDirect) entry.emplace(std::make_pair(d.elt, d.set), 0u);
+  for (auto& kv : entry) kv.second = (uint32_t)plan->entries++;
+  for (auto& d : plan->dec)
+    if (d.kind == RotateItemsPlan::kDirect) d.entry = entry[{d.elt, d.set}];
+  return HIPBFV_S_OK;
+}
+
+// why the evaluator cannot read a key set handle (nullptr: it can)
+static const char* keyset_unusable(void* handle, EvalObj* e) {
+  if (!handle) return "the set is NULL";
+  KeysObj* k = as<KeysObj>(handle, kMagicKeys);
+  if (!k) return "the handle is not a key object";
+  if (k->ctx.get() != e->ctx.get()) return "the set belongs to another context";
+  return nullptr;
+}
+
+// Both entry points past their argument checks (count != 0): plan, then launch.  watch: the status word the results are noted in
+// (nullptr: not noted), in the caller's item numbering.
+static long batch_items_keys_impl(EvalObj* e, const u64* ct2, const int32_t* steps, const uint32_t* elts, void* const* key_sets, uint64_t num_sets,
+                                  const uint32_t* key_index, u64* out2, uint64_t count, hipStream_t s, u32* watch) {
+  ItemsKeysPlan plan;
+  if (long hr = plan_items_keys(e->ctx->n(), steps, elts, key_index, count, num_sets, [&](uint32_t k) { return keyset_unusable(key_sets[k], e); },
+                                [&](uint32_t k, u32 elt) { return key_or_null(key_sets[k], e, (elt - 1) >> 1) != nullptr; }, &plan))
+    return hr;
+  // copies and direct keys: one pass over the caller's buffers, the chain items left out of it
+  std::vector<u32> pass(count, 1u);
+  std::vector<const u64*> key(count, nullptr);
+  std::vector<u64> chain_items;
+  std::vector<const u64*> dkey(plan.dec.size(), nullptr);
+  for (size_t d = 0; d < plan.dec.size(); d++)
+    if (plan.dec[d].kind == RotateItemsPlan::kDirect) dkey[d] = key_or_null(key_sets[plan.dec[d].set], e, (plan.dec[d].elt - 1) >> 1);
+  for (uint64_t i = 0; i < count; i++) {
+    if (plan.of[i] == ItemsKeysPlan::kNone) continue;
+    const ItemsKeysPlan::Decision& d = plan.dec[plan.of[i]];
+    pass[i] = d.kind == RotateItemsPlan::kDirect ? d.elt : 0u;
+    key[i] = dkey[plan.of[i]];
+    if (d.kind == RotateItemsPlan::kChain) chain_items.push_back(i);
+  }
+  WatchScope quiet(nullptr);  // (the chain rounds count their own items: the results are noted once, when all are in place)
+  if (int rc = e->ev->apply_galois_items_keyed(ct2, pass.data(), key.data(), key_index, out2, count, s, false)) return from_status(rc);
+  if (const size_t c = chain_items.size()) {
+    const size_t rounds = (size_t)plan.rounds;
+    std::vector<u32> relt(rounds * c, 0u), ids(c);
+    std::vector<const u64*> rkey(rounds * c, nullptr);
+    std::map<std::pair<uint32_t, u32>, const u64*> found;  // (set, element) -> key: one look-up per pair
+    for (size_t j = 0; j < c; j++) {
+      const ItemsKeysPlan::Decision& d = plan.dec[plan.of[chain_items[j]]];
+      ids[j] = d.set;
+      for (size_t r = 0; r < d.chain.size(); r++) {
+        auto it = found.find({d.set, d.chain[r]});
+        if (it == found.end()) it = found.emplace(std::make_pair(d.set, d.chain[r]), key_or_null(key_sets[d.set], e, (d.chain[r] - 1) >> 1)).first;
+        relt[r * c + j] = d.chain[r];
+        rkey[r * c + j] = it->second;
+      }
+    }
+    if (int rc = e->ev->apply_galois_rounds(ct2, out2, chain_items.data(), c, (u32)rounds, relt.data(), rkey.data(), ids.data(), s)) return from_status(rc);
+  }
+  if (!watch) return HIPBFV_S_OK;
+  WatchScope noted(watch);
+  return from_status(e->ev->note_result(out2, 2, e->ctx->K(), count, s));
+}
+
+#define ITEMS_KEYS_ARGS_OR_RETURN(per_item)                                                            \
+  EVAL_OR_RETURN(h);                                                                                   \
+  if (!ct2 || !out2 || (!(per_item) && count)) return HIPBFV_E_POINTER;                                \
+  if (!key_sets || (!key_index && count) || !num_sets || num_sets > 0xFFFFFFFFull) return HIPBFV_E_POINTER;
+
+long hipbfv_batch_apply_galois_items_keys(void* h, const uint64_t* ct2, const uint32_t* elts, void* const* key_sets, uint64_t num_sets,
+                                          const uint32_t* key_index, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
+  ITEMS_KEYS_ARGS_OR_RETURN(elts);
+  ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct2, e->ctx->ct_words(2), count)});
+  if (!count) return HIPBFV_S_OK;
+  return batch_items_keys_impl(e, (const u64*)ct2, nullptr, elts, key_sets, num_sets, key_index, (u64*)out2, count, (hipStream_t)stream,
+                               Evaluator::watch_status());
+HIPBFV_END
+
+long hipbfv_batch_rotate_rows_items_keys(void* h, const uint64_t* ct2, const int32_t* steps, void* const* key_sets, uint64_t num_sets,
+                                         const uint32_t* key_index, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
+  ITEMS_KEYS_ARGS_OR_RETURN(steps);
+  if (!e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
+  ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct2, e->ctx->ct_words(2), count)});
+  if (!count) return HIPBFV_S_OK;
+  return batch_items_keys_impl(e, (const u64*)ct2, steps, nullptr, key_sets, num_sets, key_index, (u64*)out2, count, (hipStream_t)stream,
+                               Evaluator::watch_status());
+HIPBFV_END
+
+// The plan of hipbfv_batch_rotate_rows_items_keys at degree n where key set k holds exactly the keys of
+// present_elts[present_offsets[k], present_offsets[k + 1]).  Host only.
+long hipbfv_debug_rotate_items_keys_plan(uint64_t n, const int32_t* steps, const uint32_t* key_index, uint64_t count, uint64_t num_sets,
+                                         const uint32_t* present_elts, const uint64_t* present_offsets, int32_t* kind, uint32_t* table_entry,
+                                         uint32_t* chain_rounds_of_item, uint64_t* table_entries, uint64_t* rounds) HIPBFV_BEGIN
+  if ((!steps || !key_index || !kind || !table_entry || !chain_rounds_of_item) && count) return HIPBFV_E_POINTER;
+  if (!present_offsets || !table_entries || !rounds || !num_sets || num_sets > 0xFFFFFFFFull) return HIPBFV_E_POINTER;
+  if (!present_elts && present_offsets[num_sets]) return HIPBFV_E_POINTER;
+  if (n < 4 || n > (1u << 20) || (n & (n - 1))) return fail(HIPBFV_E_INVALIDARG, "the degree must be a power of two");
+  for (uint64_t k = 0; k < num_sets; k++)
+    if (present_offsets[k] > present_offsets[k + 1]) return fail(HIPBFV_E_INVALIDARG, "present_offsets must not decrease");
+  ItemsKeysPlan plan;
+  if (long hr = plan_items_keys((u32)n, steps, nullptr, key_index, count, num_sets, [](uint32_t) -> const char* { return nullptr; },
+                                [&](uint32_t k, u32 elt) {
+                                  const uint32_t *b = present_elts + present_offsets[k], *e = present_elts + present_offsets[k + 1];
+                                  return std::find(b, e, elt) != e;
+                                },
+                                &plan))
+    return hr;
+  for (uint64_t i = 0; i < count; i++) {
+    const ItemsKeysPlan::Decision* d = plan.of[i] == ItemsKeysPlan::kNone ? nullptr : &plan.dec[plan.of[i]];
+    kind[i] = d ? d->kind : (int32_t)RotateItemsPlan::kCopy;
+    table_entry[i] = d && d->kind == RotateItemsPlan::kDirect ? d->entry : 0u;
+    chain_rounds_of_item[i] = d ? (uint32_t)d->chain.size() : 0u;
+  }
+  *table_entries = plan.entries;
+  *rounds = plan.rounds;
+  return HIPBFV_S_OK;
+HIPBFV_END
+
 long hipbfv_batch_add(void* h, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t size, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);
   if (!a || !b || !out) return HIPBFV_E_POINTER;
@@ -4273,6 +4457,83 @@ HIPBFV_END
 long hipbfv_Pool_RotateColumnsKeys(void* pool, const uint64_t* ct2, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index, uint64_t* out2,
                                    uint64_t count) HIPBFV_BEGIN
   return pool_rotate_keys("hipbfv_Pool_RotateColumnsKeys", pool, ct2, 0, true, key_sets, num_sets, key_index, out2, count);
+HIPBFV_END
+
+// Mixed-step rotation batches through the pool: item i by steps[i] with key set key_index[i].  The calling thread plans the whole
+// batch (every refusal is decided here, before any member copies or launches anything) and lists, per (set, step) decision, the key
+// buffers it reads: the direct key, or the chain's.  A member stages, per chunk, what the chunk's own decisions read and runs the
+// one-device call over the chunk's handle table.
+long hipbfv_Pool_RotateRowsItemsKeys(void* pool, const uint64_t* ct2, const int32_t* steps, void* const* key_sets, uint64_t num_sets,
+                                     const uint32_t* key_index, uint64_t* out2, uint64_t count) HIPBFV_BEGIN
+  PoolObj* p = as<PoolObj>(pool, kMagicPool);
+  if (!p) return HIPBFV_E_POINTER;
+  if (count && (!ct2 || !out2 || !steps || !key_index)) return HIPBFV_E_POINTER;
+  if (!key_sets || !num_sets || num_sets > 0xFFFFFFFFull) return HIPBFV_E_POINTER;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (!p->members[0]->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
+  const size_t w = p->ct_words();
+  ALIAS_OR_RETURN(cts(out2, w, count), {cts(ct2, w, count)});
+  ItemsKeysPlan plan;
+  if (long hr = plan_items_keys(p->n, steps, nullptr, key_index, count, num_sets,
+                                [&](uint32_t k) -> const char* {
+                                  if (!key_sets[k]) return "the set is NULL";
+                                  if (!as<KeysObj>(key_sets[k], kMagicKeys)) return "the handle is not a key object";
+                                  return pool_keyset(*p, key_sets[k]) ? nullptr : "the set has other encryption parameters";
+                                },
+                                [&](uint32_t k, u32 elt) {
+                                  PoolKey key;
+                                  return pool_key_of(pool_keyset(*p, key_sets[k]), (elt - 1) >> 1, &key);
+                                },
+                                &plan))
+    return hr;
+  if (!count) return HIPBFV_S_OK;
+  std::vector<std::vector<PoolKey>> reads(plan.dec.size());  // per decision: the key buffers it reads
+  for (size_t d = 0; d < plan.dec.size(); d++) {
+    const ItemsKeysPlan::Decision& dec = plan.dec[d];
+    KeysObj* gk = pool_keyset(*p, key_sets[dec.set]);
+    PoolKey key;
+    if (dec.kind == RotateItemsPlan::kDirect) {
+      if (pool_key_of(gk, (dec.elt - 1) >> 1, &key)) reads[d].push_back(key);
+    } else {
+      for (u32 elt : dec.chain)
+        if (pool_key_of(gk, (elt - 1) >> 1, &key)) reads[d].push_back(key);
+    }
+  }
+  const size_t bytes = count * w * sizeof(u64);
+  bool pi, po;
+  if (!pool_host_operand(ct2, bytes, &pi) || !pool_host_operand(out2, bytes, &po))
+    return fail(HIPBFV_E_INVALIDARG, "hipbfv_Pool_RotateRowsItemsKeys takes host memory (device pointers are not accepted)");
+  const std::vector<PoolIn> ins = {{(const u64*)ct2, w, w, pi}};
+  const std::vector<PoolOut> outs = {{(u64*)out2, w, po}};
+  const u64 chunk = p->chunk_sets(), bound = p->key_cache_bytes;
+  const bool watch = g_throw_transparent;
+  return pool_dispatch(*p, count, [&](PoolMember& m, u64 lo, u64 hi) -> long {
+    const u64 sets = std::min<u64>(chunk, hi - lo);
+    const u64 nch = (hi - lo + sets - 1) / sets;
+    if (watch)  // one watch word per chunk, in the chunk's item numbering
+      if (long hr = member_watch_begin(m, nch)) return hr;
+    PoolChunkKeys ck;
+    PoolSetKeys mine;  // what THIS chunk's (set, step) pairs read, per caller's set
+    mine.relin.assign(num_sets, {});
+    mine.galois.assign(num_sets, {});
+    long hr = member_run(m, ins, outs, lo, hi, sets, [&](u64 j, const std::vector<const u64*>& in, const std::vector<u64*>& o, u64 c, u64 first) -> long {
+      for (auto& v : mine.galois) v.clear();
+      for (u64 i = first; i < first + c; i++) {
+        if (plan.of[i] == ItemsKeysPlan::kNone) continue;
+        std::vector<PoolKey>& have = mine.galois[key_index[i]];
+        for (const PoolKey& k : reads[plan.of[i]])
+          if (std::none_of(have.begin(), have.end(), [&](const PoolKey& x) { return x.index == k.index; })) have.push_back(k);
+      }
+      if (long hr = member_chunk_keys(m, mine, key_index + first, c, bound, &ck)) return hr;
+      return batch_items_keys_impl(&m.eval, in[0], steps + first, nullptr, ck.galois.data(), ck.galois.size(), ck.index.data(), o[0], c, m.comp,
+                                   watch ? m.status + j : nullptr);
+    });
+    if (hr != HIPBFV_S_OK || !watch) return hr;
+    if (long hr2 = member_watch_read(m, nch)) return hr2;
+    for (u64 j = 0; j < nch; j++)
+      if (m.flags[j] != 0xFFFFFFFFu) return pool_transparent(lo + j * sets + m.flags[j]);
+    return HIPBFV_S_OK;
+  });
 HIPBFV_END
 
 // hipbfv_Pool_ProgramRun (key_index == nullptr: one key set, every buffer of its two handles goes to every member) and

@@ -201,6 +201,17 @@ class Evaluator {
   // (callers inside the library only: items another pass produces): the item is left out, out2[i] is not written.  Everything
   // is validated before the first launch.  watch = false: the caller notes the results itself (it fills the left-out items first).
   int apply_galois_items(const u64* ct2, const u32* elts, const u64* const* keys, u64* out2, size_t count, hipStream_t s, bool watch = true);
+  // ... with one key set per client (evaluator_client.cpp): keys[i] may differ between items of one element, the key table has one entry
+  // per (key, element) pair and the walk is ordered by (element, key).  apply_galois_items above keys its table by element alone -- its
+  // callers hand it ONE key set.  key_ids (optional, host, `count` entries): the number of item i's key set, equal for equal keys --
+  // it orders the keys of one element (without it: the order in which the key pointers first appear).
+  int apply_galois_items_keyed(const u64* ct2, const u32* elts, const u64* const* keys, const u32* key_ids, u64* out2, size_t count, hipStream_t s,
+                               bool watch = true);
+  // NAF chains in shared rounds: batch item items[j] (j < nitems) through the elements elts[r * nitems + j], r < rounds (0: the item has
+  // finished), each through keys[r * nitems + j]; one gather, one apply_galois_items_keyed call per round between two stages, the items
+  // scattered to out2 from the stage they finished in.  Host arrays; the results are not noted (the caller does).
+  int apply_galois_rounds(const u64* ct2, u64* out2, const u64* items, size_t nitems, u32 rounds, const u32* elts, const u64* const* keys,
+                          const u32* key_ids, hipStream_t s);
   int mod_switch_next(const u64* ct, u32 size, u64* out, size_t count, hipStream_t s);  // out has K-1 residues per polynomial
   int add(const u64* a, const u64* b, u64* out, u32 size, size_t count, hipStream_t s);
   int sub(const u64* a, const u64* b, u64* out, u32 size, size_t count, hipStream_t s);

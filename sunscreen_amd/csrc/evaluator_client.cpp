@@ -4,6 +4,7 @@
 // Reference interfaces: seal_fhe/src/encoder.rs:75-190 (BatchEncoder_Encode1/2, Decode1/2),
 // seal_fhe/src/encryptor_decryptor.rs:238-254 (Encryptor_Encrypt), :618-629 (Decryptor_Decrypt).
 #include <algorithm>
+#include <map>
 #include <vector>
 
 #include "evaluator.hpp"
@@ -382,6 +383,201 @@ int Evaluator::crt_compose(const u64* consts, u32 kc, const u64* in, u64* out, u
 }
 int Evaluator::crt_decompose(u32 kc, const u64* in, u64* out, u32 polys, hipStream_t s) {
   HC_CHECK(launch_crt_decompose(ctx_->dev(), ctx_->host().n, kc, in, out, polys, s));
+  return kOk;
+}
+
+// g^{-1} mod 2n (Newton iteration, g odd)
+static u32 galois_inverse_of(u32 elt, u32 n) {
+  u64 inv = 1;
+  for (int i = 0; i < 6; i++) inv = inv * (2 - (u64)elt * inv);
+  return (u32)(inv & (2 * n - 1));
+}
+
+// tables of item addresses in pinned memory the device reads directly; back to the pool behind the stream's last launch
+namespace {
+struct PinnedTables {
+  PinnedPool& pool;
+  hipStream_t s;
+  void* p;
+  ~PinnedTables() {
+    if (p) pool.release(p, s);
+  }
+};
+}  // namespace
+
+// ---- mixed-step rotation batches with one key set per client (kept apart from evaluator.cpp's single-set apply_galois_items, whose
+// callers and launch sequences stay as they are) ----
+// Item i by its own element elts[i] through its own key keys[i].  Where apply_galois would read the automorphism through the key
+// switch, ONE head / middle / tail sequence per chunk serves every element and every client: the head and the tail take item i's g^-1
+// from a device table (kernels_split.hip GinvArg), the middle kernel takes item i's key through the KeyMap -- one entry of the key table
+// per distinct (key, element) pair, the walk sorted by (element, key), so that the items that share a key share its rows in an XCD's L2
+// as the items of one client do.  Copied and left-out items stay in the grid (their workgroups leave at once): the chunk keeps the
+// caller's item numbering, no gather.  Elsewhere (in place, the whole-polynomial kernels, N outside 4096 ... 16384,
+// HIPBFV_NO_FUSED_GALOIS) the items are grouped by (key, element) and every group goes through apply_galois on a compact stage; the
+// bits are the same.  key_ids (optional): the caller's number of item i's key set -- the order of the keys of one element in the
+// table (without it: the order in which the key pointers first appear).
+int Evaluator::apply_galois_items_keyed(const u64* ct2, const u32* elts, const u64* const* keys, const u32* key_ids, u64* out2, size_t count, hipStream_t s,
+                                        bool watch) {
+  const DevCtx& h = ctx_->host();
+  const u32 n = h.n, K = h.K;
+  if (!count) return kOk;
+  if (!elts) return kInvalidArg;
+  // distinct (element > 1, key) pairs; kidx[i]: item i's entry, kKeyNone for a copied or left-out item
+  std::vector<u32> delt, kidx(count, kKeyNone);
+  std::vector<const u64*> dkey;
+  {
+    std::map<const u64*, u32> seen_key;                // key pointer -> id, where the caller numbers no sets
+    std::map<std::pair<u32, u32>, u32> entry_of;      // (element, key id) -> entry: the map's order is the walk's
+    std::vector<std::pair<u32, u32>> pair_of(count);
+    for (size_t i = 0; i < count; i++) {
+      const u32 e = elts[i];
+      if (e <= 1) continue;
+      if (!(e & 1) || e >= 2 * n) return kInvalidArg;
+      if (h.KK < 2 || !keys || !keys[i]) return kNoKey;
+      const u32 id = key_ids ? key_ids[i] : seen_key.emplace(keys[i], (u32)seen_key.size()).first->second;
+      pair_of[i] = {e, id};
+      entry_of.emplace(pair_of[i], 0u);
+    }
+    delt.resize(entry_of.size());
+    dkey.assign(entry_of.size(), nullptr);
+    u32 d = 0;
+    for (auto& kv : entry_of) kv.second = d++;
+    for (size_t i = 0; i < count; i++) {
+      if (elts[i] <= 1) continue;
+      const u32 at = entry_of[pair_of[i]];
+      kidx[i] = at;
+      delt[at] = elts[i];
+      if (!dkey[at]) dkey[at] = keys[i];
+      if (dkey[at] != keys[i]) return kInvalidArg;  // one key id, two keys
+    }
+  }
+  if (h.logn > 15) return kUnsupported;
+  const size_t rot_words = (size_t)2 * K * n;
+  if (ct2 != out2) {  // element 1: runs of neighbouring items, one copy each
+    for (size_t i = 0; i < count;) {
+      size_t r = 0;
+      while (i + r < count && elts[i + r] == 1) r++;
+      if (r) HC_CHECK(launch_copy_words(ct2 + i * rot_words, out2 + i * rot_words, r * rot_words, s));
+      i += r ? r : 1;
+    }
+  }
+  if (delt.empty()) return watch ? note_result(out2, 2, K, count, s) : (int)kOk;
+  const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, 65535 / ((size_t)h.KK * K)));
+  const size_t cc = std::min(chunk, count);
+  const size_t last = count % chunk ? count % chunk : cc;
+  const bool fused = fuse_galois_ && ct2 != out2 && h.logn >= 12 && h.logn <= 14 && ks_split_for(cc) && ks_split_for(last);
+  if (fused) {
+    std::vector<u32> ginv(count);
+    for (size_t i = 0; i < count; i++) ginv[i] = kidx[i] == kKeyNone ? kGinvSkip : galois_inverse_of(elts[i], n);
+    KeySel sel;
+    sel.keys = dkey.data();
+    sel.nkeys = (u32)dkey.size();
+    sel.index = kidx.data();
+    sel.period = count;
+    KeyMapLease kl;
+    if (int rc = stage_keymap(sel, count, chunk, s, kl, ginv.data())) return rc;
+    ScratchGuard sg(pool_, cc * ks_scratch_words() * sizeof(u64), s);
+    if (!sg.p) return kOutOfMemory;
+    for (size_t off = 0; off < count; off += chunk) {
+      const size_t c = std::min(chunk, count - off);
+      if (std::all_of(kidx.begin() + off, kidx.begin() + off + c, [](u32 k) { return k == kKeyNone; })) continue;
+      const u64* in = ct2 + off * rot_words;
+      int rc = key_switch(in + (size_t)K * n, rot_words, nullptr, in, rot_words, 1u, out2 + off * rot_words, c, (u64*)sg.p, s, nullptr, kl.at(off), 0, kl.words + off);
+      if (rc) return rc;
+    }
+    return watch ? note_result(out2, 2, K, count, s) : (int)kOk;
+  }
+  // grouped: per (key, element) pair, the group's items gathered into a compact stage, rotated by the uniform path, scattered to their places
+  // (a group that is the whole call needs no stage).  The tables of item addresses live in pinned memory the device reads directly.
+  {
+    WatchScope quiet(nullptr);  // the groups' own item numbers mean nothing to the caller: the results are noted once, below
+    if (delt.size() == 1 && std::all_of(kidx.begin(), kidx.end(), [](u32 k) { return k == 0; })) {
+      if (int rc = apply_galois(ct2, delt[0], dkey[0], out2, count, s)) return rc;
+    } else {
+      const size_t sub = std::min<size_t>(chunk_ops_, 32768);  // items per stage (and per gather / scatter grid)
+      PinnedTables tabs{pinned_, s, pinned_.acquire(2 * count * sizeof(u64*))};
+      if (!tabs.p) return kOutOfMemory;
+      const u64** src = static_cast<const u64**>(tabs.p);
+      u64** dst = static_cast<u64**>(tabs.p) + count;
+      size_t filled = 0, largest = 0;
+      std::vector<size_t> first(delt.size() + 1, 0);
+      for (size_t d = 0; d < delt.size(); d++) {
+        for (size_t i = 0; i < count; i++)
+          if (kidx[i] == d) src[filled] = ct2 + i * rot_words, dst[filled] = out2 + i * rot_words, filled++;
+        first[d + 1] = filled;
+        largest = std::max(largest, std::min(sub, filled - first[d]));
+      }
+      ScratchGuard sg(pool_, 2 * largest * rot_words * sizeof(u64), s);
+      if (!sg.p) return kOutOfMemory;
+      u64* in_stage = (u64*)sg.p;
+      u64* out_stage = in_stage + largest * rot_words;
+      for (size_t d = 0; d < delt.size(); d++) {
+        for (size_t off = first[d]; off < first[d + 1]; off += sub) {
+          const size_t c = std::min(sub, first[d + 1] - off);
+          HC_CHECK(launch_gather_items(src + off, in_stage, rot_words, c, s));
+          if (int rc = apply_galois(in_stage, delt[d], dkey[d], out_stage, c, s)) return rc;
+          HC_CHECK(launch_scatter_items(out_stage, dst + off, rot_words, c, s));
+        }
+      }
+    }
+  }
+  return watch ? note_result(out2, 2, K, count, s) : (int)kOk;
+}
+
+// NAF chains in shared rounds (mixed-step rotation batches with one key set per client): batch item items[j] goes through the
+// elements elts[r * nitems + j], r = 0 ... (0 from the round on in which it has finished), each through keys[r * nitems + j].  The
+// items are gathered ONCE into a compact stage with a twin; round r is ONE apply_galois_items_keyed call from one stage into the other
+// (out of place: the fused launch sequence serves it; finished items are left out), whatever the steps and the clients; every item
+// is scattered from the stage it finished in.  The stage lists the items that finish in the first stage (an even number of
+// rounds) ahead of the others, so that two scatter launches do.  The results are not noted: the caller does, once all are in place.
+int Evaluator::apply_galois_rounds(const u64* ct2, u64* out2, const u64* items, size_t nitems, u32 rounds, const u32* elts, const u64* const* keys,
+                                   const u32* key_ids, hipStream_t s) {
+  if (!nitems || !rounds) return kOk;
+  if (!items || !elts || !keys) return kInvalidArg;
+  const DevCtx& h = ctx_->host();
+  const size_t w = (size_t)2 * h.K * h.n;
+  const size_t sub = std::min<size_t>(chunk_ops_, 32768);  // items per stage (and per gather / scatter grid)
+  const size_t cc = std::min(sub, nitems);
+  PinnedTables tabs{pinned_, s, pinned_.acquire(2 * nitems * sizeof(u64*))};
+  if (!tabs.p) return kOutOfMemory;
+  const u64** src = static_cast<const u64**>(tabs.p);
+  u64** dst = static_cast<u64**>(tabs.p) + nitems;
+  ScratchGuard sg(pool_, 2 * cc * w * sizeof(u64), s);
+  if (!sg.p) return kOutOfMemory;
+  u64* const stage[2] = {(u64*)sg.p, (u64*)sg.p + cc * w};
+  WatchScope quiet(nullptr);
+  std::vector<u32> len(nitems), e, ids;
+  std::vector<size_t> order;
+  std::vector<const u64*> k;
+  for (size_t j = 0; j < nitems; j++)
+    while (len[j] < rounds && elts[(size_t)len[j] * nitems + j]) len[j]++;
+  for (size_t b = 0; b < nitems; b += sub) {
+    const size_t c = std::min(sub, nitems - b);
+    order.clear();
+    u32 longest = 0;
+    for (u32 parity = 0; parity < 2; parity++)
+      for (size_t j = b; j < b + c; j++)
+        if ((len[j] & 1u) == parity) order.push_back(j);
+    const size_t first_stage = std::count_if(order.begin(), order.end(), [&](size_t j) { return !(len[j] & 1u); });
+    for (size_t p = 0; p < c; p++) {
+      src[b + p] = ct2 + items[order[p]] * w;
+      dst[b + p] = out2 + items[order[p]] * w;
+      longest = std::max(longest, len[order[p]]);
+    }
+    HC_CHECK(launch_gather_items(src + b, stage[0], w, c, s));
+    e.resize(c), ids.resize(c), k.resize(c);
+    for (u32 r = 0; r < longest; r++) {
+      for (size_t p = 0; p < c; p++) {
+        const size_t at = (size_t)r * nitems + order[p];
+        e[p] = r < len[order[p]] ? elts[at] : 0u;
+        k[p] = keys[at];
+        ids[p] = key_ids ? key_ids[order[p]] : 0u;
+      }
+      if (int rc = apply_galois_items_keyed(stage[r & 1], e.data(), k.data(), key_ids ? ids.data() : nullptr, stage[(r + 1) & 1], c, s, false)) return rc;
+    }
+    if (first_stage) HC_CHECK(launch_scatter_items(stage[0], dst + b, w, first_stage, s));
+    if (c - first_stage) HC_CHECK(launch_scatter_items(stage[1] + first_stage * w, dst + b + first_stage, w, c - first_stage, s));
+  }
   return kOk;
 }
 

@@ -132,6 +132,17 @@ class DevicePool:
         _check(_lib.load().hipbfv_Pool_RotateRowsKeys(self._h, pc, int(steps), hs, n, ip, po, batch))
         return _as_u64(out)
 
+    def rotate_rows_items_keys(self, ct, steps, key_sets: Sequence[GaloisKeys | None], key_index, out=None) -> np.ndarray:
+        """Ciphertext i rotated by steps[i] with key_sets[key_index[i]] (both `batch` host integers, in any order): every (set,
+        step) pair decides on its own between a copy, the direct key and the NAF chain.  `out` may be `ct` itself."""
+        pc, batch, kc = self._one_ct(ct)
+        out, po = self._out(out, batch)
+        st = np.ascontiguousarray(np.asarray(steps, dtype=np.int32))
+        assert st.shape == (batch,), (st.shape, batch)
+        hs, n, ip, _keep = self._key_sets(key_sets, key_index, batch)
+        _check(_lib.load().hipbfv_Pool_RotateRowsItemsKeys(self._h, pc, st.ctypes.data_as(C.POINTER(C.c_int32)), hs, n, ip, po, batch))
+        return _as_u64(out)
+
     def rotate_columns_keys(self, ct, key_sets: Sequence[GaloisKeys | None], key_index, out=None) -> np.ndarray:
         pc, batch, kc = self._one_ct(ct)
         out, po = self._out(out, batch)
