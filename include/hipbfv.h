@@ -314,6 +314,12 @@ long hipbfv_batch_multiply_relin(void *evaluator, const uint64_t *a, const uint6
                                  uint64_t *out2, uint64_t count, void *stream);
 long hipbfv_batch_apply_galois(void *evaluator, const uint64_t *ct2, uint32_t galois_elt, void *galois_keys,
                                uint64_t *out2, uint64_t count, void *stream);
+/* Row rotations, here and in every other entry point that takes `steps` (Evaluator_RotateRows, the *_keys, *_items and pool
+ * forms, a program's rotation nodes), decide as SEAL's rotate_internal does: step 0 copies; the step's own Galois key when the
+ * key set holds it; otherwise the power-of-two keys of the step's non-adjacent form (NAF), least significant part first, the
+ * part of N/2 rows left out.  The whole decision is made on the host before the first launch: a refused rotation
+ * (|steps| >= N/2, or neither the step's own key nor every key of its chain) launches nothing and leaves a destination that is
+ * not the input as it was. */
 long hipbfv_batch_rotate_rows(void *evaluator, const uint64_t *ct2, int steps, void *galois_keys, uint64_t *out2,
                               uint64_t count, void *stream);
 long hipbfv_batch_rotate_columns(void *evaluator, const uint64_t *ct2, void *galois_keys, uint64_t *out2,

@@ -1613,31 +1613,6 @@ static long galois_handle(EvalObj* e, CipherObj* x, u32 elt, KeysObj* k, CipherO
   return finish_result(e, d, 2, buf, words, s, true, rq.nonzero);
 }
 
-// SEAL Evaluator::rotate_internal: use the key for `steps` if present, else the NAF decomposition
-static long rotate_internal(EvalObj* e, CipherObj* x, int steps, KeysObj* k, CipherObj* d) {
-  if (steps == 0) return HIPBFV_S_OK;
-  const u32 elt = e->ev->galois_elt_from_step(steps);
-  if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
-  if (k->find((elt - 1) >> 1)) return galois_handle(e, x, elt, k, d);
-  std::vector<int> naf;
-  {
-    const bool neg = steps < 0;
-    int v = neg ? -steps : steps;
-    for (int i = 0; v; i++) {
-      const int zi = (v & 1) ? 2 - (v & 3) : 0;
-      v = (v - zi) >> 1;
-      if (zi) naf.push_back((neg ? -zi : zi) * (1 << i));
-    }
-  }
-  if (naf.size() == 1) return fail(HIPBFV_E_INVALIDARG, "Galois key not present");
-  for (int part : naf) {
-    if ((u32)(part < 0 ? -part : part) == (e->ctx->n() >> 1)) continue;
-    long hr = rotate_internal(e, d, part, k, d);
-    if (hr != HIPBFV_S_OK) return hr;
-  }
-  return HIPBFV_S_OK;
-}
-
 static long rotate_common(void* h, void* a, bool columns, int steps, void* keys, void* dst) {
   EvalObj* e = as<EvalObj>(h, kMagicEval);
   CipherObj *x = as<CipherObj>(a, kMagicCipher), *d = as<CipherObj>(dst, kMagicCipher);
@@ -1649,9 +1624,11 @@ static long rotate_common(void* h, void* a, bool columns, int steps, void* keys,
   if (x->size != 2) return fail(HIPBFV_E_INVALIDARG, "encrypted size must be 2");
   if (k->ctx && !in_chain(k->ctx, e->ctx.get())) return fail(HIPBFV_E_INVALIDARG, "galois_keys is not valid for encryption parameters");
   if (columns) return galois_handle(e, x, 2 * e->ctx->n() - 1, k, d);
-  // a refused step leaves the destination as it was: checked before the destination takes the copy
-  if (steps && !e->ev->galois_elt_from_step(steps)) return fail(HIPBFV_E_INVALIDARG, "step count too large");
-  if (d != x) {  // work on a copy in the destination so that the NAF chain can run in place
+  // SEAL Evaluator::rotate_internal, planned before the destination takes the copy: a refused rotation leaves it as it was
+  const RowRotation r = plan_row_rotation(e->ctx->n(), steps, [&](u32 elt) { return k->find((elt - 1) >> 1) != nullptr; });
+  if (r.kind == RowRotation::kTooLarge) return fail(HIPBFV_E_INVALIDARG, "step count too large");
+  if (r.kind == RowRotation::kNoKey) return fail(HIPBFV_E_INVALIDARG, "Galois key not present");
+  if (d != x) {  // work on a copy in the destination so that the hops can run in place
     u64* buf = g_buffers.get(x->words);
     if (!buf) return from_status(kOutOfMemory);
     if (copy_d2d(buf, x->dev, x->words * sizeof(u64)) != hipSuccess) {
@@ -1660,7 +1637,7 @@ static long rotate_common(void* h, void* a, bool columns, int steps, void* keys,
     }
     d->adopt(x->ctx, 2, buf, x->words);
   }
-  return rotate_internal(e, d, steps, k, d);
+  return run_row_rotation(r, d, d, [&](u32 elt, CipherObj* cur, CipherObj* out) { return galois_handle(e, cur, elt, k, out); });
 }
 
 long Evaluator_RotateRows(void* h, void* a, int steps, void* keys, void* dst, void* pool) HIPBFV_BEGIN
@@ -1748,30 +1725,11 @@ long hipbfv_batch_apply_galois(void* h, const uint64_t* ct2, uint32_t elt, void*
   return from_status(e->ev->apply_galois((const u64*)ct2, elt, key, (u64*)out2, count, (hipStream_t)stream));
 HIPBFV_END
 
-// all items rotate by the same step (each Galois key is streamed once per batch); NAF chain like SEAL
-static long batch_rotate_internal(EvalObj* e, const u64* in, int steps, void* keys, u64* out, uint64_t count, hipStream_t s) {
-  if (steps == 0) return HIPBFV_S_OK;
-  const u32 elt = e->ev->galois_elt_from_step(steps);
-  if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
-  if (const u64* key = key_or_null(keys, e, (elt - 1) >> 1))
-    return from_status(e->ev->apply_galois(in, elt, key, out, count, s));
-  std::vector<int> naf;
-  const bool neg = steps < 0;
-  int v = neg ? -steps : steps;
-  for (int i = 0; v; i++) {
-    const int zi = (v & 1) ? 2 - (v & 3) : 0;
-    v = (v - zi) >> 1;
-    if (zi) naf.push_back((neg ? -zi : zi) * (1 << i));
-  }
-  if (naf.size() == 1) return from_status(kNoKey);
-  const u64* cur = in;
-  for (int part : naf) {
-    if ((u32)(part < 0 ? -part : part) == (e->ctx->n() >> 1)) continue;
-    long hr = batch_rotate_internal(e, cur, part, keys, out, count, s);
-    if (hr != HIPBFV_S_OK) return hr;
-    cur = out;
-  }
-  return HIPBFV_S_OK;
+// all items rotate by the same step (each Galois key is streamed once per hop): the launches of an accepted plan over `keys`
+static long batch_rotate_planned(EvalObj* e, const RowRotation& r, const u64* in, void* keys, u64* out, uint64_t count, hipStream_t s) {
+  return run_row_rotation(r, in, out, [&](u32 elt, const u64* cur, u64* o) {
+    return from_status(e->ev->apply_galois(cur, elt, key_or_null(keys, e, (elt - 1) >> 1), o, count, s));
+  });
 }
 
 long hipbfv_batch_rotate_rows(void* h, const uint64_t* ct2, int steps, void* keys, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
@@ -1780,13 +1738,16 @@ long hipbfv_batch_rotate_rows(void* h, const uint64_t* ct2, int steps, void* key
   if (!e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
   ALIAS_OR_RETURN(cts(out2, e->ctx->ct_words(2), count), {cts(ct2, e->ctx->ct_words(2), count)});
   hipStream_t s = (hipStream_t)stream;
-  if (steps == 0) {
+  const RowRotation r = plan_row_rotation(e->ctx->n(), steps, [&](u32 elt) { return key_or_null(keys, e, (elt - 1) >> 1) != nullptr; });
+  if (r.kind == RowRotation::kTooLarge) return fail(HIPBFV_E_INVALIDARG, "step count too large");
+  if (r.kind == RowRotation::kNoKey) return from_status(kNoKey);
+  if (r.kind == RowRotation::kCopy) {
     if ((const u64*)ct2 != (u64*)out2 &&
         hipMemcpyAsync(out2, ct2, count * e->ctx->ct_words(2) * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess)
       return from_status(kHipError);
     return HIPBFV_S_OK;
   }
-  return batch_rotate_internal(e, (const u64*)ct2, steps, keys, (u64*)out2, count, s);
+  return batch_rotate_planned(e, r, (const u64*)ct2, keys, (u64*)out2, count, s);
 HIPBFV_END
 
 long hipbfv_batch_rotate_columns(void* h, const uint64_t* ct2, void* keys, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
@@ -1878,42 +1839,14 @@ long hipbfv_batch_apply_galois_keys(void* h, const uint64_t* ct2, uint32_t elt, 
   return from_status(e->ev->apply_galois((const u64*)ct2, elt, sel, (u64*)out2, count, (hipStream_t)stream));
 HIPBFV_END
 
-// SEAL's decomposition of a row rotation into power-of-two rotations (non-adjacent form, rotate_internal).  A part of n/2 rows
-// is the identity on the rows: the chains skip it (naf_skip).
-static std::vector<int> naf_parts(int steps) {
-  std::vector<int> naf;
-  const bool neg = steps < 0;
-  int v = neg ? -steps : steps;
-  for (int i = 0; v; i++) {
-    const int zi = (v & 1) ? 2 - (v & 3) : 0;
-    v = (v - zi) >> 1;
-    if (zi) naf.push_back((neg ? -zi : zi) * (1 << i));
-  }
-  return naf;
-}
-static bool naf_skip(int part, u64 n) { return (u64)(part < 0 ? -part : part) == (n >> 1); }
-
-// SEAL's rotate_internal over per-item key sets that all decide alike: the direct key when the referenced sets hold it, the NAF
-// chain otherwise (hipbfv_batch_rotate_rows_keys splits a batch whose sets decide differently)
-static long batch_rotate_keys_internal(EvalObj* e, const u64* in, int steps, void* const* key_sets, uint64_t num_sets, const uint32_t* key_index,
-                                       u64* out, uint64_t count, hipStream_t s) {
-  if (steps == 0) return HIPBFV_S_OK;
-  const u32 elt = e->ev->galois_elt_from_step(steps);
-  if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
-  std::vector<const u64*> tab;
-  uint64_t missing = 0;
-  if (const KeySel sel = keys_sel(key_sets, num_sets, key_index, count, e, (elt - 1) >> 1, tab, &missing); sel.present())
-    return from_status(e->ev->apply_galois(in, elt, sel, out, count, s));
-  const std::vector<int> naf = naf_parts(steps);
-  if (naf.size() == 1) return no_key_in_set(missing);
-  const u64* cur = in;
-  for (int part : naf) {
-    if (naf_skip(part, e->ctx->n())) continue;
-    long hr = batch_rotate_keys_internal(e, cur, part, key_sets, num_sets, key_index, out, count, s);
-    if (hr != HIPBFV_S_OK) return hr;
-    cur = out;
-  }
-  return HIPBFV_S_OK;
+// the launches of an accepted plan over per-item key sets that all decided on it (hipbfv_batch_rotate_rows_keys splits a batch
+// whose sets decide differently)
+static long batch_rotate_keys_planned(EvalObj* e, const RowRotation& r, const u64* in, void* const* key_sets, uint64_t num_sets,
+                                      const uint32_t* key_index, u64* out, uint64_t count, hipStream_t s) {
+  return run_row_rotation(r, in, out, [&](u32 elt, const u64* cur, u64* o) {
+    std::vector<const u64*> tab;
+    return from_status(e->ev->apply_galois(cur, elt, keys_sel(key_sets, num_sets, key_index, count, e, (elt - 1) >> 1, tab), o, count, s));
+  });
 }
 
 // Item copies between a batch and a compact stage: stage item j <-> batch item items[j] (`width` words each, batch items
@@ -1940,26 +1873,23 @@ static long batch_rotate_rows_keys_impl(EvalObj* e, const u64* ct2, int steps, v
                                         u64* out2, uint64_t count, hipStream_t s, u32* watch2 = nullptr,
                                         std::vector<uint64_t>* groups = nullptr) {
   const size_t w = e->ctx->ct_words(2);
-  const u32 elt = e->ev->galois_elt_from_step(steps);
-  if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
-  // per referenced set, as the single-key call decides: the direct key, or else every key of the NAF chain
+  // per referenced set, as the single-key call decides; the sets of a group share one plan (the hops depend on the step alone)
   const std::vector<char> used = referenced_sets(key_index, count, num_sets);
-  const std::vector<int> naf = naf_parts(steps);
   std::vector<char> direct(num_sets, 0);
-  bool any_direct = false, any_naf = false;
+  RowRotation plan[2];  // the direct group's, the chain group's
+  bool any[2] = {false, false};
   for (uint64_t k = 0; k < num_sets; k++) {
     if (!used[k]) continue;
-    direct[k] = key_or_null(key_sets[k], e, (elt - 1) >> 1) != nullptr;
-    if (!direct[k]) {
-      bool chain = naf.size() > 1;
-      for (int part : naf) chain = chain && (naf_skip(part, e->ctx->n()) || key_or_null(key_sets[k], e, (e->ev->galois_elt_from_step(part) - 1) >> 1));
-      if (!chain) return no_key_in_set(k);
-    }
-    (direct[k] ? any_direct : any_naf) = true;
+    const RowRotation r = plan_row_rotation(e->ctx->n(), steps, [&](u32 elt) { return key_or_null(key_sets[k], e, (elt - 1) >> 1) != nullptr; });
+    if (r.kind == RowRotation::kTooLarge) return fail(HIPBFV_E_INVALIDARG, "step count too large");
+    if (r.kind == RowRotation::kNoKey) return no_key_in_set(k);
+    direct[k] = r.kind == RowRotation::kDirect;
+    plan[!direct[k]] = r;
+    any[!direct[k]] = true;
   }
-  if (!(any_direct && any_naf)) {  // the common case: one call over the caller's buffers
+  if (!(any[0] && any[1])) {  // the common case: one call over the caller's buffers
     WatchScope scope(watch2 ? watch2 : Evaluator::watch_status());
-    return batch_rotate_keys_internal(e, ct2, steps, key_sets, num_sets, key_index, out2, count, s);
+    return batch_rotate_keys_planned(e, plan[any[0] ? 0 : 1], ct2, key_sets, num_sets, key_index, out2, count, s);
   }
   // the sets disagree: the direct group and the NAF group run apart, each gathered into a compact stage and scattered back
   std::vector<uint64_t> items[2];
@@ -1978,7 +1908,7 @@ static long batch_rotate_rows_keys_impl(EvalObj* e, const u64* ct2, int steps, v
     if (copy_items(in_stage, ct2, nullptr, w, w, items[g], s) != hipSuccess) return from_status(kHipError);
     {
       WatchScope scope(watch2 ? watch2 + g : Evaluator::watch_status());
-      if (long hr = batch_rotate_keys_internal(e, in_stage, steps, key_sets, num_sets, kidx[g].data(), out_stage, c, s)) return hr;
+      if (long hr = batch_rotate_keys_planned(e, plan[g], in_stage, key_sets, num_sets, kidx[g].data(), out_stage, c, s)) return hr;
     }
     if (copy_items(out_stage, nullptr, out2, w, w, items[g], s) != hipSuccess) return from_status(kHipError);
     if (groups) groups[g] = std::move(items[g]);
@@ -2017,10 +1947,9 @@ HIPBFV_END
 // items share ONE launch sequence (Evaluator::apply_galois_items); any other step runs its NAF chain, together with the items
 // of the same step.  Host only (hipbfv_debug_rotate_items_plan shows it).
 struct RotateItemsPlan {
-  enum Kind : int32_t { kCopy = 0, kDirect = 1, kChain = 2 };
-  std::vector<int32_t> kind;               // per item
+  std::vector<int32_t> kind;               // per item: RowRotation::kCopy, kDirect or kChain
   std::vector<uint32_t> group;             // per item: kDirect: the Galois element, kChain: the chain group, kCopy: 0
-  std::vector<int> chain_step;             // per chain group (groups are numbered in the order their step first appears)
+  std::vector<RowRotation> chain;          // per chain group (groups are numbered in the order their step first appears)
   std::vector<std::vector<uint64_t>> chain_items;
 };
 static long item_error(uint64_t item, const char* what) {
@@ -2031,7 +1960,7 @@ static long item_error(uint64_t item, const char* what) {
 // has(element): the key set holds that element's key.  Fails, naming the first offending item, on a step of n/2 rows or more and
 // on a step with neither its own key nor every key of its chain.
 static long plan_rotate_items(u32 n, const int32_t* steps, uint64_t count, const std::function<bool(u32)>& has, RotateItemsPlan* plan) {
-  plan->kind.assign(count, RotateItemsPlan::kCopy);
+  plan->kind.assign(count, RowRotation::kCopy);
   plan->group.assign(count, 0);
   std::vector<std::pair<int, std::pair<int32_t, uint32_t>>> seen;  // step -> (kind, group)
   for (uint64_t i = 0; i < count; i++) {
@@ -2039,16 +1968,13 @@ static long plan_rotate_items(u32 n, const int32_t* steps, uint64_t count, const
     if (step == 0) continue;
     auto it = std::find_if(seen.begin(), seen.end(), [&](const auto& e) { return e.first == step; });
     if (it == seen.end()) {
-      const u32 elt = Evaluator::galois_elt_from_step(n, step);
-      if (!elt) return item_error(i, "step count too large");
-      std::pair<int32_t, uint32_t> what{RotateItemsPlan::kDirect, elt};
-      if (!has(elt)) {
-        const std::vector<int> naf = naf_parts(step);
-        bool chain = naf.size() > 1;
-        for (int part : naf) chain = chain && (naf_skip(part, n) || has(Evaluator::galois_elt_from_step(n, part)));
-        if (!chain) return item_error(i, "required key-switching key is not present");
-        what = {RotateItemsPlan::kChain, (uint32_t)plan->chain_step.size()};
-        plan->chain_step.push_back(step);
+      const RowRotation r = plan_row_rotation(n, step, has);
+      if (r.kind == RowRotation::kTooLarge) return item_error(i, "step count too large");
+      if (r.kind == RowRotation::kNoKey) return item_error(i, "required key-switching key is not present");
+      std::pair<int32_t, uint32_t> what{RowRotation::kDirect, r.elt};
+      if (r.kind == RowRotation::kChain) {
+        what = {RowRotation::kChain, (uint32_t)plan->chain.size()};
+        plan->chain.push_back(r);
         plan->chain_items.emplace_back();
       }
       seen.emplace_back(step, what);
@@ -2056,7 +1982,7 @@ static long plan_rotate_items(u32 n, const int32_t* steps, uint64_t count, const
     }
     plan->kind[i] = it->second.first;
     plan->group[i] = it->second.second;
-    if (it->second.first == RotateItemsPlan::kChain) plan->chain_items[it->second.second].push_back(i);
+    if (it->second.first == RowRotation::kChain) plan->chain_items[it->second.second].push_back(i);
   }
   return HIPBFV_S_OK;
 }
@@ -2089,13 +2015,13 @@ long hipbfv_batch_rotate_rows_items(void* h, const uint64_t* ct2, const int32_t*
   std::vector<u32> elts(count);
   std::vector<const u64*> key(count, nullptr);
   for (uint64_t i = 0; i < count; i++) {
-    elts[i] = plan.kind[i] == RotateItemsPlan::kCopy ? 1u : plan.kind[i] == RotateItemsPlan::kDirect ? plan.group[i] : 0u;
-    if (plan.kind[i] == RotateItemsPlan::kDirect) key[i] = key_or_null(keys, e, (elts[i] - 1) >> 1);
+    elts[i] = plan.kind[i] == RowRotation::kCopy ? 1u : plan.kind[i] == RowRotation::kDirect ? plan.group[i] : 0u;
+    if (plan.kind[i] == RowRotation::kDirect) key[i] = key_or_null(keys, e, (elts[i] - 1) >> 1);
   }
   u32* const watch = Evaluator::watch_status();
   WatchScope quiet(nullptr);  // (the chain groups count their own items: the results are noted once, when all are in place)
   if (int rc = e->ev->apply_galois_items((const u64*)ct2, elts.data(), key.data(), (u64*)out2, count, s, false)) return from_status(rc);
-  if (!plan.chain_step.empty()) {
+  if (!plan.chain.empty()) {
     // a chain group: its items in a compact stage, hipbfv_batch_rotate_rows' own chain over the stage, the results to their places
     size_t largest = 0;
     for (const auto& items : plan.chain_items) largest = std::max(largest, items.size());
@@ -2103,10 +2029,10 @@ long hipbfv_batch_rotate_rows_items(void* h, const uint64_t* ct2, const int32_t*
     if (!sg.p) return from_status(kOutOfMemory);
     u64* in_stage = (u64*)sg.p;
     u64* out_stage = in_stage + largest * w;
-    for (size_t g = 0; g < plan.chain_step.size(); g++) {
+    for (size_t g = 0; g < plan.chain.size(); g++) {
       const std::vector<uint64_t>& items = plan.chain_items[g];
       if (copy_items(in_stage, (const u64*)ct2, nullptr, w, w, items, s) != hipSuccess) return from_status(kHipError);
-      if (long hr = batch_rotate_internal(e, in_stage, plan.chain_step[g], keys, out_stage, items.size(), s)) return hr;
+      if (long hr = batch_rotate_planned(e, plan.chain[g], in_stage, keys, out_stage, items.size(), s)) return hr;
       if (copy_items(out_stage, nullptr, (u64*)out2, w, w, items, s) != hipSuccess) return from_status(kHipError);
     }
   }
@@ -2127,7 +2053,7 @@ long hipbfv_debug_rotate_items_plan(uint64_t n, const int32_t* steps, uint64_t c
     return hr;
   std::copy(plan.kind.begin(), plan.kind.end(), kind);
   std::copy(plan.group.begin(), plan.group.end(), group);
-  *chain_groups = plan.chain_step.size();
+  *chain_groups = plan.chain.size();
   return HIPBFV_S_OK;
 HIPBFV_END
 
@@ -2142,7 +2068,7 @@ struct ItemsKeysPlan {
   static constexpr uint32_t kNone = 0xFFFFFFFFu;
   struct Decision {
     uint32_t set;
-    int32_t kind;                 // RotateItemsPlan::kDirect or kChain
+    int32_t kind;                 // RowRotation::kDirect or kChain
     uint32_t elt;                 // the step's own Galois element
     std::vector<uint32_t> chain;  // kChain: the elements of the chain's parts, in order, the skipped n/2 part left out
     uint32_t entry;               // kDirect: the entry of the mixed launch's key table
@@ -2179,18 +2105,17 @@ static long plan_items_keys(u32 n, const int32_t* steps, const uint32_t* elts, c
     auto it = seen.find(what);
     if (it == seen.end()) {
       if (const char* why = usable(k)) return item_set_error(i, k, why);
-      ItemsKeysPlan::Decision d{k, RotateItemsPlan::kDirect, elt, {}, 0};
-      if (!has(k, elt)) {
-        const std::vector<int> naf = steps ? naf_parts(step) : std::vector<int>();
-        bool chain = naf.size() > 1;
-        for (int part : naf) {
-          if (!chain || naf_skip(part, n)) continue;
-          const u32 e = Evaluator::galois_elt_from_step(n, part);
-          if ((chain = has(k, e))) d.chain.push_back(e);
-        }
-        if (!chain) return item_set_error(i, k, "the set does not hold the required key-switching key");
-        d.kind = RotateItemsPlan::kChain;
-        plan->rounds = std::max<uint64_t>(plan->rounds, d.chain.size());
+      const auto held = [&](u32 e) { return has(k, e); };
+      RowRotation r;  // a Galois element has no chain: its own key or none
+      if (steps)
+        r = plan_row_rotation(n, step, held);
+      else
+        r.kind = held(elt) ? RowRotation::kDirect : RowRotation::kNoKey;
+      if (r.kind == RowRotation::kNoKey) return item_set_error(i, k, "the set does not hold the required key-switching key");
+      ItemsKeysPlan::Decision d{k, r.kind, elt, {}, 0};
+      if (r.kind == RowRotation::kChain) {
+        d.chain.assign(r.hop, r.hop + r.hops);
+        plan->rounds = std::max<uint64_t>(plan->rounds, r.hops);
       }
       it = seen.emplace(what, (uint32_t)plan->dec.size()).first;
       plan->dec.push_back(std::move(d));
@@ -2199,10 +2124,10 @@ static long plan_items_keys(u32 n, const int32_t* steps, const uint32_t* elts, c
   }
   std::map<std::pair<u32, uint32_t>, uint32_t> entry;  // (element, set): the table's order
   for (const auto& d : plan->dec)
-    if (d.kind == RotateItemsPlan::kDirect) entry.emplace(std::make_pair(d.elt, d.set), 0u);
+    if (d.kind == RowRotation::kDirect) entry.emplace(std::make_pair(d.elt, d.set), 0u);
   for (auto& kv : entry) kv.second = (uint32_t)plan->entries++;
   for (auto& d : plan->dec)
-    if (d.kind == RotateItemsPlan::kDirect) d.entry = entry[{d.elt, d.set}];
+    if (d.kind == RowRotation::kDirect) d.entry = entry[{d.elt, d.set}];
   return HIPBFV_S_OK;
 }
 
@@ -2229,13 +2154,13 @@ static long batch_items_keys_impl(EvalObj* e, const u64* ct2, const int32_t* ste
   std::vector<u64> chain_items;
   std::vector<const u64*> dkey(plan.dec.size(), nullptr);
   for (size_t d = 0; d < plan.dec.size(); d++)
-    if (plan.dec[d].kind == RotateItemsPlan::kDirect) dkey[d] = key_or_null(key_sets[plan.dec[d].set], e, (plan.dec[d].elt - 1) >> 1);
+    if (plan.dec[d].kind == RowRotation::kDirect) dkey[d] = key_or_null(key_sets[plan.dec[d].set], e, (plan.dec[d].elt - 1) >> 1);
   for (uint64_t i = 0; i < count; i++) {
     if (plan.of[i] == ItemsKeysPlan::kNone) continue;
     const ItemsKeysPlan::Decision& d = plan.dec[plan.of[i]];
-    pass[i] = d.kind == RotateItemsPlan::kDirect ? d.elt : 0u;
+    pass[i] = d.kind == RowRotation::kDirect ? d.elt : 0u;
     key[i] = dkey[plan.of[i]];
-    if (d.kind == RotateItemsPlan::kChain) chain_items.push_back(i);
+    if (d.kind == RowRotation::kChain) chain_items.push_back(i);
   }
   WatchScope quiet(nullptr);  // (the chain rounds count their own items: the results are noted once, when all are in place)
   if (int rc = e->ev->apply_galois_items_keyed(ct2, pass.data(), key.data(), key_index, out2, count, s, false)) return from_status(rc);
@@ -2306,8 +2231,8 @@ long hipbfv_debug_rotate_items_keys_plan(uint64_t n, const int32_t* steps, const
     return hr;
   for (uint64_t i = 0; i < count; i++) {
     const ItemsKeysPlan::Decision* d = plan.of[i] == ItemsKeysPlan::kNone ? nullptr : &plan.dec[plan.of[i]];
-    kind[i] = d ? d->kind : (int32_t)RotateItemsPlan::kCopy;
-    table_entry[i] = d && d->kind == RotateItemsPlan::kDirect ? d->entry : 0u;
+    kind[i] = d ? d->kind : (int32_t)RowRotation::kCopy;
+    table_entry[i] = d && d->kind == RowRotation::kDirect ? d->entry : 0u;
     chain_rounds_of_item[i] = d ? (uint32_t)d->chain.size() : 0u;
   }
   *table_entries = plan.entries;
@@ -4377,23 +4302,23 @@ static long pool_rotate_keys(const char* name, void* pool, const uint64_t* ct2, 
   const u32 elt = columns ? 2 * p->n - 1 : steps ? ev0.galois_elt_from_step(steps) : 1;
   if (!elt) return fail(HIPBFV_E_INVALIDARG, "step count too large");
   const bool copy_only = !columns && steps == 0;  // the identity: no key is read
-  const std::vector<int> naf = columns || copy_only ? std::vector<int>() : naf_parts(steps);
   PoolSetKeys all;
   if (long hr = pool_set_keys(*p, nullptr, key_sets, num_sets, key_index, count,
                               [&](KeysObj*, KeysObj* gk, std::vector<PoolKey>*, std::vector<PoolKey>* need) {
                                 if (copy_only) return true;
-                                PoolKey k;
                                 if (!gk) return false;
-                                if (pool_key_of(gk, (elt - 1) >> 1, &k)) {  // the direct key: the only one this set's rotation reads
+                                PoolKey k;
+                                const auto held = [&](u32 e) { return pool_key_of(gk, (e - 1) >> 1, &k); };  // (k: that key)
+                                if (columns) {
+                                  if (!held(elt)) return false;
                                   need->push_back(k);
                                   return true;
                                 }
-                                if (naf.size() < 2) return false;
-                                for (int part : naf) {
-                                  if (naf_skip(part, p->n)) continue;
-                                  if (!pool_key_of(gk, (ev0.galois_elt_from_step(part) - 1) >> 1, &k)) return false;
-                                  need->push_back(k);
-                                }
+                                // the keys of the set's hops, the only ones its rotation reads: the direct key, or else the chain's
+                                const RowRotation r = plan_row_rotation(p->n, steps, held);
+                                if (r.kind == RowRotation::kNoKey) return false;
+                                for (u32 h = 0; h < r.hops; h++)
+                                  if (held(r.hop[h])) need->push_back(k);
                                 return true;
                               },
                               &all))
@@ -4492,7 +4417,7 @@ long hipbfv_Pool_RotateRowsItemsKeys(void* pool, const uint64_t* ct2, const int3
     const ItemsKeysPlan::Decision& dec = plan.dec[d];
     KeysObj* gk = pool_keyset(*p, key_sets[dec.set]);
     PoolKey key;
-    if (dec.kind == RotateItemsPlan::kDirect) {
+    if (dec.kind == RowRotation::kDirect) {
       if (pool_key_of(gk, (dec.elt - 1) >> 1, &key)) reads[d].push_back(key);
     } else {
       for (u32 elt : dec.chain)

@@ -300,4 +300,60 @@ class Evaluator {
   bool fuse_mulrelin_ = true;  // multiply_relin: c0, c1 of the product formed inside the key switch's last kernel
 };
 
+// How a row rotation by `step` runs over one holding of Galois keys (SEAL's Evaluator::rotate_internal), decided on the host before
+// anything is launched: through the step's own key when it is held, otherwise through the chain of power-of-two rotations of the
+// step's non-adjacent form (NAF), least significant digit first, the sign carried by every part.  A part of n/2 rows is the identity
+// on the rows and is no hop.  hop[0, hops) are the Galois elements to apply in order: the step's own for kDirect, none for kCopy.
+struct RowRotation {
+  enum Kind : int32_t { kCopy = 0, kDirect = 1, kChain = 2, kTooLarge = 3, kNoKey = 4 };  // kTooLarge, kNoKey: refused
+  Kind kind = kCopy;
+  u32 elt = 1;      // the step's own Galois element (0: kTooLarge)
+  u32 missing = 0;  // kNoKey: the element whose key was looked for and not found
+  u32 hops = 0;
+  u32 hop[32];
+};
+
+// has(element): the holding has that element's key.  A chain needs two NAF parts or more: a power of two without its key is kNoKey.
+template <class Has>
+RowRotation plan_row_rotation(u32 n, int step, Has&& has) {
+  RowRotation r;
+  if (step == 0) return r;
+  r.elt = Evaluator::galois_elt_from_step(n, step);  // refuses |step| >= n/2 (INT_MIN too) before the step is negated below
+  const auto refused = [&](RowRotation::Kind why, u32 missing) {
+    r.kind = why, r.missing = missing, r.hops = 0;
+    return r;
+  };
+  if (!r.elt) return refused(RowRotation::kTooLarge, 0);
+  if (has(r.elt)) {
+    r.kind = RowRotation::kDirect, r.hop[r.hops++] = r.elt;
+    return r;
+  }
+  u32 parts = 0;
+  int v = step < 0 ? -step : step;
+  for (int i = 0; v; i++) {
+    const int zi = (v & 1) ? 2 - (v & 3) : 0;
+    v = (v - zi) >> 1;
+    if (!zi) continue;
+    parts++;
+    if ((1u << i) == (n >> 1)) continue;
+    r.hop[r.hops++] = Evaluator::galois_elt_from_step(n, (step < 0 ? -zi : zi) * (1 << i));
+  }
+  if (parts < 2) return refused(RowRotation::kNoKey, r.elt);
+  for (u32 h = 0; h < r.hops; h++)
+    if (!has(r.hop[h])) return refused(RowRotation::kNoKey, r.hop[h]);
+  r.kind = RowRotation::kChain;
+  return r;
+}
+
+// The launches of an accepted plan: hop(element, cur, out) per hop, cur = in first and out afterwards; the first non-zero status ends it.
+template <class In, class Out, class Hop>
+auto run_row_rotation(const RowRotation& r, In in, Out out, Hop&& hop) -> decltype(hop(0u, in, out)) {
+  In cur = in;
+  for (u32 h = 0; h < r.hops; h++) {
+    if (auto st = hop(r.hop[h], cur, out)) return st;
+    cur = out;
+  }
+  return 0;
+}
+
 }  // namespace hipbfv

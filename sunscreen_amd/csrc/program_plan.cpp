@@ -979,32 +979,16 @@ int Program::run_plan(Evaluator& ev, size_t batch, const ProgramInput* inputs, s
   };
 
   auto galois_key = [&](u32 elt) -> KeySel { return keys.galois_sel(elt); };
-  // rotate `in` by `steps` into `out` following SEAL's rotate_internal (direct key or NAF chain)
-  std::function<int(const u64*, int, u64*)> rotate = [&](const u64* in, int steps, u64* out) -> int {
-    if (steps == 0) {
+  // rotate `in` by `steps` into `out` following SEAL's rotate_internal: planned over the run's keys, then launched
+  auto rotate = [&](const u64* in, int steps, u64* out) -> int {
+    const RowRotation r = plan_row_rotation((u32)n, steps, [&](u32 elt) { return galois_key(elt).present(); });
+    if (r.kind == RowRotation::kTooLarge) return kInvalidArg;
+    if (r.kind == RowRotation::kNoKey) return kNoKey;
+    if (r.kind == RowRotation::kCopy) {
       if (in != out && hipMemcpyAsync(out, in, batch * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess) return kHipError;
       return kOk;
     }
-    const u32 elt = ev.galois_elt_from_step(steps);
-    if (!elt) return kInvalidArg;
-    if (const KeySel key = galois_key(elt); key.present()) return ev.apply_galois(in, elt, key, out, batch, s);
-    std::vector<int> naf;
-    const bool neg = steps < 0;
-    int v = neg ? -steps : steps;
-    for (int i = 0; v; i++) {
-      const int zi = (v & 1) ? 2 - (v & 3) : 0;
-      v = (v - zi) >> 1;
-      if (zi) naf.push_back((neg ? -zi : zi) * (1 << i));
-    }
-    if (naf.size() == 1) return kNoKey;
-    const u64* cur = in;
-    for (int part : naf) {
-      if ((size_t)(part < 0 ? -part : part) == (n >> 1)) continue;
-      int rc = rotate(cur, part, out);
-      if (rc) return rc;
-      cur = out;
-    }
-    return kOk;
+    return run_row_rotation(r, in, out, [&](u32 elt, const u64* cur, u64* o) { return ev.apply_galois(cur, elt, galois_key(elt), o, batch, s); });
   };
 
   // operands of a merged launch as ONE array: used in place when the members' buffers are adjacent and in order, staged otherwise

@@ -1,9 +1,10 @@
-"""Row rotations at the edges of the step range through every caller's copy of SEAL's rotate_internal.
+"""Row rotations at the edges of the step range through every caller of SEAL's rotate_internal.
 
 A rotation whose own Galois key is absent is decomposed into power-of-two rotations: the non-adjacent form (NAF) of the step,
-low digit first, a part of exactly n/2 rows skipped.  The library holds that loop six times (the handle-level call, the batch
-call, the per-key batch call with its split into a direct and a chain group, the two program executors, the device pool's
-walk over the keys a member copies).  Every copy is run here on the steps where the loop can go wrong -- chains of up to six
+low digit first, a part of exactly n/2 rows skipped.  The library decides that once (plan_row_rotation) for six callers (the
+handle-level call, the batch call, the per-key batch call with its split into a direct and a chain group, the two program
+executors, the device pool's walk over the keys a member copies).  Every caller is run here on the steps where the chain can go
+wrong -- chains of up to six
 hops (the first hop of an out-of-place chain reads the automorphism through the key switch, every later hop rotates its own
 output in place through the rotated copy), mixed signs, the skipped n/2 part, steps that must be refused -- and judged three
 ways: word for word against the CPU oracle, word for word against the other callers, and by the decoded slots (both rows of
@@ -476,9 +477,9 @@ def test_every_caller_refuses_a_step_of_half_the_degree_or_more(step, monkeypatc
 # ---- a chain key that is missing -----------------------------------------------------------------------------------------
 def test_a_missing_chain_key_fails_the_chains_that_read_it_and_no_other():
     """Holding M lacks the key of step +4.  1365 = [1, 4, 16, ...] and -11 = [1, 4, -16] read it: the per-key call and the pool
-    fail before anything runs (the output keeps its sentinel, the error names the set), the single-key batch call and the
-    handle call return the missing-key error (their destination may hold a half-rotated value, as SEAL's does; a distinct
-    input keeps its words).  11 = [-1, -4, 16] reads the key of -4, not of +4, and succeeds, as do 2047 (the key of -1),
+    fail before anything runs (the output keeps its sentinel, the error names the set), and so do the single-key batch call
+    (its output keeps its sentinel too) and the handle call, with the missing-key error: a refused rotation launches nothing;
+    the input keeps its words.  11 = [-1, -4, 16] reads the key of -4, not of +4, and succeeds, as do 2047 (the key of -1),
     1025 and 2045."""
     import torch
     from sunscreen_amd import Ciphertext
@@ -502,11 +503,11 @@ def test_a_missing_chain_key_fails_the_chains_that_read_it_and_no_other():
         hr, msg = _hr(lambda: pool.rotate_rows_keys(host_in, step, sets, ki, out=host_out))
         assert hr == E_INVALIDARG and re.search(r"key set 2\b", msg), (step, hex(hr), msg)
         assert (host_out == 7).all() and (host_in == w.cts[:count]).all(), step
-        scratch_out = torch.empty_like(da)
+        scratch_out = torch.full_like(da, SENTINEL)
         hr, msg = _hr(lambda: ev.rotate_rows(da, step, w.gkd["M"], out=scratch_out))
         assert hr == E_INVALIDARG and "key" in msg and "step count" not in msg, (step, hex(hr), msg)
         torch.cuda.synchronize()
-        assert torch.equal(da, w.dev[:count]), step
+        assert bool((scratch_out == SENTINEL).all()) and torch.equal(da, w.dev[:count]), step
         a = Ciphertext.from_array(w.ctx, w.cts[0])
         hr, msg = _hr(lambda: w.hev().rotate_rows(a, step, w.gkd["M"]))
         assert hr == E_INVALIDARG and "key" in msg and "step count" not in msg, (step, hex(hr), msg)

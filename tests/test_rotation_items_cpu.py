@@ -5,6 +5,8 @@ import re
 
 import pytest
 
+from tests import rotation_plan_expect as X
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALIDARG = 0x80070057
 N = 4096
@@ -114,3 +116,44 @@ def test_a_missing_key_names_the_first_item_that_needs_it():
     assert hr == E_INVALIDARG and re.search(r"\bitem 2\b", msg) and "key" in msg and "step count" not in msg, (hex(hr), msg)
     hr, msg = _refused([0, 4], without4)
     assert hr == E_INVALIDARG and re.search(r"\bitem 1\b", msg) and "key" in msg, (hex(hr), msg)
+
+
+# ---- the planner against an independent derivation, every step of four degrees ----------------------------------------
+def _sweep(n, name, held):
+    """Accepted steps in batches (a refusal would name its item), the steps expected to be refused one per call."""
+    want = {s: X.expected(n, s, held) for s in X.sweep_steps(n)}
+    for chunk in X.batches([s for s in want if want[s][0] in (COPY, DIRECT, CHAIN)]):
+        kind, group, chains = _plan(chunk, sorted(held), n)
+        assert kind == [want[s][0] for s in chunk], (n, name, chunk)
+        assert [g for s, g in zip(chunk, group) if want[s][0] == DIRECT] == [X.elt(s, n) for s in chunk if want[s][0] == DIRECT], (n, name, chunk)
+        assert chains == kind.count(CHAIN), (n, name, chunk)  # (distinct steps: a group each)
+    for step, (why, _) in want.items():
+        if why in (X.TOO_LARGE, X.NO_KEY):
+            hr, msg = _refused([0, step], sorted(held), n)
+            assert hr == E_INVALIDARG and re.search(r"\bitem 1\b", msg) and why in msg, (n, name, step, msg)
+            assert why == X.TOO_LARGE or X.TOO_LARGE not in msg, (n, name, step, msg)
+
+
+@pytest.mark.parametrize("n", X.DEGREES)
+def test_every_step_plans_as_the_independent_naf_says(n):
+    """Kind and refusal of every step in (-n/2, n/2), of +-n/2, n/2 + 1, INT_MIN and INT_MAX, over every +-2^i key and over
+    that set with each power removed in turn; then every step over a set that holds its own key alone: direct."""
+    for name, held in X.holdings(n):
+        _sweep(n, name, held)
+    for step in range(-n // 2 + 1, n // 2):
+        if step:
+            assert _plan([step], [X.elt(step, n)], n) == ([DIRECT], [X.elt(step, n)], 0), (n, step)
+    assert X.expected(n, n // 2 - 1, frozenset(X.pow2(n)))[0] == DIRECT  # the element of step -1
+
+
+def test_the_edge_steps_of_degree_4096():
+    """2047 and 2046 go through the keys of -1 and -2 and walk no chain; 2045, 1707 and 1365 are chains (their hop counts are in
+    tests/test_rotation_items_keys_cpu.py); 11 does not read the key of +4, -11 does."""
+    assert X.hops(2045, N) == [1, -4] and X.hops(1707, N) == [-1, -4, -16, -64, -256] and X.hops(1365, N) == [1, 4, 16, 64, 256, 1024]
+    assert X.hops(11, N) == [-1, -4, 16] and X.hops(-11, N) == [1, 4, -16]
+    kind, group, chains = _plan([2047, 2046, 2045, 1707, 1365], POW2)
+    assert kind == [DIRECT, DIRECT, CHAIN, CHAIN, CHAIN] and group[:2] == [_elt(-1), _elt(-2)] and chains == 3
+    without4 = [e for e in POW2 if e != _elt(4)]
+    assert _plan([11], without4) == ([CHAIN], [0], 1)
+    hr, msg = _refused([-11], without4)
+    assert hr == E_INVALIDARG and "key" in msg and "step count" not in msg, msg

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from tests import rotation_plan_expect as X
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALIDARG = 0x80070057
 E_POINTER = 0x80004003
@@ -199,3 +201,41 @@ def test_null_arguments_of_the_entry_points_need_no_device():
     assert hr(plan(N, steps, idx, 1, 1, None, None, kind, entry, rounds_of, C.byref(ne), C.byref(nr))) == E_POINTER
     assert hr(plan(N, steps, idx, 1, 0, None, offsets, kind, entry, rounds_of, C.byref(ne), C.byref(nr))) == E_POINTER
     assert hr(plan(N + 1, steps, idx, 1, 1, None, offsets, kind, entry, rounds_of, C.byref(ne), C.byref(nr))) == E_INVALIDARG
+
+
+# ---- the planner against an independent derivation, every step of four degrees ----------------------------------------
+@pytest.mark.parametrize("n", X.DEGREES)
+def test_every_step_plans_as_the_independent_naf_says(n):
+    """Kind, refusal and rounds (the chain's hops, the n/2 part left out) of every step in (-n/2, n/2), of +-n/2, n/2 + 1,
+    INT_MIN and INT_MAX: set 0 holds every +-2^i key, set 1 that set with one power removed (each power in turn).  Accepted
+    steps go in batches (a refusal would name its item), the steps expected to be refused one per call.  Then every step with a
+    set of its own that holds the step's key alone: direct, one table entry each."""
+    for name, held in X.holdings(n):
+        sets = [sorted(X.pow2(n)), sorted(held)]
+        want = {(s, k): X.expected(n, s, frozenset(sets[k])) for s in X.sweep_steps(n) for k in (0, 1)}
+        for chunk in X.batches([sk for sk in want if want[sk][0] in (COPY, DIRECT, CHAIN)]):
+            kind, _, rounds_of, _, rounds = _plan([s for s, _ in chunk], [k for _, k in chunk], sets, n)
+            assert kind == [want[sk][0] for sk in chunk], (n, name, chunk)
+            assert rounds_of == [want[sk][1] for sk in chunk] and rounds == max(rounds_of), (n, name, chunk)
+        for (step, k), (why, _) in want.items():
+            if why in (X.TOO_LARGE, X.NO_KEY):
+                hr, msg = _refused([0, step], [1 - k, k], sets, n)
+                assert hr == E_INVALIDARG and "item 1: key set %d" % k in msg and why in msg, (n, name, step, k, msg)
+                assert why == X.TOO_LARGE or X.TOO_LARGE not in msg, (n, name, step, k, msg)
+    steps = [s for s in range(-n // 2 + 1, n // 2) if s]
+    for chunk in X.batches(steps):
+        kind, entry, rounds_of, entries, rounds = _plan(chunk, list(range(len(chunk))), [[X.elt(s, n)] for s in chunk], n)
+        assert kind == [DIRECT] * len(chunk) and rounds_of == [0] * len(chunk) and (entries, rounds) == (len(chunk), 0), (n, chunk)
+        assert sorted(entry) == list(range(len(chunk))), (n, chunk)
+
+
+def test_the_edge_steps_of_degree_4096():
+    """2047 and 2046 go through the keys of -1 and -2 and walk no chain; 2045 has two hops, 1707 five, 1365 six; 11 does not read
+    the key of +4, -11 does."""
+    kind, _, rounds_of, entries, rounds = _plan([2047, 2046, 2045, 1707, 1365, -1, -2], [0] * 7, [POW2])
+    assert kind == [DIRECT, DIRECT, CHAIN, CHAIN, CHAIN, DIRECT, DIRECT] and rounds_of == [0, 0, 2, 5, 6, 0, 0]
+    assert entries == 2 and rounds == 6  # 2047 and -1, 2046 and -2: one key each
+    without4 = [e for e in POW2 if e != _elt(4)]
+    assert _plan([11], [0], [without4])[2] == [3]
+    hr, msg = _refused([-11], [0], [without4])
+    assert hr == E_INVALIDARG and "item 0: key set 0" in msg and "step count" not in msg, msg
