@@ -359,6 +359,34 @@ long hipbfv_batch_relinearize_keys(void *evaluator, const uint64_t *ct3, void *c
 long hipbfv_batch_multiply_relin_keys(void *evaluator, const uint64_t *a, const uint64_t *b, void *const *relin_key_sets,
                                       uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t count,
                                       void *stream);
+/* Sums of products with lazy relinearization: out[g] = sum_t a[g][t] * b[g][t] -- an inner product of two ciphertext vectors,
+ * the sum of squares of a variance, a row of a ciphertext matrix product -- with ONE key switch per group instead of one per
+ * term.  a, b: u64[groups][terms][2][K][N]; b == a (the same pointer) sums squares, and the operand is extended and transformed
+ * once.  out3: u64[groups][3][K][N]; out2: u64[groups][2][K][N].
+ *  - Bits: out3[g] is, word for word, the sum (hipbfv_batch_add) of hipbfv_batch_multiply over the group's terms, and out2[g] is
+ *    hipbfv_batch_relinearize of that sum.  With terms == 1 the calls give exactly the bits of hipbfv_batch_multiply and
+ *    hipbfv_batch_multiply_relin.  The _keys form takes one key set per GROUP (key_index: a HOST array of `groups` entries): group
+ *    g gives the bits of the single-key call with relin_key_sets[key_index[g]]; only referenced sets are validated and read, as in
+ *    hipbfv_batch_relinearize_keys.
+ *  - Refusals, all before anything is launched or written: a NULL a, b, output (or key table) is HIPBFV_E_POINTER; terms == 0 is
+ *    HIPBFV_E_INVALIDARG; ANY overlap of the output range with [a, a + groups * terms * 2 K N) or the same range of b is
+ *    HIPBFV_E_INVALIDARG (the widths differ: there is no in-place form); key_index[g] >= num_key_sets is HIPBFV_E_INVALIDARG; a
+ *    missing relinearization key fails as hipbfv_batch_relinearize(_keys) does.  groups == 0 returns HIPBFV_S_OK, nothing launched.
+ *  - Launches: where hipbfv_batch_multiply takes the split kernels for groups * terms items, every term is finished inside the
+ *    multiply's last kernel and summed in registers: the 3 K rows of a term are never written.  Elsewhere (N < 4096, N = 32768, a
+ *    few items) the terms are multiplied into a staging buffer and folded: the same bits.  The evaluator's chunk setting bounds
+ *    the scratch: a chunk is a whole number of groups; a group with more terms than a chunk holds is summed in slices
+ *    (hipbfv_debug_multiply_sum_plan).  Asynchronous on `stream`.
+ *  - Transparent results: the final sums (out3; out2 for the relinearizing forms) are recorded under GROUP numbers
+ *    (hipbfv_batch_status).  A transparent single term inside a sum that is not transparent is NOT detected, where the sequence
+ *    of single multiplications would have reported it. */
+long hipbfv_batch_multiply_sum(void *evaluator, const uint64_t *a, const uint64_t *b, uint64_t *out3, uint64_t groups,
+                               uint64_t terms, void *stream);
+long hipbfv_batch_multiply_sum_relin(void *evaluator, const uint64_t *a, const uint64_t *b, void *relin_keys, uint64_t *out2,
+                                     uint64_t groups, uint64_t terms, void *stream);
+long hipbfv_batch_multiply_sum_relin_keys(void *evaluator, const uint64_t *a, const uint64_t *b, void *const *relin_key_sets,
+                                          uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t groups,
+                                          uint64_t terms, void *stream);
 long hipbfv_batch_apply_galois_keys(void *evaluator, const uint64_t *ct2, uint32_t galois_elt, void *const *galois_key_sets,
                                     uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t count,
                                     void *stream);
@@ -645,6 +673,12 @@ long hipbfv_debug_rotate_items_keys_plan(uint64_t n, const int32_t *steps, const
                                          uint64_t num_key_sets, const uint32_t *present_elts, const uint64_t *present_offsets,
                                          int32_t *kind, uint32_t *table_entry, uint32_t *chain_rounds_of_item,
                                          uint64_t *table_entries, uint64_t *rounds);
+/* Host only: the launch sequences of hipbfv_batch_multiply_sum(_relin) for `groups` groups of `terms` terms under a chunk of
+ * `chunk` items (at most 65535 count).  steps5[i] = {first group, groups, first term, terms, accumulate} of sequence i (capacity
+ * rows of five): its items are multiplied together and summed by one launch; accumulate = 1: the sums are added onto the rows an
+ * earlier slice of the same group wrote.  *count = the number of sequences (E_INVALIDARG when it exceeds capacity). */
+long hipbfv_debug_multiply_sum_plan(uint64_t groups, uint64_t terms, uint64_t chunk, uint64_t *steps5, uint64_t capacity,
+                                    uint64_t *count);
 
 /* Per-kernel timing (HIP events recorded on the launch stream, around every kernel launch):
  * total milliseconds, number of launches and work units (residue polynomials for the NTT kernels,

@@ -662,6 +662,22 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
     if (steps.size() != key_index.size()) throw std::invalid_argument("one step and one key index per item");
     check(hipbfv_batch_rotate_rows_items_keys(h_, ct, steps.data(), hs.data(), hs.size(), key_index.data(), out, key_index.size(), stream));
   }
+  // Sums of products with one relinearization per group on device buffers (hipbfv.h): a, b = u64[groups][terms][2][K][N] (b == a sums
+  // squares), out3 = u64[groups][3][K][N], out2 = u64[groups][2][K][N].  No in-place form.  Not part of the reference crate's surface.
+  void multiply_sum(const uint64_t* a, const uint64_t* b, uint64_t* out3, uint64_t groups, uint64_t terms, void* stream = nullptr) const {
+    check(hipbfv_batch_multiply_sum(h_, a, b, out3, groups, terms, stream));
+  }
+  void multiply_sum_relin(const uint64_t* a, const uint64_t* b, const RelinearizationKeys& rk, uint64_t* out2, uint64_t groups, uint64_t terms,
+                          void* stream = nullptr) const {
+    check(hipbfv_batch_multiply_sum_relin(h_, a, b, rk.get_handle(), out2, groups, terms, stream));
+  }
+  // ... group g through keys[key_index[g]]; an entry of `keys` that no group names may be nullptr
+  void multiply_sum_relin_keys(const uint64_t* a, const uint64_t* b, const std::vector<const RelinearizationKeys*>& keys,
+                               const std::vector<uint32_t>& key_index, uint64_t* out2, uint64_t terms, void* stream = nullptr) const {
+    std::vector<void*> hs;
+    for (const RelinearizationKeys* k : keys) hs.push_back(k ? k->get_handle() : nullptr);
+    check(hipbfv_batch_multiply_sum_relin_keys(h_, a, b, hs.data(), hs.size(), key_index.data(), out2, key_index.size(), terms, stream));
+  }
 };
 
 // The device pool (hipbfv.h, "Device pool"): host-resident batches u64[count][2][K][N] sharded over several GPUs, every input

@@ -122,6 +122,35 @@ impl<'e> BatchEvaluator<'e> {
             bindgen::hipbfv_batch_relinearize_keys(self.h(), ct3.ptr, handles.as_ptr(), handles.len() as u64, key_index.as_ptr(), out.ptr, ct3.count, self.stream)
         })
     }
+    // ---- sums of products with one relinearization per group (include/hipbfv.h) ----
+    // `a`, `b`: `groups * terms` ciphertexts of size 2, group-major (`u64[groups][terms][2][K][N]`); `out`: one ciphertext per group.
+    // The same batch as `a` and `b` sums squares.  No in-place form: the output may not overlap an operand.
+    fn sum_shape_ok(a: &DeviceBatch, b: &DeviceBatch, terms: u64, out: &DeviceBatch) -> Result<()> {
+        same_count(a, b)?;
+        if terms == 0 || out.count.checked_mul(terms) != Some(a.count) {
+            return Err(crate::Error::InvalidArgument(format!("{} terms of {} per group for {} groups", a.count, terms, out.count)));
+        }
+        Ok(())
+    }
+    pub fn multiply_sum(&self, a: DeviceBatch, b: DeviceBatch, terms: u64, out3: DeviceBatch) -> Result<()> {
+        Self::sum_shape_ok(&a, &b, terms, &out3)?;
+        check(unsafe { bindgen::hipbfv_batch_multiply_sum(self.h(), a.ptr, b.ptr, out3.ptr, out3.count, terms, self.stream) })
+    }
+    pub fn multiply_sum_relin(&self, a: DeviceBatch, b: DeviceBatch, terms: u64, rk: &RelinearizationKeys, out: DeviceBatch) -> Result<()> {
+        Self::sum_shape_ok(&a, &b, terms, &out)?;
+        check(unsafe { bindgen::hipbfv_batch_multiply_sum_relin(self.h(), a.ptr, b.ptr, rk.get_handle(), out.ptr, out.count, terms, self.stream) })
+    }
+    /// Group g is relinearised with `keys[key_index[g]]`; an entry no group names may be `None`.
+    pub fn multiply_sum_relin_keys(&self, a: DeviceBatch, b: DeviceBatch, terms: u64, keys: &[Option<&RelinearizationKeys>], key_index: &[u32],
+                                   out: DeviceBatch) -> Result<()> {
+        Self::sum_shape_ok(&a, &b, terms, &out)?;
+        Self::key_index_ok(key_index, keys.len(), out.count)?;
+        let handles: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(std::ptr::null_mut(), |k| k.get_handle())).collect();
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_sum_relin_keys(self.h(), a.ptr, b.ptr, handles.as_ptr(), handles.len() as u64, key_index.as_ptr(), out.ptr, out.count, terms,
+                                                          self.stream)
+        })
+    }
     pub fn rotate_rows_keys(&self, a: DeviceBatch, steps: i32, keys: &[&GaloisKeys], key_index: &[u32], out: DeviceBatch) -> Result<()> {
         same_count(&a, &out)?;
         Self::key_index_ok(key_index, keys.len(), a.count)?;

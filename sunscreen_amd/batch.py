@@ -183,6 +183,37 @@ class BatchEvaluator:
         _check(_lib.load().hipbfv_batch_multiply_relin_keys(self._h, _ptr(a), _ptr(b), hs, n, ip, _ptr(out), a.shape[0], _stream()))
         return out
 
+    # ---- sums of products, one relinearization per group (include/hipbfv.h) ----
+    def _sum_shape(self, a: torch.Tensor, b: torch.Tensor):
+        for t in (a, b):
+            assert t.dim() == 5 and t.shape[2] == 2 and t.shape[3] == self.K and t.shape[4] == self.n, tuple(t.shape)
+        assert a.shape == b.shape, (tuple(a.shape), tuple(b.shape))
+        return a.shape[0], a.shape[1]
+
+    def multiply_sum(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """a, b: [groups, terms, 2, K, N] (`b is a`: sums of squares).  out[g] = sum_t a[g, t] * b[g, t] as size-3 ciphertexts
+        [groups, 3, K, N]: the words of multiply() on every term, added.  No in-place form."""
+        groups, terms = self._sum_shape(a, b)
+        out = out if out is not None else self._new(groups, 3, a)
+        _check(_lib.load().hipbfv_batch_multiply_sum(self._h, _ptr(a), _ptr(b), _ptr(out), groups, terms, _stream()))
+        return out
+
+    def multiply_sum_relin(self, a: torch.Tensor, b: torch.Tensor, rk: RelinearizationKeys, out: torch.Tensor | None = None) -> torch.Tensor:
+        """relinearize(multiply_sum(a, b)), [groups, 2, K, N]: one key switch per group instead of one per term."""
+        groups, terms = self._sum_shape(a, b)
+        out = out if out is not None else self._new(groups, 2, a)
+        _check(_lib.load().hipbfv_batch_multiply_sum_relin(self._h, _ptr(a), _ptr(b), rk.get_handle(), _ptr(out), groups, terms, _stream()))
+        return out
+
+    def multiply_sum_relin_keys(self, a: torch.Tensor, b: torch.Tensor, key_sets: Sequence[RelinearizationKeys | None], key_index,
+                                out: torch.Tensor | None = None) -> torch.Tensor:
+        """Group g is relinearised with key_sets[key_index[g]] (key_index: `groups` host integers); only named sets are read."""
+        groups, terms = self._sum_shape(a, b)
+        out = out if out is not None else self._new(groups, 2, a)
+        hs, n, ip, _keep = self._key_sets(key_sets, key_index, groups)
+        _check(_lib.load().hipbfv_batch_multiply_sum_relin_keys(self._h, _ptr(a), _ptr(b), hs, n, ip, _ptr(out), groups, terms, _stream()))
+        return out
+
     def apply_galois_keys(self, ct: torch.Tensor, galois_elt: int, key_sets: Sequence[GaloisKeys], key_index, out: torch.Tensor | None = None) -> torch.Tensor:
         self._shape_ok(ct, 2)
         out = out if out is not None else self._new(ct.shape[0], 2, ct)
@@ -408,3 +439,15 @@ def rotate_items_keys_plan(n: int, steps, key_index, present_sets) -> tuple[list
                                                            offsets.ctypes.data_as(C.POINTER(C.c_uint64)), kind, entry, rounds_of, C.byref(entries),
                                                            C.byref(rounds)))
     return list(kind[: st.size]), list(entry[: st.size]), list(rounds_of[: st.size]), entries.value, rounds.value
+
+
+def multiply_sum_plan(groups: int, terms: int, chunk: int) -> list[tuple[int, int, int, int, bool]]:
+    """The library's launch sequences for multiply_sum / multiply_sum_relin (host only) under a chunk of `chunk` items: per sequence
+    (first group, groups, first term, terms, accumulate).  A chunk is a whole number of groups; a group with more terms than a chunk
+    holds runs alone in slices of `chunk` terms, every slice but the first adding onto the group's sums."""
+    L = _lib.load()
+    n = C.c_uint64()
+    L.hipbfv_debug_multiply_sum_plan(groups, terms, chunk, None, 0, C.byref(n))  # (the count; refused only for a plan that is not empty)
+    buf = (C.c_uint64 * (5 * max(1, n.value)))()
+    _check(L.hipbfv_debug_multiply_sum_plan(groups, terms, chunk, buf, n.value, C.byref(n)))
+    return [(buf[5 * i], buf[5 * i + 1], buf[5 * i + 2], buf[5 * i + 3], bool(buf[5 * i + 4])) for i in range(n.value)]

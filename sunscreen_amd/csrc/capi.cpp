@@ -1827,6 +1827,63 @@ long hipbfv_batch_multiply_relin_keys(void* h, const uint64_t* a, const uint64_t
   return from_status(e->ev->multiply_relin((const u64*)a, (const u64*)b, sel, (u64*)out2, count, (hipStream_t)stream));
 HIPBFV_END
 
+// ---- sums of products with one relinearization per group (include/hipbfv.h) ----
+// the checks the three forms share, in the header's order; the output is wider (narrower) than the inputs: no in-place form
+#define MULTIPLY_SUM_ARGS_OR_RETURN(out, out_size)                                                                          \
+  if (!a || !b || !out) return HIPBFV_E_POINTER;                                                                            \
+  if (!terms) return fail(HIPBFV_E_INVALIDARG, "a sum of products needs at least one term per group");                      \
+  if (groups > 0xFFFFFFFFull || terms > 0xFFFFFFFFull) return fail(HIPBFV_E_INVALIDARG, "too many groups or terms");        \
+  {                                                                                                                         \
+    const size_t w__ = e->ctx->ct_words(2);                                                                                 \
+    if (long hr__ = check_alias(cts(out, e->ctx->ct_words(out_size), groups), {cts(a, w__, groups * terms), cts(b, w__, groups * terms)}, false)) \
+      return hr__;                                                                                                          \
+  }
+
+long hipbfv_batch_multiply_sum(void* h, const uint64_t* a, const uint64_t* b, uint64_t* out3, uint64_t groups, uint64_t terms, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  MULTIPLY_SUM_ARGS_OR_RETURN(out3, 3);
+  if (!groups) return HIPBFV_S_OK;
+  return from_status(e->ev->multiply_sum((const u64*)a, (const u64*)b, (u64*)out3, groups, terms, (hipStream_t)stream));
+HIPBFV_END
+
+long hipbfv_batch_multiply_sum_relin(void* h, const uint64_t* a, const uint64_t* b, void* keys, uint64_t* out2, uint64_t groups, uint64_t terms,
+                                     void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  MULTIPLY_SUM_ARGS_OR_RETURN(out2, 2);
+  if (!groups) return HIPBFV_S_OK;
+  const u64* rk = key_or_null(keys, e, 0);
+  if (!rk) return from_status(kNoKey);
+  return from_status(e->ev->multiply_sum_relin((const u64*)a, (const u64*)b, rk, (u64*)out2, groups, terms, (hipStream_t)stream));
+HIPBFV_END
+
+long hipbfv_batch_multiply_sum_relin_keys(void* h, const uint64_t* a, const uint64_t* b, void* const* key_sets, uint64_t num_sets,
+                                          const uint32_t* key_index, uint64_t* out2, uint64_t groups, uint64_t terms, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  MULTIPLY_SUM_ARGS_OR_RETURN(out2, 2);
+  const uint64_t count = groups;  // (one key per GROUP)
+  KEYSETS_OR_RETURN();
+  if (!groups) return HIPBFV_S_OK;
+  KEYSEL_OR_RETURN(sel, 0);
+  return from_status(e->ev->multiply_sum_relin((const u64*)a, (const u64*)b, sel, (u64*)out2, groups, terms, (hipStream_t)stream));
+HIPBFV_END
+
+// the launch sequences of the two calls above for a chunk of `chunk` items (Evaluator::set_chunk_ops), host only
+long hipbfv_debug_multiply_sum_plan(uint64_t groups, uint64_t terms, uint64_t chunk, uint64_t* steps5, uint64_t capacity, uint64_t* count) HIPBFV_BEGIN
+  if (!count || (!steps5 && capacity)) return HIPBFV_E_POINTER;
+  if (!terms || !chunk) return fail(HIPBFV_E_INVALIDARG, "terms and chunk must not be zero");
+  uint64_t nsteps = 0;
+  (void)plan_multiply_sum(groups, terms, std::min<uint64_t>(chunk, 65535), [&](const MulSumStep& st) {
+    if (nsteps < capacity) {
+      uint64_t* o = steps5 + nsteps * 5;
+      o[0] = st.group0, o[1] = st.groups, o[2] = st.term0, o[3] = st.terms, o[4] = st.accumulate ? 1 : 0;
+    }
+    nsteps++;
+    return 0;
+  });
+  *count = nsteps;
+  return nsteps <= capacity ? HIPBFV_S_OK : fail(HIPBFV_E_INVALIDARG, "the plan has more steps than `capacity`; *count says how many");
+HIPBFV_END
+
 long hipbfv_batch_apply_galois_keys(void* h, const uint64_t* ct2, uint32_t elt, void* const* key_sets, uint64_t num_sets,
                                     const uint32_t* key_index, uint64_t* out2, uint64_t count, void* stream) HIPBFV_BEGIN
   EVAL_OR_RETURN(h);

@@ -153,7 +153,7 @@ const char* kernel_name(int id) {
   static const char* names[kKernCount] = {"ntt_fwd",   "ntt_inv",    "behz_extend", "tensor",  "behz_floor_sk", "ks_decompose",
                                           "ks_mac",    "ks_moddown", "galois",      "eltwise", "plain",
                                           "ks_head",    "ks_mid",      "ks_tail", "mul_head",      "mul_mid",
-                                          "mul_tail"};
+                                          "mul_tail",  "mul_tail_sum"};
   return id >= 0 && id < kKernCount ? names[id] : "?";
 }
 
@@ -485,6 +485,84 @@ int Evaluator::relinearize(const u64* ct3, const KeySel& rk, u64* out2, size_t c
     if (rc) return rc;
   }
   return watch ? note_result(out2, 2, K, count, s) : (int)kOk;
+}
+
+// out3[g] = sum_t a[g][t] * b[g][t] (evaluator.hpp).  The path is multiply()'s choice for groups * terms items.
+int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch) {
+  const DevCtx& h = ctx_->host();
+  if (!terms) return kInvalidArg;
+  if (h.logn > 15) return kUnsupported;
+  if (!groups) return kOk;
+  const u32 n = h.n, K = h.K, S = h.S, R = K + S;
+  const u32 kneed = std::max(K, S > 2 ? S - 2 : 0u);
+  const bool split = split_mul_ && (kneed <= 4 || (kneed <= 8 && h.aux_f64)) && h.logn >= 12 && h.logn <= 14 && !few_for_split_mul(groups * terms);
+  const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, split ? 65535 : 65535 / (R * 4)));
+  const size_t in_words = (size_t)2 * K * n, out_words = (size_t)3 * K * n;
+  const size_t cc = std::min(chunk, groups * terms);
+  if (!split) {
+    // multiply() of a chunk's terms into a staging buffer, then the element-wise kernel per group: the same words
+    ScratchGuard sg(pool_, cc * out_words * sizeof(u64), s);
+    if (!sg.p) return kOutOfMemory;
+    u64* stage = (u64*)sg.p;
+    const size_t polys = (size_t)3 * K;
+    const int rc = plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) -> int {
+      const size_t first = st.group0 * terms + st.term0;
+      if (int r = multiply(a + first * in_words, 2, b + first * in_words, 2, stage, st.groups * st.terms, s, false)) return r;
+      for (size_t g = 0; g < st.groups; g++) {
+        u64* o = out3 + (st.group0 + g) * out_words;
+        const u64* t0 = stage + g * st.terms * out_words;
+        size_t t = 0;
+        if (!st.accumulate) {
+          if (st.terms == 1)
+            HB_CHECK(hipMemcpyAsync(o, t0, out_words * sizeof(u64), hipMemcpyDeviceToDevice, s));
+          else
+            HB_LAUNCH(kKernEltwise, polys, launch_eltwise(ctx_->dev(), n, t0, t0 + out_words, o, polys, 0, s));
+          t = st.terms == 1 ? 1 : 2;
+        }
+        for (; t < st.terms; t++) HB_LAUNCH(kKernEltwise, polys, launch_eltwise(ctx_->dev(), n, o, t0 + t * out_words, o, polys, 0, s));
+      }
+      return kOk;
+    });
+    if (rc) return rc;
+    return watch ? note_result(out3, 3, K, groups, s) : (int)kOk;
+  }
+  const size_t ext_words = (size_t)4 * R * n, d_words = (size_t)3 * R * n;
+  ScratchGuard sg(pool_, cc * (ext_words + d_words) * sizeof(u64), s);
+  if (!sg.p) return kOutOfMemory;
+  u64* ext = (u64*)sg.p;
+  u64* D = ext + cc * ext_words;
+  const bool square = a == b;  // sums of squares: the head extends and the middle kernel transforms x once
+  const int rc = plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) -> int {
+    const size_t first = st.group0 * terms + st.term0, c = st.groups * st.terms;
+    HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + first * in_words, b + first * in_words, ext, c, s, square ? 2u : 4u));
+    HB_LAUNCH(kKernMulMid, c, launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square));
+    HB_LAUNCH(kKernMulTailSum, c * 3, launch_mul_tail_sum(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out3 + st.group0 * out_words, st.groups, st.terms, st.accumulate, s));
+    return kOk;
+  });
+  if (rc) return rc;
+  return watch ? note_result(out3, 3, K, groups, s) : (int)kOk;
+}
+
+// one key switch per group: the size-3 sums go through a pooled buffer, chunk_ops() groups at a time
+int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s) {
+  const DevCtx& h = ctx_->host();
+  if (h.KK < 2 || !rk.present()) return kNoKey;
+  if (!terms) return kInvalidArg;
+  if (h.logn > 15) return kUnsupported;
+  if (!groups) return kOk;
+  const size_t K = h.K, n = h.n, block = std::min(groups, chunk_ops_);
+  ScratchGuard sg(pool_, block * 3 * K * n * sizeof(u64), s);
+  if (!sg.p) return kOutOfMemory;
+  u64* sum3 = (u64*)sg.p;
+  for (size_t g0 = 0; g0 < groups; g0 += block) {
+    const size_t c = std::min(block, groups - g0);
+    const size_t off = g0 * terms * 2 * K * n;  // (b == a stays b + off == a + off: the squaring form)
+    if (int rc = multiply_sum(a + off, b + off, sum3, c, terms, s, false)) return rc;
+    KeySel sel = rk;
+    sel.first = rk.first + g0;
+    if (int rc = relinearize(sum3, sel, out2 + g0 * 2 * K * n, c, s, nullptr, false)) return rc;
+  }
+  return note_result(out2, 2, (u32)K, groups, s);
 }
 
 // the all-FP64 fused multiply + relinearize (every SEAL default set up to N = 16384) would run for a batch of `count`

@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
@@ -65,6 +66,7 @@ enum KernelId : int {
   kKernMulHead,
   kKernMulMid,
   kKernMulTail,
+  kKernMulTailSum,
   kKernCount
 };
 const char* kernel_name(int id);
@@ -153,6 +155,30 @@ struct ScratchGuard {
   ScratchGuard& operator=(const ScratchGuard&) = delete;
 };
 
+// The launch sequences of Evaluator::multiply_sum (sums of `terms` products per group, `chunk` items of scratch), decided on the host:
+// step = items [term0, term0 + terms) of the groups [group0, group0 + groups), multiplied together and summed by one launch.
+//  - a chunk is a whole number of groups, max(1, chunk / terms) of them and at most 65535 (the groups are on grid z);
+//  - a group with more terms than a chunk holds runs alone, in slices of `chunk` terms: the first slice writes the group's sums,
+//    the later ones add onto them (accumulate).
+struct MulSumStep {
+  size_t group0, groups, term0, terms;
+  bool accumulate;
+};
+template <class Visit>
+int plan_multiply_sum(size_t groups, size_t terms, size_t chunk, Visit&& visit) {
+  if (!terms || !chunk) return kInvalidArg;
+  if (terms <= chunk) {
+    const size_t per = std::min<size_t>(chunk / terms, 65535);
+    for (size_t g = 0; g < groups; g += per)
+      if (int rc = visit(MulSumStep{g, std::min(per, groups - g), 0, terms, false})) return rc;
+    return 0;
+  }
+  for (size_t g = 0; g < groups; g++)
+    for (size_t t0 = 0; t0 < terms; t0 += chunk)
+      if (int rc = visit(MulSumStep{g, 1, t0, std::min(chunk, terms - t0), t0 != 0})) return rc;
+  return 0;
+}
+
 // Transparent-result watch of the batched path.  While a WatchScope is alive on the calling thread, every Evaluator
 // operation that produces ciphertexts records, in the device word it was given, the smallest batch index whose result is
 // transparent (all polynomials but the first are zero; 0xFFFFFFFF = none): the reference's SEAL build throws on such a
@@ -194,6 +220,14 @@ class Evaluator {
   int multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr,
                      const MemberTail* members = nullptr, u32 per = 0, const MemberHead* heads = nullptr, bool heads_square = false);
   bool member_tail_ok(size_t count) const;
+  // Sums of products with lazy relinearization: a, b = u64[groups][terms][2][K][N] (b == a: sums of squares),
+  // out3[g] = sum_t a[g][t] * b[g][t] as size-3 ciphertexts -- word for word the sum of multiply()'s results (the order of a modular
+  // sum does not matter), written once per group.  Where multiply() takes the split kernels for groups * terms items, the last of them
+  // sums in registers (launch_mul_tail_sum); otherwise multiply() runs into a staging buffer that the element-wise kernel folds.
+  // The launch sequences are plan_multiply_sum's over chunk_ops().  A transparent term inside a non-transparent sum is not seen.
+  int multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch = true);
+  // out2[g] = relinearize(sum_t a[g][t] * b[g][t]): one key switch per GROUP; rk selects per group
+  int multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s);
   // out2 = (sigma_g(c0), 0) + switch_key(sigma_g(c1), key)
   int apply_galois(const u64* ct2, u32 galois_elt, const KeySel& key, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr);
   // every item by its OWN Galois element in one key-switch pass (mixed-step rotation batches): elts / keys are HOST arrays of `count`

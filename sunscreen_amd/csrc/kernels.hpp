@@ -80,6 +80,10 @@ hipError_t launch_mul_mid(const DevCtx* ctx, const MulOp* twf, const MulOp* twi,
                           const unsigned char* res_i, u32 ni, const u64* ext, u64* D, size_t ops, hipStream_t s, bool square = false);
 hipError_t launch_mul_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out,
                            size_t ops, hipStream_t s, u32 poly0 = 0, u32 npolys = 3);
+// the summing form (Evaluator::multiply_sum): D = [groups][terms][3][R][N]; out3[g] = the sum over group g's terms of what launch_mul_tail
+// writes for each (canonical, u64[groups][3][K][N]); accumulate: added onto the rows already in out3.  groups <= 65535 (grid z).
+hipError_t launch_mul_tail_sum(const DevCtx* ctx, const MulOp* twi, u32 logn, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out3,
+                               size_t groups, size_t terms, bool accumulate, hipStream_t s);
 hipError_t launch_mulrelin_head(const DevCtx* ctx, const MulOp* twi, const MulOp* twf, u32 logn, int pack_mul, bool conv_grid, int pack_ks, u32 kneed,
                                 const u64* D, u64* T, size_t ops, hipStream_t s);
 // Per-member epilogue of a MERGED multiply + relinearize launch (the graph executor's members x batch items): item i of the launch is

@@ -2359,6 +2359,178 @@ __global__ EDGE_BOUNDS(KMAX) void mul_tail_kernel(const DevCtx* __restrict__ ctx
 }
 
 // -------------------------------------------------------------------------------------------------
+// mul tail, summing form (Evaluator::multiply_sum: sum_t a_t * b_t with one relinearization per group): grid (N/4/256, 3 polys, groups);
+// D = [groups][terms][3][R][N] as launch_mul_mid leaves it, out = [groups][3][K][N] canonical.  A thread owns the four coefficients
+// {t + k*N/4} of ONE product polynomial of ONE group and walks the group's terms.  The floor + Shenoy-Kumaresan step is a rounding per
+// product, so every term is finished on its own, by the device functions mul_tail_kernel finishes it with; the canonical residues are
+// then summed mod q_i in registers (every summand is below q_i <= 2^61: one add, one conditional subtract, no overflow) and stored
+// once per group: the 3 K rows of a term never travel through HBM.
+// accumulate: the sums start from the words already in out (a group longer than a chunk arrives in slices); otherwise out is only written.
+// The sums are held as acc[k][i] = residue i of coefficient slot k.
+template <int L, int KMAX>
+__device__ __forceinline__ void mul_tail_sum_term_int(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base, const u64* __restrict__ d, u32 t,
+                                                      u64 (&acc)[4][KMAX]) {
+  // the integer base: mul_tail_kernel's general arm -- the same walk over the K + S rows of D with the next row requested before the
+  // current one is transformed, then one coefficient per trip through behz_floor_sk_coeff
+  constexpr u32 N = 1u << L;
+  const u32 K = ctx->K, S = ctx->S, KK = ctx->KK;
+  u64 y[4][KMAX], xb[4][KMAX + 2];
+  const u32 last_row = K + S - 1;
+  const BufRsrc rd = buf_rsrc(d);
+  u64 cur[4], nxt[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) cur[k] = ld_tail_in<L>(buf_row(rd, 0), t, k);
+#pragma unroll
+  for (int i = 0; i < KMAX; i++) {
+    {
+      const u32 nr = (u32)i + 1 < K ? (u32)i + 1 : K;
+      const BufRow next_row = buf_row(rd, (size_t)(nr < last_row ? nr : last_row) * N);
+#pragma unroll
+      for (int k = 0; k < 4; k++) nxt[k] = ld_tail_in<L>(next_row, t, k);
+    }
+    if ((u32)i < K) {
+      const DevMod& dm = ctx->mod[i];
+      u64 r4[4];
+      if (residue_is_f64(dm)) {
+        const ArithD ar(dm);
+        tail_inv4_scale_raw<ArithD, L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->intt_scale_q_d[i], dm.split_inv_mask, r4);
+      } else {
+        const ArithI ar(dm);
+        tail_inv4_scale_raw<ArithI, L>(ar, cur, t, twi_base + (size_t)i * N, ctx->intt_scale_q[i], 0u, r4);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) y[k][i] = r4[k];
+#pragma unroll
+      for (int k = 0; k < 4; k++) cur[k] = nxt[k];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KMAX + 2; j++) {
+    {
+      const u32 nr = K + (u32)j + 1;
+      const BufRow next_row = buf_row(rd, (size_t)(nr < last_row ? nr : last_row) * N);
+#pragma unroll
+      for (int k = 0; k < 4; k++) nxt[k] = ld_tail_in<L>(next_row, t, k);
+    }
+    if ((u32)j < S) {
+      const DevMod& dm = ctx->mod[KK + j];
+      u64 r4[4];
+      const ArithI ar(dm);
+      tail_inv4_scale_raw<ArithI, L>(ar, cur, t, twi_base + (size_t)(KK + j) * N, ctx->intt_scale_bsk[j], 0u, r4);
+#pragma unroll
+      for (int k = 0; k < 4; k++) xb[k][j] = r4[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) cur[k] = nxt[k];
+  }
+  // a rolled loop must not index y / xb / acc by k (dynamic indexing puts them in scratch): each trip consumes row 0 and the rows
+  // rotate down; the sums rotate all the way round, so after four trips acc is in order again
+#pragma unroll 1
+  for (int k = 0; k < 4; k++) {
+    u64 r[KMAX], a0[KMAX];
+    behz_floor_sk_coeff<KMAX>(ctx, y[0], xb[0], r);
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) a0[i] = (u32)i < K ? add_mod(acc[0][i], r[i], ctx->mod[i].q) : 0ull;
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++) {
+#pragma unroll
+      for (int i = 0; i < KMAX; i++) y[kk][i] = y[kk + 1][i], acc[kk][i] = acc[kk + 1][i];
+#pragma unroll
+      for (int j = 0; j < KMAX + 2; j++) xb[kk][j] = xb[kk + 1][j];
+    }
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) acc[3][i] = a0[i];
+  }
+}
+
+// The 8-prime instantiations sum THROUGH the output rows instead: with 64 registers of sums beside mul_tail_compute_d<.., 8, ..> they
+// need 298 ... 316 registers -- one wave per SIMD where mul_tail_kernel runs two -- and mul_tail_sum took 5.53 ms against
+// mul_tail's 3.38 ms + 1.42 ms of additions (n = 16384, 128 groups x 8 terms); bounded to two waves per SIMD they spill 172 ... 244 bytes.
+// So every term adds onto the group's words in out and writes them back (the first one onto zeros: the descriptor without records).  The
+// 64 KB a workgroup owns are its own from one term to the next and stay in its XCD's L2; the registers are mul_tail_kernel's.
+template <int KMAX>
+constexpr bool kTailSumThroughOut = KMAX > 4;
+template <int L, int KMAX, bool AUXD, int PACK, bool GRID>
+__global__ __launch_bounds__(kHeadThreads, (kTailSumThroughOut<KMAX> ? 2 : 1)) void mul_tail_sum_kernel(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base, const u64* __restrict__ D,
+                                                      u64* __restrict__ out, u32 terms, u32 accumulate) {
+  constexpr u32 N = 1u << L;
+  constexpr bool mixed = !AUXD && PACK;
+  static_assert(!mixed || TAIL_MIXED_NC == 4, "the mixed summing tail finishes four coefficients at once (mul_tail_compute_mixed)");
+  const u32 t = blockIdx.x * kHeadThreads + threadIdx.x;
+  const u32 poly = blockIdx.y, group = blockIdx.z;
+  const u32 K = ctx->K, R = K + ctx->S;
+  u64* o = out + ((size_t)group * 3 + poly) * K * N;
+  if constexpr (kTailSumThroughOut<KMAX>) {
+    static_assert(AUXD, "only the all-FP64 instantiation exists for 5..8 data primes");
+    const BufRsrc ro = buf_rsrc(o);
+    const u64* d = D + ((size_t)group * terms * 3 + poly) * R * N;
+#pragma unroll 1
+    for (u32 term = 0; term < terms; term++, d += (size_t)3 * R * N) {
+      u64 res[KMAX][4];
+      mul_tail_compute_d<L, KMAX, PACK, GRID>(ctx, twi_base, d, t, res);
+      const BufRsrc rin = buf_rsrc_opt(o, (accumulate | term) != 0);
+#pragma unroll
+      for (int i = 0; i < KMAX; i++)
+        if ((u32)i < K) {
+          const u64 q = ctx->mod[i].q;
+          u64 w[4];
+#pragma unroll
+          for (int k = 0; k < 4; k++) w[k] = ld_tail_out<L>(buf_row(rin, (size_t)i * N), t, k);
+#pragma unroll
+          for (int k = 0; k < 4; k++) st_tail_out<L>(buf_row(ro, (size_t)i * N), t, k, add_mod(w[k], res[i][k], q));
+        }
+    }
+    return;
+  }
+  u64 acc[4][KMAX];
+  {
+    // without `accumulate` the descriptor has no records: the loads return 0 and touch no memory (buf_rsrc_opt)
+    const BufRsrc rin = buf_rsrc_opt(o, accumulate != 0);
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) {
+      const BufRow row = buf_row(rin, (size_t)((u32)i < K ? (u32)i : K - 1) * N);
+#pragma unroll
+      for (int k = 0; k < 4; k++) acc[k][i] = ld_tail_out<L>(row, t, k);
+    }
+  }
+  const size_t term_words = (size_t)3 * R * N;
+  const u64* d = D + ((size_t)group * terms * 3 + poly) * R * N;
+#pragma unroll 1
+  for (u32 term = 0; term < terms; term++, d += term_words) {
+    if constexpr (AUXD) {
+      u64 res[KMAX][4];
+      mul_tail_compute_d<L, KMAX, PACK, GRID>(ctx, twi_base, d, t, res);
+#pragma unroll
+      for (int i = 0; i < KMAX; i++)
+        if ((u32)i < K) {
+          const u64 q = ctx->mod[i].q;
+#pragma unroll
+          for (int k = 0; k < 4; k++) acc[k][i] = add_mod(acc[k][i], res[i][k], q);
+        }
+    } else if constexpr (mixed) {
+      u64 res[4][KMAX];
+      mul_tail_compute_mixed<L, KMAX>(ctx, twi_base, d, t, res);
+#pragma unroll
+      for (int i = 0; i < KMAX; i++)
+        if ((u32)i < K) {
+          const u64 q = ctx->mod[i].q;
+#pragma unroll
+          for (int k = 0; k < 4; k++) acc[k][i] = add_mod(acc[k][i], res[k][i], q);
+        }
+    } else {
+      mul_tail_sum_term_int<L, KMAX>(ctx, twi_base, d, t, acc);
+    }
+  }
+  const BufRsrc ro = buf_rsrc(o);
+#pragma unroll
+  for (int i = 0; i < KMAX; i++)
+    if ((u32)i < K) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) st_tail_out<L>(buf_row(ro, (size_t)i * N), t, k, acc[k][i]);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // multiply + relinearize, last kernel: ks_tail whose base ciphertext (c0, c1 of the product) is computed in place from the
 // multiply's intermediates D instead of being read back: c0 and c1 never travel through HBM (1 MB of the 12 MB a mul+relin
 // moves at N = 8192).  Thread t of polynomial c owns the same coefficients {t + k*N/4} in both halves.  All-FP64 contexts
@@ -3065,6 +3237,33 @@ static hipError_t mul_tail_t(const DevCtx* ctx, const MulOp* twi, bool aux_f64, 
 hipError_t launch_mul_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out,
                            size_t ops, hipStream_t s, u32 poly0, u32 npolys) {
   SPLIT_DISPATCH(mul_tail_t, ctx, twi, aux_f64, pack, conv_grid && aux_f64, kneed, D, out, ops, poly0, npolys, s)
+}
+
+// the instantiations of mul_tail_t, summing over the terms of a group
+template <int L>
+static hipError_t mul_tail_sum_t(const DevCtx* ctx, const MulOp* twi, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out3, size_t groups,
+                                 size_t terms, bool accumulate, hipStream_t s) {
+  const dim3 grid((1u << L) / 4 / kHeadThreads, 3, (unsigned)groups);
+#define MTS(KM, AD, PK, GR) mul_tail_sum_kernel<L, KM, AD, PK, GR><<<grid, kHeadThreads, 0, s>>>(ctx, twi, D, out3, (u32)terms, accumulate ? 1u : 0u)
+  if (kneed > 4) {
+    if (pack == 2) { if (conv_grid) MTS(8, true, 2, true); else MTS(8, true, 2, false); }
+    else if (pack) { if (conv_grid) MTS(8, true, 1, true); else MTS(8, true, 1, false); }
+    else { if (conv_grid) MTS(8, true, 0, true); else MTS(8, true, 0, false); }
+  } else if (aux_f64) {
+    if (pack == 2) return hipErrorInvalidValue;
+    if (pack) MTS(4, true, 1, false); else MTS(4, true, 0, false);
+  } else if (pack) {  // mixed base
+    MTS(4, false, 1, false);
+  } else {
+    MTS(4, false, 0, false);
+  }
+#undef MTS
+  return hipGetLastError();
+}
+hipError_t launch_mul_tail_sum(const DevCtx* ctx, const MulOp* twi, u32 logn, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out3,
+                               size_t groups, size_t terms, bool accumulate, hipStream_t s) {
+  if (!groups || groups > 65535 || !terms || terms > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  SPLIT_DISPATCH(mul_tail_sum_t, ctx, twi, aux_f64, pack, conv_grid && aux_f64, kneed, D, out3, groups, terms, accumulate, s)
 }
 
 template <int L>
