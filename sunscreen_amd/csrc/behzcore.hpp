@@ -494,7 +494,9 @@ __device__ __forceinline__ void behz_extend_multi_mixed(const DevCtx* __restrict
 // the register copies that come with it cancel the saving (ISA count).
 // OutT: u64 (canonical words, for a kernel that stores them) or double (the same canonical integers kept as doubles for a fused
 // consumer -- the key-switch head's digits, the mod-down's base -- that would convert them straight back: r05)
-template <int KMAX, int NC, bool GRID, class Raw, class Fetch, class Finish, class OutT>
+// ONE_IP: q^-1 and (B/B_j)^-1 as ONE constant product for the primes of B (DevCtx::inv_q_ip_mod_bsk_d) -- the value between the two
+// products was used nowhere else; the m_sk row keeps q^-1 alone.  Same canonical y_b (tests/native/tailfold_check.cpp).
+template <int KMAX, int NC, bool GRID, bool ONE_IP, class Raw, class Fetch, class Finish, class OutT>
 __device__ __forceinline__ void behz_floor_sk_multi_d(const DevCtx* __restrict__ ctx, const double (&yc)[KMAX][NC], Fetch&& fetch, Finish&& finish,
                                                       OutT (&out)[KMAX][NC]) {
   const u32 K = ctx->K, S = ctx->S, KK = ctx->KK, nB = ctx->nB;
@@ -518,7 +520,7 @@ __device__ __forceinline__ void behz_floor_sk_multi_d(const DevCtx* __restrict__
     double cq[KMAX], cb[KMAX];
 #pragma unroll
     for (int i = 0; i < KMAX; i++) cq[i] = ctx->q_to_bsk_d[j][i], cb[i] = ctx->B_to_q_d[i][j];
-    MulOpD invq = ctx->inv_q_mod_bsk_d[j], ip = ctx->inv_punct_B_d[j];
+    MulOpD invq = ctx->inv_q_mod_bsk_d[j], ip = ONE_IP ? ctx->inv_q_ip_mod_bsk_d[j] : ctx->inv_punct_B_d[j];
     double bm = ctx->B_to_msk_d[j];
     {
       double unused = 0.0;
@@ -560,12 +562,12 @@ __device__ __forceinline__ void behz_floor_sk_multi_d(const DevCtx* __restrict__
       }
     }
 #pragma unroll
-    for (int k = 0; k < NC; k++) fl[k] = ar.mul_const(ar.reduce(fl[k]), invq);
+    for (int k = 0; k < NC; k++) fl[k] = ONE_IP ? ar.reduce(fl[k]) : ar.mul_const(ar.reduce(fl[k]), invq);
     if (j < nB) {
       const ArithD am(ctx->mod[KK + nB]);
 #pragma unroll
       for (int k = 0; k < NC; k++) {
-        fl[k] = canonical_d(ar, ar.mul_const(fl[k], ip));  // yb_j, canonical
+        fl[k] = canonical_d(ar, ar.mul_const(fl[k], ip));  // yb_j = fl * q^-1 * (B/B_j)^-1, canonical
         amsk[k] += am.mul_var(fl[k], bm);
       }
 #pragma unroll
@@ -579,7 +581,7 @@ __device__ __forceinline__ void behz_floor_sk_multi_d(const DevCtx* __restrict__
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < NC; k++) flm[k] = fl[k];
+      for (int k = 0; k < NC; k++) flm[k] = ONE_IP ? ar.mul_const(fl[k], invq) : fl[k];
     }
   }
   const ArithD am(ctx->mod[KK + nB]);

@@ -629,6 +629,34 @@ Context* Context::create(u32 n, const std::vector<u64>& key_primes, u64 t, int d
     invm(prod_mod(B, m_sk), m_sk, &inv);
     h.inv_B_mod_msk = make_mulop(inv, m_sk);
   }
+  {
+    // the tails' scaling folded into their last two inverse stages (devctx.hpp TailFoldD, moddown_d.hpp tail_fold4_d): per
+    // FP64-policy modulus and scale kind, the scaling times the three twiddles of the tail's window
+    auto fold = [&](u32 m, u64 sc) {
+      const u64 p = all[m];
+      u64 tw[4] = {0, 0, 0, 0};
+      for (u32 k = 1; k < 4; k++) {
+        double d;
+        std::memcpy(&d, reinterpret_cast<const double*>(&twi[(size_t)m * n]) + k, sizeof(double));
+        tw[k] = (u64)d;
+      }
+      TailFoldD f;
+      f.sc = make_mulop_d(sc, p);
+      f.tw1sc = make_mulop_d(mulm(tw[1], sc, p), p);
+      f.tw2sc = make_mulop_d(mulm(tw[2], sc, p), p);
+      f.tw3sc = make_mulop_d(mulm(tw[3], sc, p), p);
+      f.tw1 = make_mulop_d(tw[1], p);
+      return f;
+    };
+    for (u32 i = 0; i < KK; i++)
+      if (h.mod[i].use_f64) h.tail_fold_key[i] = fold(i, h.mod[i].ninv.w);
+    for (u32 i = 0; i < K; i++)
+      if (h.mod[i].use_f64) h.tail_fold_q[i] = fold(i, h.intt_scale_q[i].w);
+    for (u32 j = 0; j < h.S; j++)
+      if (h.mod[KK + j].use_f64) h.tail_fold_bsk[j] = fold(KK + j, h.intt_scale_bsk[j].w);
+    // the floor's product by q^-1 followed, for the primes of B, by the one by (B/B_j)^-1: one constant
+    for (u32 j = 0; j < h.nB; j++) h.inv_q_ip_mod_bsk_d[j] = make_mulop_d(mulm(h.inv_q_mod_bsk[j].w, h.inv_punct_B[j].w, B[j]), B[j]);
+  }
 
   if (h.aux_f64) {
     for (u32 i = 0; i < K; i++) {

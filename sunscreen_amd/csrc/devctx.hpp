@@ -29,6 +29,17 @@ struct MulOpD {
   double wq;
 };
 
+// The constants of a tail whose scaling product is folded into its two inverse stages (twiddles tw1 = tw_inv[1], tw2 = tw_inv[2],
+// tw3 = tw_inv[3] of the modulus, sc the tail's fixed scaling): in a Gentleman-Sande butterfly the product sits on the difference
+// output, so every output but the all-sums one has a twiddle product on its path that can carry sc.
+struct TailFoldD {
+  MulOpD sc;     // sc                (the all-sums output)
+  MulOpD tw1sc;  // tw1 * sc mod q    (second stage, difference of the two sums)
+  MulOpD tw2sc;  // tw2 * sc mod q    (first stage, pair 0/1)
+  MulOpD tw3sc;  // tw3 * sc mod q    (first stage, pair 2/3)
+  MulOpD tw1;    // tw1               (second stage, difference of the two scaled differences)
+};
+
 // flags in DevMod::split_fwd_mask / split_inv_mask beside the per-pass reduce bits (context.cpp plan_f64_split)
 constexpr u32 kPlanStoreReduce = 1u << 30;  // fwd: the head's outputs / inv: the middle kernel's outputs exceed the 48-bit packed range
                                             // unless reduced in front of the store (packed rows only; 8-byte rows never reduce there)
@@ -176,6 +187,14 @@ struct DevCtx {
   u64 t_half_up;                       // (t + 1) >> 1
   u32 fast_plain_lift;                 // t < every q_i
   u32 pad2;
+
+  // ---- the tails' fixed scaling folded into their last two inverse stages (moddown_d.hpp tail_fold4_d); appended, so that every
+  // field above keeps its offset.  Valid for FP64-policy moduli: key prime J with n^-1 (the key switch's accumulator rows), data
+  // prime i with intt_scale_q (the multiply's data rows), auxiliary prime j with intt_scale_bsk ----
+  TailFoldD tail_fold_key[kMaxKey];
+  TailFoldD tail_fold_q[kMaxKey];
+  TailFoldD tail_fold_bsk[kMaxBsk];
+  MulOpD inv_q_ip_mod_bsk_d[kMaxBsk];  // q^{-1} * (B/B_j)^{-1} mod B_j, j < nB: the floor's two consecutive constant products as one
 };
 
 // The invariant-noise measure (kernels_client.hip noise_partial_kernel; SEAL Decryptor::invariant_noise_budget) of one context: its own

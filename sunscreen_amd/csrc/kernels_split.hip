@@ -1310,6 +1310,42 @@ __device__ __forceinline__ void tail_inverse4(const A& ar, typename A::V (&v)[4]
   ar.inv(v[1], v[3], tw[1]);
 }
 
+// The FP64 tails' inverse stages AND their fixed scaling `c.sc` on the 4 values thread t holds, the scaling folded into the stage
+// constants (moddown_d.hpp tail_fold4_d: five constant products where tail_inverse4 + four scaling products take eight).  Out:
+// v[0], v[2], v[3] as the scaling product left them -- |v| < q, reduced under kPlanScaleReduce like the scaling product was;
+// v[1] is a sum of two such products: |v[1]| <= 2q, what mod_down_d takes as it is (REDUCE1 = false); a consumer that makes
+// its values canonical with ONE conditional add, or states |v| < q, asks for it reduced (REDUCE1 = true).
+// The lane-split geometry (three stages across a lane pair) keeps the unfolded form.
+template <int L, bool REDUCE1>
+__device__ __forceinline__ void tail_inv_scale_fold_d(const ArithD& ar, double (&v)[4], const double* __restrict__ tw, const TailFoldD& c, u32 mask, u32 t) {
+  if constexpr (EdgeGeom<L>::SPLIT) {
+    tail_inv_owned<ArithD, L>(ar, v, tw, mask, t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = ar.mul_const(v[k], c.sc);
+    if (mask & kPlanScaleReduce) {
+      HIPBFV_KEEP_BRANCH();
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = ar.reduce(v[k]);
+    }
+  } else {
+    if ((mask >> 8) & 1u) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = ar.reduce(v[k]);
+    }
+    if ((mask >> 24) & 1u) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = ar.reduce(v[k]);
+    }
+    tail_fold4_d(ar.q, c, v);
+    if (mask & kPlanScaleReduce) {
+      HIPBFV_KEEP_BRANCH();
+      v[0] = ar.reduce(v[0]), v[2] = ar.reduce(v[2]), v[3] = ar.reduce(v[3]);
+      if constexpr (!REDUCE1) v[1] = ar.reduce(v[1]);
+    }
+    if constexpr (REDUCE1) v[1] = ar.reduce(v[1]);
+  }
+}
+
 // The special-prime residue of a key-switch accumulator as the mod-down wants it: tl = (a * n^-1 mod p + floor(p/2)) mod p, the
 // canonical integer in [0, p), as a double (moddown_d.hpp) -- formed in FP64 from the four values the middle kernel left
 // (r05: it used to go through a canonical u64 and a 64-bit add_mod, and back)
@@ -1317,16 +1353,9 @@ template <int L>
 __device__ __forceinline__ void tail_special_d(const DevCtx* __restrict__ ctx, const DevMod& sp, double (&v)[4], const double* __restrict__ tw, u32 t,
                                                double (&tld)[4]) {
   const ArithD ar(sp);
-  tail_inv_owned<ArithD, L>(ar, v, tw, sp.split_inv_mask, t);
+  tail_inv_scale_fold_d<L, true>(ar, v, tw, ctx->tail_fold_key[ctx->KK - 1], sp.split_inv_mask, t);
   const double half = ArithD::from_u64(ctx->qsp_half);
-  double s[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) s[k] = ar.mul_const(v[k], sp.ninv_d);
-  if (sp.split_inv_mask & kPlanScaleReduce) {
-    HIPBFV_KEEP_BRANCH();
-#pragma unroll
-    for (int k = 0; k < 4; k++) s[k] = ar.reduce(s[k]);
-  }
+  const double(&s)[4] = v;
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     double c = s[k] < 0.0 ? s[k] + ar.q : s[k];  // canonical: |s| < p
@@ -1397,20 +1426,14 @@ __global__ __launch_bounds__(kHeadThreads) void ks_tail_kernel(const DevCtx* __r
       double v[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) v[k] = nat_unpack<PACK>(cur[k]);
-      tail_inv_owned<ArithD, L>(ar, v, reinterpret_cast<const double*>(twi_base + (size_t)J * N), mj.split_inv_mask, t);
+      // (n^-1 folded into the stage constants; mod_down_d wants |s| <= 2q, which the sum output satisfies unreduced)
+      tail_inv_scale_fold_d<L, false>(ar, v, reinterpret_cast<const double*>(twi_base + (size_t)J * N), ctx->tail_fold_key[J], mj.split_inv_mask, t);
       // the mod-down in exact FP64 on the representative the transform leaves (moddown_d.hpp): no canonical u64 of `a`, no 64-bit
       // Barrett / Shoup chain per output value
       const MulOpD iw = ctx->inv_qsp_mod_q_d[J];
       const double hf = ctx->qsp_half_mod_q_d[J];
       const bool p_above_q = qsp > mj.q;
-      double s[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) s[k] = ar.mul_const(v[k], mj.ninv_d);
-      if (mj.split_inv_mask & kPlanScaleReduce) {  // mod_down_d wants |s| <= 2q
-        HIPBFV_KEEP_BRANCH();
-#pragma unroll
-        for (int k = 0; k < 4; k++) s[k] = ar.reduce(s[k]);
-      }
+      const double(&s)[4] = v;
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const double bd = ArithD::from_u64(bw[k]) + ArithD::from_u64(ex[k]);  // the base ciphertext + a fused Add node's (absent: 0)
@@ -2031,22 +2054,28 @@ __device__ __forceinline__ void tail_inv4_scale_raw(const A& ar, const u64 (&raw
   for (int k = 0; k < 4; k++) out[k] = ar.scale_canonical(v[k], sc);
 }
 
-// the same for the FP64 epilogue: doubles out with |out| < q -- the scaling product as ArithD::mul_const leaves it, q * (0.5 + |v| * 2^-52),
-// which the range plan keeps below 0.95 q for every prime without kPlanScaleReduce (context.cpp); reduced first otherwise
-template <int L, bool PACK>
-__device__ __forceinline__ void tail_inv4_scale_d(const ArithD& ar, const NatRaw<PACK> (&raw)[4], const double* __restrict__ tw, const MulOpD& sc,
-                                                  u32 mask, u32 t, double (&out)[4]) {
+// the FP64 rows of the same (the mixed kernels' auxiliary rows, the stand-alone mixed tail): the scaling folded into the stage
+// constants (tail_inv_scale_fold_d), every output reduced and made canonical as ArithD::scale_canonical did
+template <int L>
+__device__ __forceinline__ void tail_inv4_fold_raw_d(const ArithD& ar, const u64 (&raw)[4], u32 t, const double* __restrict__ tw, const TailFoldD& c,
+                                                     u32 mask, u64 (&out)[4]) {
   double v[4];
 #pragma unroll
-  for (int k = 0; k < 4; k++) v[k] = nat_unpack<PACK>(raw[k]);
-  tail_inv_owned<ArithD, L>(ar, v, tw, mask, t);
+  for (int k = 0; k < 4; k++) v[k] = __longlong_as_double((long long)raw[k]);
+  tail_inv_scale_fold_d<L, false>(ar, v, tw, c, mask & ~kPlanScaleReduce, t);
 #pragma unroll
-  for (int k = 0; k < 4; k++) out[k] = ar.mul_const(v[k], sc);
-  if (mask & kPlanScaleReduce) {
-    HIPBFV_KEEP_BRANCH();
+  for (int k = 0; k < 4; k++) out[k] = ar.canonical(v[k]);
+}
+
+// the same for the FP64 epilogue: doubles out with |out| < q -- the scaling product as ArithD::mul_const leaves it, q * (0.5 + |v| * 2^-52),
+// which the range plan keeps below 0.95 q for every prime without kPlanScaleReduce (context.cpp); reduced first otherwise.  The scaling is
+// folded into the stage constants `c` (tail_inv_scale_fold_d); the one output that is a sum of two products is reduced
+template <int L, bool PACK>
+__device__ __forceinline__ void tail_inv4_scale_d(const ArithD& ar, const NatRaw<PACK> (&raw)[4], const double* __restrict__ tw, const TailFoldD& c,
+                                                  u32 mask, u32 t, double (&out)[4]) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = ar.reduce(out[k]);
-  }
+  for (int k = 0; k < 4; k++) out[k] = nat_unpack<PACK>(raw[k]);
+  tail_inv_scale_fold_d<L, true>(ar, out, tw, c, mask, t);
 }
 
 // mul tail: grid (N/4/256, 3 polys, ops); out = [ops][3][K][N] canonical
@@ -2083,7 +2112,7 @@ __device__ __forceinline__ void mul_tail_compute_d(const DevCtx* __restrict__ ct
         const DevMod& dm = ctx->mod[i];
         const ArithD ar(dm);
         double r4[4];
-        tail_inv4_scale_d<L, PD>(ar, cur, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->intt_scale_q_d[i], dm.split_inv_mask, t, r4);
+        tail_inv4_scale_d<L, PD>(ar, cur, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->tail_fold_q[i], dm.split_inv_mask, t, r4);
 #pragma unroll
         for (int k = 0; k < 4; k++) yc[i][k] = r4[k] < 0.0 ? r4[k] + ar.q : r4[k];  // canonical: |r4| < q
       }
@@ -2128,12 +2157,12 @@ __device__ __forceinline__ void mul_tail_compute_d(const DevCtx* __restrict__ ct
           NatRaw<true> raw[4];
 #pragma unroll
           for (int k = 0; k < 4; k++) raw[k].lo = cur[k].lo, raw[k].hi = cur[k].hi;
-          tail_inv4_scale_d<L, true>(ar, raw, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->intt_scale_q_d[i], dm.split_inv_mask, t, r4);
+          tail_inv4_scale_d<L, true>(ar, raw, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->tail_fold_q[i], dm.split_inv_mask, t, r4);
         } else {
           NatRaw<false> raw[4];
 #pragma unroll
           for (int k = 0; k < 4; k++) raw[k].d = __hiloint2double((int)cur[k].hi, (int)cur[k].lo);
-          tail_inv4_scale_d<L, false>(ar, raw, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->intt_scale_q_d[i], dm.split_inv_mask, t, r4);
+          tail_inv4_scale_d<L, false>(ar, raw, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->tail_fold_q[i], dm.split_inv_mask, t, r4);
         }
 #pragma unroll
         for (int k = 0; k < 4; k++) yc[i][k] = r4[k] < 0.0 ? r4[k] + ar.q : r4[k];  // canonical: |r4| < q
@@ -2142,7 +2171,9 @@ __device__ __forceinline__ void mul_tail_compute_d(const DevCtx* __restrict__ ct
       for (int k = 0; k < 4; k++) cur[k] = nxt[k];
     }
   }
-  behz_floor_sk_multi_d<KMAX, 4, GRID, NatRaw<PA>>(
+  // (the lane-split geometry keeps the floor's two constant products, as it keeps the unfolded tail stages: with one product the
+  // 8-prime summing tail of that geometry spilt three registers)
+  behz_floor_sk_multi_d<KMAX, 4, GRID, !G::SPLIT, NatRaw<PA>>(
       ctx, yc,
       [&](u32 j, NatRaw<PA>(&raw)[4]) {
 #pragma unroll
@@ -2150,7 +2181,7 @@ __device__ __forceinline__ void mul_tail_compute_d(const DevCtx* __restrict__ ct
       },
       [&](u32 j, const NatRaw<PA>(&raw)[4], double(&xb)[4]) {
         const DevMod& dm = ctx->mod[KK + j];
-        tail_inv4_scale_d<L, PA>(ArithD(dm), raw, reinterpret_cast<const double*>(twi_base + (size_t)(KK + j) * N), ctx->intt_scale_bsk_d[j],
+        tail_inv4_scale_d<L, PA>(ArithD(dm), raw, reinterpret_cast<const double*>(twi_base + (size_t)(KK + j) * N), ctx->tail_fold_bsk[j],
                                    dm.split_inv_mask, t, xb);
       },
       res);
@@ -2183,7 +2214,7 @@ __device__ __forceinline__ void mul_tail_compute_mixed(const DevCtx* __restrict_
       u64 r4[4];
       if (residue_is_f64(dm)) {
         const ArithD ar(dm);
-        tail_inv4_scale_raw<ArithD, L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->intt_scale_q_d[i], dm.split_inv_mask, r4);
+        tail_inv4_fold_raw_d<L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->tail_fold_q[i], dm.split_inv_mask, r4);
       } else {
         const ArithI ar(dm);
         tail_inv4_scale_raw<ArithI, L>(ar, cur, t, twi_base + (size_t)i * N, ctx->intt_scale_q[i], 0u, r4);
@@ -2206,7 +2237,7 @@ __device__ __forceinline__ void mul_tail_compute_mixed(const DevCtx* __restrict_
       const DevMod& dm = ctx->mod[KK + j];
       u64 r4[4];
       const ArithD ar(dm);  // the auxiliary rows come back from the FP64 middle kernel as doubles
-      tail_inv4_scale_raw<ArithD, L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)(KK + j) * N), ctx->intt_scale_bsk_d[j], dm.split_inv_mask, r4);
+      tail_inv4_fold_raw_d<L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)(KK + j) * N), ctx->tail_fold_bsk[j], dm.split_inv_mask, r4);
 #pragma unroll
       for (int k = 0; k < 4; k++) xb[k][j] = r4[k];
     }
@@ -2274,7 +2305,7 @@ __global__ EDGE_BOUNDS(KMAX) void mul_tail_kernel(const DevCtx* __restrict__ ctx
       u64 r4[4];
       if (residue_is_f64(dm)) {
         const ArithD ar(dm);
-        tail_inv4_scale_raw<ArithD, L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->intt_scale_q_d[i], dm.split_inv_mask, r4);
+        tail_inv4_fold_raw_d<L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->tail_fold_q[i], dm.split_inv_mask, r4);
       } else {
         const ArithI ar(dm);
         tail_inv4_scale_raw<ArithI, L>(ar, cur, t, twi_base + (size_t)i * N, ctx->intt_scale_q[i], 0u, r4);
@@ -2298,7 +2329,7 @@ __global__ EDGE_BOUNDS(KMAX) void mul_tail_kernel(const DevCtx* __restrict__ ctx
       u64 r4[4];
       if constexpr (mixed) {  // the auxiliary rows come back from the FP64 middle kernel as doubles
         const ArithD ar(dm);
-        tail_inv4_scale_raw<ArithD, L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)(KK + j) * N), ctx->intt_scale_bsk_d[j], dm.split_inv_mask, r4);
+        tail_inv4_fold_raw_d<L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)(KK + j) * N), ctx->tail_fold_bsk[j], dm.split_inv_mask, r4);
       } else {
         const ArithI ar(dm);
         tail_inv4_scale_raw<ArithI, L>(ar, cur, t, twi_base + (size_t)(KK + j) * N, ctx->intt_scale_bsk[j], 0u, r4);
@@ -2393,7 +2424,7 @@ __device__ __forceinline__ void mul_tail_sum_term_int(const DevCtx* __restrict__
       u64 r4[4];
       if (residue_is_f64(dm)) {
         const ArithD ar(dm);
-        tail_inv4_scale_raw<ArithD, L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->intt_scale_q_d[i], dm.split_inv_mask, r4);
+        tail_inv4_fold_raw_d<L>(ar, cur, t, reinterpret_cast<const double*>(twi_base + (size_t)i * N), ctx->tail_fold_q[i], dm.split_inv_mask, r4);
       } else {
         const ArithI ar(dm);
         tail_inv4_scale_raw<ArithI, L>(ar, cur, t, twi_base + (size_t)i * N, ctx->intt_scale_q[i], 0u, r4);
@@ -2601,18 +2632,12 @@ __global__ EDGE_BOUNDS(KMAX) void mulrelin_tail_kernel(const DevCtx* __restrict_
       double v[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) v[k] = nat_unpack<PACKK>(cur[k]);
-      tail_inv_owned<ArithD, L>(ar, v, tw, mj.split_inv_mask, t);
+      // (n^-1 folded into the stage constants; mod_down_d wants |s| <= 2q, which the sum output satisfies unreduced)
+      tail_inv_scale_fold_d<L, false>(ar, v, tw, ctx->tail_fold_key[J], mj.split_inv_mask, t);
       const MulOpD iw = ctx->inv_qsp_mod_q_d[J];
       const double hf = ctx->qsp_half_mod_q_d[J];
       const bool p_above_q = qsp > mj.q;
-      double s[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) s[k] = ar.mul_const(v[k], mj.ninv_d);
-      if (mj.split_inv_mask & kPlanScaleReduce) {  // mod_down_d wants |s| <= 2q
-        HIPBFV_KEEP_BRANCH();
-#pragma unroll
-        for (int k = 0; k < 4; k++) s[k] = ar.reduce(s[k]);
-      }
+      const double(&s)[4] = v;
       if (members) {
         // mult * (c_J of the relinearised product) + sign * addend: |.| <= 4q + q < 2^53, an exact integer, reduced once more
         HIPBFV_KEEP_BRANCH();

@@ -17,6 +17,8 @@
 #pragma once
 #include <cmath>
 
+#include "devctx.hpp"
+
 #if defined(__HIPCC__)
 #define HIPBFV_MD_HD __host__ __device__ inline __attribute__((always_inline))
 #else
@@ -49,6 +51,30 @@ HIPBFV_MD_HD double mod_down_d(double q, double qinv, double w, double wq, doubl
   const double dd = md_mul_const(d, w, wq, q);
   const double r = md_reduce(dd + base, q, qinv);
   return r < 0.0 ? r + q : r;
+}
+
+// The tails' last two inverse stages WITH their fixed scaling sc (n^-1, or a fused BEHZ scaling), on the four values of one thread
+// (kernels_split.hip tail_inverse4 followed by four products by sc, eight constant products in all), in five products: the
+// Gentleman-Sande product sits on the difference output, so the constant of every difference whose inputs are still unscaled
+// carries sc (DevCtx::tail_fold_*, context.cpp), the second-stage pair of the two SCALED differences keeps the plain twiddle, and
+// only the all-sums output is scaled on its own:
+//   X0 = v0 + v1            Y1 = (v0 - v1) * (tw2 sc)
+//   X2 = v2 + v3            Y3 = (v2 - v3) * (tw3 sc)
+//   out0 = (X0 + X2) * sc   out2 = (X0 - X2) * (tw1 sc)
+//   out1 = Y1 + Y3          out3 = (Y1 - Y3) * tw1
+// Every output is congruent mod q to the one it replaces.  The largest argument of a product is still the four-input sum the
+// old scaling product saw (range plan: context.cpp plan_f64_split), so out0, out2, out3 are bounded as the scaled values were,
+// q * (0.5 + |y| * 2^-51); out1 is a SUM of two such products of two-input differences: |out1| <= 2q where the plan leaves the
+// products unreduced (each below 0.95 q) -- what mod_down_d accepts as it is; a consumer that makes it canonical with one
+// conditional add reduces it first.  tests/native/tailfold_check.cpp compares with 128-bit integer arithmetic.
+HIPBFV_MD_HD void tail_fold4_d(double q, const TailFoldD& c, double (&v)[4]) {
+  const double x0 = v[0] + v[1], x2 = v[2] + v[3];
+  const double y1 = md_mul_const(v[0] - v[1], c.tw2sc.w, c.tw2sc.wq, q);
+  const double y3 = md_mul_const(v[2] - v[3], c.tw3sc.w, c.tw3sc.wq, q);
+  v[0] = md_mul_const(x0 + x2, c.sc.w, c.sc.wq, q);
+  v[2] = md_mul_const(x0 - x2, c.tw1sc.w, c.tw1sc.wq, q);
+  v[1] = y1 + y3;
+  v[3] = md_mul_const(y1 - y3, c.tw1.w, c.tw1.wq, q);
 }
 
 }  // namespace hipbfv
