@@ -11,8 +11,19 @@ integers (`object` arrays).  Every builder returns (operands, expected); tests/t
 operands to `expected` on every crafted word (a builder that does not land would make the GPU test vacuous), and
 tests/test_gpu_landing.py compares the HIP kernels with the oracle on the same operands, word for word.
 
-What the method cannot reach: the multiply tails and the BEHZ floor (their outputs are not an affine function of anything the
-caller holds), polynomial 1 of a stand-alone rotation (it is ks1 alone), and the gamma-correction boundary of decrypt."""
+Values INSIDE the multiply and the decryption are reached through bijections instead (sections F, G, H below).  The extension's
+rows y_i = x_i m~ (q / q_i)^-1 mod q_i are a bijection of the caller's x_i row by row, and r_mtilde is a function of the y_i mod 2^32:
+the y are chosen and x solved for, one row above 2^32 taking up the target (land_mtilde).  A multiplication by (1, 1) has the tensor
+d0 = a0, d1 = a0 + a1, d2 = a1, so the floor's inputs y_i = t d (q / q_i)^-1 mod q_i are again the caller's (land_floor_inputs), and
+polynomial 0 (2) of the product is a function of a0[k] (a1[k]) alone: candidates whose product is 0, q_i - 1 or 1 in EVERY row are
+harvested from the oracle (land_multiply_output; floor(t D / q) - u' with u' in [0, K) the fast conversion's overflow, so +1 is found
+among D near j q / t, and a SMALL D never gives 0 or +1: its u' is at least 1).  The gamma residue of decrypt's rounding is a linear
+form of (y_0, y_1) mod gamma: the nearest point of a two-dimensional lattice coset puts it on any target (land_gamma).
+tests/test_gpu_landing_multiply.py runs these.
+
+What the method cannot reach: polynomial 1 of a stand-alone key switch or rotation (it is ks1 alone), polynomial 1 of a product by
+(1, 1) (a0 + a1 is not free once a0 and a1 are spent; it is compared all the same), and alpha_sk's own branch in the
+Shenoy-Kumaresan step (alpha is a small integer far from m_sk / 2 in any valid run)."""
 from __future__ import annotations
 
 import numpy as np
@@ -134,10 +145,12 @@ def land_plain(o, plain, T0, sub: bool):
 
 
 def land_phase(o, sk, c1, phases):
-    """(ct2, residues): c0 + c1 s == phases[k] mod Q in coefficient k.  phases: n integers in [0, Q)."""
+    """(ct, residues): c0 + c1 s (+ c2 s^2 ...) == phases[k] mod Q in coefficient k.  phases: n integers in [0, Q); c1:
+    uint64[K][n], or uint64[size - 1][K][n] for the polynomials 1 ... size - 1 of a larger ciphertext."""
+    rest = c1[None] if c1.ndim == 2 else c1
     want = _u64(np.array([[int(x) % q for x in phases] for q in o.primes], dtype=object))
-    d = o.dot_with_secret(np.stack([np.zeros_like(c1), c1]), sk)
-    return np.stack([lin_mod(o.primes, [(1, want), (-1, d)]), c1]), want
+    d = o.dot_with_secret(np.concatenate([np.zeros_like(rest[:1]), rest]), sk)
+    return np.concatenate([lin_mod(o.primes, [(1, want), (-1, d)])[None], rest]), want
 
 
 # ---------------------------------------------------------------------------------------------------------- parameter sets
@@ -591,3 +604,318 @@ def table_case(L: Landing, batch: int = 3, rows: int = 5, cols: int = 17):
         return cq, db
 
     return L.cached(("table", batch, rows, cols), make)
+
+
+# ------------------------------------------------------------------------------------- shared by the sections F, G and H
+def _product(primes) -> int:
+    out = 1
+    for q in primes:
+        out *= int(q)
+    return out
+
+
+def thread_cycle(n: int, per_thread: int, length: int, shift: int = 0) -> np.ndarray:
+    """int[n]: an index into a cycle of `length` such that the `per_thread` coefficients {t + j n / per_thread} of one thread take
+    `per_thread` CONSECUTIVE indices.  (k % length alone gives one thread k-steps of n / per_thread, a power of two: with a cycle
+    of six that is three different values at the most.)"""
+    k = np.arange(n)
+    stride = n // per_thread
+    return (k % stride + k // stride + shift) % length
+
+
+def scale_rows(primes, a, consts, invert: bool = False) -> np.ndarray:
+    """uint64[K][n]: a[i] * consts[i] mod q_i (or a[i] / consts[i]) in Python integers."""
+    rows = []
+    for q, row, c in zip(primes, a, consts):
+        c = pow(int(c), -1, int(q)) if invert else int(c)
+        rows.append(_obj(row) * c % int(q))
+    return _u64(np.stack(rows))
+
+
+def odd_max(primes, n: int) -> np.ndarray:
+    """uint64[K][n]: q_i - 1 in every row on the odd coefficients, 0 in every row on the even ones."""
+    out = np.zeros((len(primes), n), dtype=np.uint64)
+    for i, q in enumerate(primes):
+        out[i, 1::2] = q - 1
+    return out
+
+
+# --------------------------------------------------------------- F: the multiply head -- r_mtilde and the y_i on their edges
+M_TILDE = 1 << 32
+R_TARGETS = [0, 1, (1 << 31) - 1, 1 << 31, (1 << 31) + 1, (1 << 32) - 1]
+
+
+def ext_scale(primes) -> list[int]:
+    """m~ (q / q_i)^-1 mod q_i: what the extension q -> Bsk u {m~} multiplies row i by first."""
+    Q = _product(primes)
+    return [(M_TILDE * pow(Q // q, -1, q)) % q for q in primes]
+
+
+def r_targets(n: int, shift: int = 0) -> np.ndarray:
+    """uint64[n]: R_TARGETS placed so that the eight coefficients of one head thread see all six."""
+    return np.array(R_TARGETS, dtype=np.uint64)[thread_cycle(n, 8, len(R_TARGETS), shift)]
+
+
+def land_mtilde(o, r_targets, y_of) -> np.ndarray:
+    """uint64[K][n], one polynomial x whose scaled rows y_i = x_i m~ (q / q_i)^-1 mod q_i are y_of (uint64[K][n]) and whose
+    r_mtilde = (sum y_i (q / q_i)) (-q^-1) mod 2^32 is r_targets (uint64[n]) in every coefficient.  x -> y is a bijection per
+    row, so the y are chosen and x solved for; the first row whose prime is above 2^32 is `free`: its y is solved mod 2^32 from the
+    target and the other rows (below 2^32, hence a residue).  r_targets None: all rows as given, r_mtilde whatever results."""
+    P = [int(q) for q in o.primes]
+    Q = _product(P)
+    y = np.array(y_of, dtype=np.uint64)
+    if r_targets is not None:
+        free = next(i for i, q in enumerate(P) if q > M_TILDE)
+        mask = np.uint64(M_TILDE - 1)
+        c = [(Q // q) % M_TILDE for q in P]
+        rest = np.zeros(y.shape[1], dtype=np.uint64)
+        for i in range(len(P)):
+            if i != free:
+                rest = (rest + (y[i] & mask) * np.uint64(c[i])) & mask
+        want = (np.asarray(r_targets, dtype=np.uint64) * np.uint64((-Q) % M_TILDE)) & mask  # the sum that gives the target
+        y[free] = (((want - rest) & mask) * np.uint64(pow(c[free], -1, M_TILDE))) & mask
+    return scale_rows(P, y, ext_scale(P), invert=True)
+
+
+def mtilde_polynomial(L: "Landing", rng, kind: str, shift: int) -> np.ndarray:
+    """One crafted polynomial: kind "random" (uniform y in the rows that are not free), "edge" (y cycling 0, q - 1, 1, (q -+ 1) / 2)
+    or "max" (every y at q - 1 on the odd coefficients and 0 on the even ones, r_mtilde as it comes)."""
+    P, n = L.primes, L.n
+    if kind == "max":
+        return land_mtilde(L.o, None, odd_max(P, n))
+    y = random_residues(rng, P, (), n) if kind == "random" else pattern(P, 1, n, shift)[0]
+    return land_mtilde(L.o, r_targets(n, shift), y)
+
+
+MTILDE_KINDS = [("random", "edge"), ("edge", "random"), ("max", "random"), ("edge", "max")]
+
+
+def mtilde_case(L: "Landing", size_a: int = 2, size_b: int = 2, items: int = 4):
+    """(a uint64[items][size_a][K][n], b uint64[items][size_b][K][n]): item i multiplies a MTILDE_KINDS[i][0] operand by a
+    MTILDE_KINDS[i][1] one; every polynomial has its own phase of the r_mtilde cycle."""
+
+    def make():
+        rng = L.rng(70 + 10 * size_a + size_b)
+        a, b = [], []
+        for i in range(items):
+            ka, kb = MTILDE_KINDS[i % len(MTILDE_KINDS)]
+            a.append(np.stack([mtilde_polynomial(L, rng, ka, 5 * i + p) for p in range(size_a)]))
+            b.append(np.stack([mtilde_polynomial(L, rng, kb, 5 * i + p + 3) for p in range(size_b)]))
+        return np.stack(a), np.stack(b)
+
+    return L.cached(("mtilde", size_a, size_b, items), make)
+
+
+# ------------------------------------------------------- G: the floor's inputs and the multiply's outputs, through b = (1, 1)
+def floor_scale(o) -> list[int]:
+    """t (q / q_i)^-1 mod q_i: the scaled inverse transform hands the floor y_i = d_i t (q / q_i)^-1 mod q_i."""
+    P = [int(q) for q in o.primes]
+    Q = _product(P)
+    return [(int(o.t) * pow(Q // q, -1, q)) % q for q in P]
+
+
+def ones_ct(L: "Landing", items: int) -> np.ndarray:
+    """uint64[items][2][K][n]: (1, 1), the constant polynomial 1 twice.  Not transparent; its extension is the integer 1, so the
+    tensor of a with it is d0 = a0, d1 = a0 + a1, d2 = a1 in every row."""
+    b = np.zeros((items, 2, L.K, L.n), dtype=np.uint64)
+    b[..., 0] = 1
+    return b
+
+
+def land_floor_inputs(o, y_of) -> np.ndarray:
+    """uint64[K][n], the polynomial a with a_i t (q / q_i)^-1 = y_of[i] mod q_i: as a0 (a1) of a ciphertext multiplied by (1, 1),
+    the floor of polynomial 0 (2) of the product reads exactly y_of."""
+    return scale_rows(o.primes, y_of, floor_scale(o), invert=True)
+
+
+def floor_case(L: "Landing"):
+    """(a uint64[2][2][K][n], y uint64[2][2][K][n]): item 0 gives d0 and d2 the y cycle in different phases, item 1 has every row
+    at q - 1 on the odd coefficients and 0 on the even ones (the conversion sums at their largest)."""
+
+    def make():
+        P, n = L.primes, L.n
+        y = np.stack([pattern(P, 2, n, 1), np.stack([odd_max(P, n), odd_max(P, n)[:, ::-1].copy()])])
+        a = np.stack([np.stack([land_floor_inputs(L.o, y[i, p]) for p in range(2)]) for i in range(2)])
+        return a, y
+
+    return L.cached("floor", make)
+
+
+OUTPUT_TARGETS = (0, -1, 1)
+
+
+def output_candidates(o, rng, count: int) -> list[int]:
+    """Integers D whose product with (1, 1) may land on 0, -1 or +1: polynomial 0 of a (1, 1) is floor(t D / q) - u' coefficient by
+    coefficient, u' in [0, K) the overflow of the fast conversion.  Half of them uniform in (-2^40, 2^40) (floor 0 or -1), half
+    ceil(j q / t) + delta with j in [1, K] and delta uniform in (-2^40, 2^40) (floor j or j - 1, and u' is most often near K / 2:
+    a small positive D has floor 0 and u' >= 1, so it never lands on 0 and none of the small ones lands on +1).  Even places hold
+    the small candidates, odd places the others."""
+    Q, t, K = _product(o.primes), int(o.t), o.K
+    delta = [int(v) for v in rng.integers(-(1 << 40) + 1, 1 << 40, count)]
+    j = [int(v) for v in rng.integers(1, K + 1, count)]
+    return [d if k % 2 == 0 else -((-jj * Q) // t) + d for k, (d, jj) in enumerate(zip(delta, j))]
+
+
+def _residues(primes, values) -> np.ndarray:
+    return _u64(np.array([[int(v) % int(q) for v in values] for q in primes], dtype=object))
+
+
+def land_multiply_output(o, rng=None, want: int = 4, rounds: int = 8, keep: int = 8):
+    """({target: [D, ...]}, stats): candidates harvested from the oracle.  One candidate per coefficient of a0 and of a1, one oracle
+    multiply by (1, 1) per round; kept are the D whose output (polynomial 0 for a0, polynomial 2 for a1) is 0 in every row, q_i - 1
+    in every row, or 1 in every row.  Stops at `want` distinct candidates for 0 and for -1 (+1 is kept where found); fails loudly
+    after `rounds` rounds.  stats: {family: [candidates, landed on 0, on -1, on +1]} for the two families of output_candidates."""
+    rng = rng if rng is not None else np.random.default_rng(o.n + 77)
+    P, n = [int(q) for q in o.primes], o.n
+    b = np.zeros((2, o.K, n), dtype=np.uint64)
+    b[..., 0] = 1
+    wants = {0: np.zeros((o.K, 1), dtype=np.uint64), -1: np.array(P, dtype=np.uint64)[:, None] - 1, 1: np.ones((o.K, 1), dtype=np.uint64)}
+    kept = {v: [] for v in OUTPUT_TARGETS}
+    stats = {"small": [0, 0, 0, 0], "near j q / t": [0, 0, 0, 0]}
+    small = np.arange(n) % 2 == 0  # (n is even: the places of a1's candidates have the parity of a0's)
+    for _ in range(rounds):
+        cand = output_candidates(o, rng, 2 * n)
+        out = o.multiply(np.stack([_residues(P, cand[:n]), _residues(P, cand[n:])]), b)
+        stats["small"][0] += n
+        stats["near j q / t"][0] += n
+        for poly, cs in ((0, cand[:n]), (2, cand[n:])):
+            for slot, v in enumerate(OUTPUT_TARGETS):
+                hit = np.flatnonzero((out[poly] == wants[v]).all(axis=0))
+                stats["small"][1 + slot] += int(small[hit].sum())
+                stats["near j q / t"][1 + slot] += int((~small[hit]).sum())
+                for k in hit:
+                    if cs[k] not in kept[v] and len(kept[v]) < keep:
+                        kept[v].append(cs[k])
+        if len(kept[0]) >= want and len(kept[-1]) >= want:
+            return kept, stats
+    raise RuntimeError(f"the harvest ran out: {stats} candidates / 0 / -1 / +1 after {rounds} rounds, kept {[len(kept[v]) for v in OUTPUT_TARGETS]}")
+
+
+def output_polynomial(L: "Landing", kept, kinds) -> np.ndarray:
+    """uint64[K][n]: coefficient k holds a harvested candidate for the target kinds[k] (the candidates of a target taken in turn)."""
+    turn = thread_cycle(L.n, 4, 1 << 20) // 3
+    return _residues(L.primes, [kept[int(v)][int(s) % len(kept[int(v)])] for v, s in zip(kinds, turn)])
+
+
+def output_kinds(L: "Landing", targets, shift: int) -> np.ndarray:
+    """int[n]: `targets` cycled so that the four coefficients {t + k n / 4} of one tail thread take four consecutive places."""
+    return np.array(targets)[thread_cycle(L.n, 4, len(targets), shift)]
+
+
+def output_case(L: "Landing"):
+    """(a uint64[2][2][K][n], kinds int[2][2][n], kept, stats): polynomials 0 and 2 of a[i] (1, 1) are 0, q_i - 1 (and 1 where the
+    harvest found some) in EVERY row, as kinds says, the targets in turn over a tail thread's coefficients."""
+
+    def make():
+        kept, stats = land_multiply_output(L.o, L.rng(80))
+        targets = [v for v in OUTPUT_TARGETS if len(kept[v]) >= 4]
+        kinds = np.stack([np.stack([output_kinds(L, targets, 2 * i + p) for p in range(2)]) for i in range(2)])
+        a = np.stack([np.stack([output_polynomial(L, kept, kinds[i, p]) for p in range(2)]) for i in range(2)])
+        return a, kinds, kept, stats
+
+    return L.cached("output", make)
+
+
+def output_sum_case(L: "Landing", groups: int = 2, terms: int = 3):
+    """(a uint64[groups][terms][2][K][n], kinds int[groups][terms][2][n]): per coefficient the three terms' outputs are 0, q_i - 1,
+    q_i - 1 in some order, so the sums of canonical residues pass through q_i - 1 and wrap to q_i - 2."""
+
+    def make():
+        kept = output_case(L)[2]
+        kinds = np.stack([np.stack([np.stack([output_kinds(L, [0, -1, -1], g + j + p) for p in range(2)]) for j in range(terms)]) for g in range(groups)])
+        a = np.stack([np.stack([np.stack([output_polynomial(L, kept, kinds[g, j, p]) for p in range(2)]) for j in range(terms)]) for g in range(groups)])
+        return a, kinds
+
+    return L.cached(("output sum", groups, terms), make)
+
+
+def kinds_to_words(primes, kinds) -> np.ndarray:
+    """uint64[..., K, n]: the residues of the small integers in kinds (int[..., n])."""
+    k = np.asarray(kinds).astype(object)[..., None, :]
+    return _u64(k % _qcol(primes, 0))
+
+
+# ------------------------------------------------------------------------------------------ H: decrypt's gamma correction
+def gamma_targets(gamma: int) -> list[int]:
+    return [0, 1, gamma // 2 - 1, gamma // 2, gamma // 2 + 1, gamma - 1]
+
+
+def _reduced_basis(u, v):
+    """Lagrange-Gauss reduction of a two-dimensional integer basis."""
+    norm = lambda w: w[0] * w[0] + w[1] * w[1]  # noqa: E731
+    if norm(u) < norm(v):
+        u, v = v, u
+    while True:  # norm(u) >= norm(v)
+        dot, nv = u[0] * v[0] + u[1] * v[1], norm(v)
+        m = (2 * dot + nv) // (2 * nv)  # round(dot / nv)
+        u = (u[0] - m * v[0], u[1] - m * v[1])
+        if norm(u) >= nv:
+            return v, u
+        u, v = v, u
+
+
+def _round_div(a: int, d: int) -> int:
+    if d < 0:
+        a, d = -a, -d
+    return (2 * a + d) // (2 * d)
+
+
+def land_gamma(o, targets, rng=None):
+    """(phases: n integers in [0, Q), y uint64[K][n]): the gamma residue of decrypt's fast conversion,
+    g = (sum y_i ((q / q_i) mod gamma)) (-q^-1) mod gamma with y_i = phase_i t gamma (q / q_i)^-1 mod q_i, is targets[k] in
+    coefficient k.  The rows from the third on are random; (y_0, y_1) is the point of the coset
+    {y_0 c_0 + y_1 c_1 = w mod gamma} nearest the middle of [0, q_0) x [0, q_1): a particular solution moved by the reduced basis
+    of the lattice {y_0 c_0 + y_1 c_1 = 0} (determinant gamma, far below q_0 q_1), in exact integer arithmetic."""
+    rng = rng if rng is not None else np.random.default_rng(o.n + 99)
+    P, n, K, t, gamma = [int(q) for q in o.primes], o.n, o.K, int(o.t), int(o.gamma)
+    assert K >= 2
+    Q = _product(P)
+    c = [(Q // q) % gamma for q in P]
+    y = np.zeros((K, n), dtype=np.uint64)
+    for i in range(2, K):
+        y[i] = rng.integers(0, P[i], n, dtype=np.uint64)
+    c0inv = pow(c[0], -1, gamma)
+    b1, b2 = _reduced_basis((gamma, 0), ((-c[1] * c0inv) % gamma, 1))
+    det = b1[0] * b2[1] - b1[1] * b2[0]
+    assert abs(det) == gamma
+    mid = (P[0] // 2, P[1] // 2)
+    y0, y1 = [], []
+    for k in range(n):
+        rest = sum(int(y[i, k]) * c[i] for i in range(2, K))
+        w = (-int(targets[k]) * Q - rest) % gamma  # sum y_i c_i must be w: g = w (-q^-1)
+        px = (w * c0inv) % gamma
+        dx, dy = mid[0] - px, mid[1]
+        al, be = _round_div(dx * b2[1] - dy * b2[0], det), _round_div(b1[0] * dy - b1[1] * dx, det)
+        for da, db in ((0, 0), (1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (1, -1), (-1, 1)):
+            x0 = px + (al + da) * b1[0] + (be + db) * b2[0]
+            x1 = (al + da) * b1[1] + (be + db) * b2[1]
+            if 0 <= x0 < P[0] and 0 <= x1 < P[1]:
+                break
+        else:
+            raise RuntimeError(f"no point of the coset in the box at coefficient {k}")
+        y0.append(x0), y1.append(x1)
+    y[0], y[1] = _u64(np.array(y0, dtype=object)), _u64(np.array(y1, dtype=object))
+    scale = [(t * gamma * pow(Q // q, -1, q)) % q for q in P]
+    ph = scale_rows(P, y, scale, invert=True)
+    acc = np.zeros(n, dtype=object)
+    for i, q in enumerate(P):
+        acc = acc + _obj(ph[i]) * (pow(Q // q, -1, q) * (Q // q))
+    return [int(v) % Q for v in acc], y
+
+
+def gamma_case(L: "Landing", items: int = 2, size: int = 2):
+    """(ct uint64[items][size][K][n], phases, targets int[items][n]): random c1 (and c2), c0 landed on land_gamma's phases; the six
+    targets cycled over the coefficients, item i shifted by 2 i."""
+
+    def make():
+        rng = L.rng(90 + size)
+        G = gamma_targets(int(L.o.gamma))
+        cts, phases, tg = [], [], []
+        for i in range(items):
+            want = [G[(k + 2 * i) % len(G)] for k in range(L.n)]
+            ph, _ = land_gamma(L.o, want, rng)
+            ct, _ = land_phase(L.o, L.sk, random_residues(rng, L.primes, (size - 1,), L.n), ph)
+            cts.append(ct), phases.append(ph), tg.append(want)
+        return np.stack(cts), phases, tg
+
+    return L.cached(("gamma", items, size), make)

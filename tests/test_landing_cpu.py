@@ -196,3 +196,167 @@ def test_phases_land_and_decrypt_by_the_integer_algorithm(pid, t):
         want, _ = _decrypt_over_the_integers(o, phases[i])
         assert (o.decrypt(ct[i], L.sk) == want).all(), i
         assert set(phases[i]) == set(vals)
+
+
+# ---- F: the multiply head ----------------------------------------------------------------------------------------------------
+def _head_model(P, x):
+    """(y: K object rows, r: object[n], v: object[n]) of one polynomial from the primes alone: y_i = x_i 2^32 (q / q_i)^-1 mod q_i,
+    v = sum y_i (q / q_i) over the integers, r = -v / q mod 2^32."""
+    Q = LD._product(P)
+    y = [LD._obj(x[i]) * ((1 << 32) * pow(Q // q, -1, q)) % q for i, q in enumerate(P)]
+    v = sum(y[i] * (Q // q) for i, q in enumerate(P))
+    return y, (-v * pow(Q, -1, 1 << 32)) % (1 << 32), v
+
+
+def test_thread_cycle_gives_one_thread_consecutive_places():
+    for n in (1024, 4096, 8192, 16384):
+        for t in (0, 1, n // 8 - 1):
+            assert len({int(LD.r_targets(n, 3)[t + k * (n // 8)]) for k in range(8)}) == 6   # a head thread's eight see all six (four asked for)
+        assert set(int(v) for v in LD.r_targets(n)) == set(LD.R_TARGETS)
+        idx = LD.thread_cycle(n, 4, 3, 1)
+        for t in (0, 5, n // 4 - 1):
+            assert {int(idx[t + k * (n // 4)]) for k in range(4)} == {0, 1, 2}               # a tail thread's four: all three
+    assert LD.R_TARGETS == [0, 1, 2**31 - 1, 2**31, 2**31 + 1, 2**32 - 1]
+
+
+HEAD_SETS = ["P1", "P3", "P4", "P5", "W2048", "U1024"]
+
+
+@pytest.mark.parametrize("pid", HEAD_SETS)
+def test_multiply_head_operands_land(pid):
+    """Every coefficient of every crafted polynomial carries the intended r_mtilde and y_i (from the primes alone), and the oracle's
+    behz_extend of it is the integer (sum y_i (q / q_i) + q centred(r)) / 2^32 mod every Bsk prime, r = 2^31 centred as -2^31."""
+    L = landing(pid)
+    o, P, n, Q = L.o, L.primes, L.n, L.Q
+    free = next(i for i, q in enumerate(P) if q > 1 << 32)
+    if pid == "U1024":
+        assert [q.bit_length() for q in P] == [50, 30, 30, 50] and free == 0  # 30-bit rows below m~ beside 50-bit ones
+    a, b = LD.mtilde_case(L)
+    assert a.shape == b.shape == (4, 2, L.K, n)
+    qm1 = np.array(P, dtype=object)[:, None] - 1
+    seen_r = set()
+    for i in range(4):
+        for side, ops in enumerate((a, b)):
+            kind = LD.MTILDE_KINDS[i][side]
+            for p in range(2):
+                x = ops[i, p]
+                assert all((x[k] < q).all() for k, q in enumerate(P))  # canonical residues
+                y, r, v = _head_model(P, x)
+                shift = 5 * i + p + 3 * side
+                if kind == "max":
+                    assert all((y[k][1::2] == q - 1).all() and (y[k][0::2] == 0).all() for k, q in enumerate(P))
+                    print(pid, "max operand: r_mtilde on the odd coefficients", hex(int(r[1])), "on the even ones", hex(int(r[0])))
+                else:
+                    assert (r == LD._obj(LD.r_targets(n, shift))).all(), (i, side, p)
+                    seen_r |= set(int(v) for v in r)
+                    assert (y[free] < 1 << 32).all()
+                if kind == "edge":
+                    pat = LD.pattern(P, 1, n, shift)[0]
+                    assert all((y[k] == LD._obj(pat[k])).all() for k in range(L.K) if k != free), (i, side, p)
+                    assert all(set(int(w) for w in y[k]) == set(LD.targets(q)) for k, q in enumerate(P) if k != free)
+                if (i, p) in ((0, 0), (2, 0), (3, 1)):  # the integer model of the extension (all kinds, both sides)
+                    rc = np.where(r >= 1 << 31, r - (1 << 32), r)
+                    num = v + Q * rc
+                    assert (num % (1 << 32) == 0).all()
+                    ext = o.behz_extend(x)
+                    for j, m in enumerate(o.bsk):
+                        assert (LD._obj(ext[j]) == (num >> 32) % m).all(), (i, side, p, j)
+    assert seen_r == set(LD.R_TARGETS)
+    if pid == "P1":
+        a3, b2 = LD.mtilde_case(L, 3, 2, 2)
+        assert a3.shape[1] == 3 and (_head_model(P, a3[0, 2])[1] == LD._obj(LD.r_targets(n, 2))).all()
+
+
+def test_the_turned_centring_differs_on_the_crafted_operands_only():
+    """The integer multiply of tests/test_oracle_behz_exact.py with `>` for `>=` at r = 2^31: other words on the crafted operands
+    (which the oracle does not follow), the same words on that file's random and extreme operands -- those never put 2^31 there."""
+    from tests.test_oracle_behz_exact import behz_multiply_over_the_integers, random_and_extreme_operands
+
+    L = landing("P1")
+    a, b = LD.mtilde_case(L)
+    right = behz_multiply_over_the_integers(a[0], b[0], L.primes, L.t)
+    wrong = behz_multiply_over_the_integers(a[0], b[0], L.primes, L.t, turned=True)
+    assert (L.o.multiply(a[0], b[0]) == right).all()
+    differ = (right != wrong).any(axis=(0, 1))
+    print("turned centring: coefficients that differ on the crafted operands:", int(differ.sum()), "of", L.n)
+    assert differ.sum() > L.n // 6  # (r = 2^31 sits in every sixth coefficient of each factor; the product spreads it)
+    for x, y in random_and_extreme_operands(np.random.default_rng(L.n + 17), L.primes, L.n, 2, 2)[:3]:
+        assert (behz_multiply_over_the_integers(x, y, L.primes, L.t, turned=True) == behz_multiply_over_the_integers(x, y, L.primes, L.t)).all()
+
+
+# ---- G: the floor's inputs and the multiply's outputs ------------------------------------------------------------------------
+FLOOR_SETS = ["P1", "P3", "P4", "P5", "W2048"]
+
+
+@pytest.mark.parametrize("pid", FLOOR_SETS)
+def test_floor_inputs_and_harvested_outputs_land(pid):
+    L = landing(pid)
+    o, P, n, Q, t = L.o, L.primes, L.n, L.Q, L.t
+    a, y = LD.floor_case(L)
+    for i in range(2):
+        for p in range(2):  # what the floor of polynomial 0 (2) of a (1, 1) reads, from the primes alone
+            got = [LD._obj(a[i, p, k]) * (t * pow(Q // q, -1, q)) % q for k, q in enumerate(P)]
+            assert all((got[k] == LD._obj(y[i, p, k])).all() for k in range(L.K)), (i, p)
+    assert all(set(int(v) for v in y[0, p, k]) == set(LD.targets(q)) for p in range(2) for k, q in enumerate(P))
+    assert not (y[0, 0] == y[0, 1]).all()  # different phases
+    assert all((y[1, 0, k, 1::2] == q - 1).all() and (y[1, 0, k, 0::2] == 0).all() for k, q in enumerate(P))
+    ones = LD.ones_ct(L, 1)[0]
+    prod = o.multiply(a[0], ones)  # (1, 1) is what the builder says: d0 = a0 and d2 = a1 pass the same floor
+    assert (prod[0] == o.multiply(np.stack([a[0, 0], a[0, 0]]), ones)[2]).all()
+    # the harvested outputs
+    ao, kinds, kept, stats = LD.output_case(L)
+    print(pid, "harvest {family: [candidates, on 0, on -1, on +1]}:", stats, "kept", {v: len(c) for v, c in kept.items()})
+    for v in (0, -1):
+        assert len(set(kept[v])) >= 4, (v, kept[v])
+    assert stats["small"][1] == 0 and stats["small"][3] == 0  # a small D has floor 0 or -1 and u' >= 1: never 0, never +1
+    used = sorted(set(int(v) for v in kinds.ravel()))
+    assert used[:2] == [-1, 0] and all(len(set(kept[v])) >= 4 for v in used)
+    for i in range(2):
+        out = o.multiply(ao[i], ones)
+        for p, poly in ((0, 0), (1, 2)):
+            assert (out[poly] == LD.kinds_to_words(P, kinds[i, p])).all(), (i, poly)  # every row of every coefficient
+            for th in (0, 1, n // 4 - 1):  # a tail thread's four coefficients see every target in use
+                assert {int(kinds[i, p, th + k * (n // 4)]) for k in range(4)} == set(used), (i, p, th)
+    # the sums: per coefficient the three term outputs are 0, -1, -1 in some order
+    if pid in ("P3", "P4"):
+        asum, ksum = LD.output_sum_case(L)
+        assert (ksum.sum(axis=1) == -2).all() and sorted(set(int(v) for v in ksum.ravel())) == [-1, 0]
+        total = None
+        for j in range(asum.shape[1]):
+            term = o.multiply(asum[0, j], ones)
+            assert (term[0] == LD.kinds_to_words(P, ksum[0, j, 0])).all() and (term[2] == LD.kinds_to_words(P, ksum[0, j, 1])).all()
+            total = term if total is None else o.add(total, term)
+        qm2 = np.array(P, dtype=np.uint64)[:, None] - 2
+        assert (total[0] == qm2).all() and (total[2] == qm2).all()
+
+
+# ---- H: decrypt's gamma correction -------------------------------------------------------------------------------------------
+GAMMA_CASES = [(p, t) for p in ("P1", "P2", "P3", "W4096") for t in (None, 500, (1 << 60) - 1)]
+
+
+@pytest.mark.parametrize("pid,t", GAMMA_CASES, ids=[f"{p}-t{t or 'batching'}" for p, t in GAMMA_CASES])
+def test_gamma_residues_land_and_only_the_turned_branch_differs(pid, t):
+    L = landing(pid, t)
+    o, P, n, Q, gamma = L.o, L.primes, L.n, L.Q, int(L.o.gamma)
+    if t == (1 << 60) - 1:
+        assert t > max(P)  # t above every data prime
+    G = LD.gamma_targets(gamma)
+    assert gamma % 2 == 1 and G[3] == gamma >> 1 and len(set(G)) == 6
+    sizes = (2, 3) if (pid, t) == ("P1", None) else (2,)
+    for size in sizes:
+        ct, phases, targets = LD.gamma_case(L, 2, size)
+        assert ct.shape == (2, size, L.K, n)
+        for i in range(2):
+            assert set(targets[i]) == set(G)
+            d = o.dot_with_secret(ct[i], L.sk)
+            g = 0
+            for k, q in enumerate(P):  # from the primes, t and gamma alone
+                assert (d[k] == np.array([x % q for x in phases[i]], dtype=np.uint64)).all(), (i, k)
+                g = g + (LD._obj(d[k]) * (L.t * gamma * pow(Q // q, -1, q)) % q) * ((Q // q) % gamma)
+            g = g * (-pow(Q, -1, gamma)) % gamma
+            assert (g == np.array(targets[i], dtype=object)).all(), i  # 100 % of the coefficients
+            want, slack = _decrypt_over_the_integers(o, phases[i])
+            assert [s % gamma for s in slack] == targets[i]
+            assert (o.decrypt(ct[i], L.sk) == want).all(), i
+            turned, _ = _decrypt_over_the_integers(o, phases[i], turned=True)
+            assert ((turned != want) == (np.array(targets[i], dtype=object) == gamma >> 1)).all(), i

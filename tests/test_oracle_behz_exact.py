@@ -70,8 +70,9 @@ def _negacyclic(a: list[int], b: list[int], bound_bits: int) -> list[int]:
     return [d[k] - d[k + n] for k in range(n)]
 
 
-def behz_multiply_over_the_integers(a: np.ndarray, b: np.ndarray, q: list[int], t: int) -> np.ndarray:
-    """a, b: uint64[size][K][n] (coefficient form) -> uint64[size_a + size_b - 1][K][n], by the integer steps above."""
+def behz_multiply_over_the_integers(a: np.ndarray, b: np.ndarray, q: list[int], t: int, turned: bool = False) -> np.ndarray:
+    """a, b: uint64[size][K][n] (coefficient form) -> uint64[size_a + size_b - 1][K][n], by the integer steps above.  `turned`: the
+    WRONG centring of r (2^31 taken as +2^31), for tests/test_landing_cpu.py to show which operands tell the two apart."""
     n = a.shape[2]
     K = len(q)
     Q, terms = _crt_terms(q)
@@ -85,13 +86,13 @@ def behz_multiply_over_the_integers(a: np.ndarray, b: np.ndarray, q: list[int], 
                 res = [(int(poly[i][k]) * M_TILDE) % q[i] for i in range(K)]
                 v = _fast_conv_integer(res, q, terms)
                 r = (v * neg_inv_q_mod_mt) % M_TILDE
-                if r >= M_TILDE // 2:
+                if (r > M_TILDE // 2) if turned else (r >= M_TILDE // 2):
                     r -= M_TILDE
                 num = v + Q * r
                 assert num % M_TILDE == 0
                 x = num // M_TILDE
                 assert all(x % q[i] == int(poly[i][k]) for i in range(K))
-                assert 2 * abs(x) <= Q + (2 * K * Q) // M_TILDE + 2
+                assert turned or 2 * abs(x) <= Q + (2 * K * Q) // M_TILDE + 2
                 xs.append(x)
             polys.append(xs)
         return polys
@@ -136,17 +137,9 @@ CASES += [(f"n2048_default_t{b}b", 2048, None, b, None, 2, 2) for b in (36, 40)]
 CASES += [("n8192_3x54_t2^59", 8192, [54, 54, 54, 56], None, 1 << 59, 2, 2)]
 
 
-@pytest.mark.parametrize("name,n,bits,tbits,t,sa,sb", CASES, ids=[c[0] for c in CASES])
-def test_oracle_multiply_is_the_integer_algorithm(name, n, bits, tbits, t, sa, sb):
-    primes = O.bfv_default(n) if bits is None else O.coeff_modulus_create(n, bits)
-    t = O.plain_batching(n, tbits) if t is None else t
-    o = O.Oracle(n, primes, t)
-    o.throw_on_transparent = False
-    if name.startswith("n2048_default_t"):
-        assert len(o.bsk) == o.K + 2  # |B| = K + 1: SEAL's extra auxiliary prime
-    q = [int(p) for p in primes[: o.K]]
+def random_and_extreme_operands(rng, q, n, sa, sb):
+    """The operand pairs of this file: random residues and the constants that drive every intermediate to its largest."""
     Q = _prod(q)
-    rng = np.random.default_rng(n + (tbits if tbits is not None else t.bit_length()))
 
     def rand(size):
         return np.stack([rng.integers(0, p, (size, n), dtype=np.uint64) for p in q], axis=1)
@@ -160,13 +153,26 @@ def test_oracle_multiply_is_the_integer_algorithm(name, n, bits, tbits, t, sa, s
             ct[:, i, :] = np.where(sign > 0, value_even % p, (value_even if value_odd is None else value_odd) % p).astype(np.uint64)
         return ct
 
-    operands = [
+    return [
         (rand(sa), rand(sb)),
         (const(sa, half), const(sb, half)),                    # every coefficient floor(q/2): the largest sums
         (const(sa, half, Q - half), const(sb, half)),          # ... with alternating signs
         (const(sa, Q - 1), const(sb, Q - 1)),                  # -1 everywhere
         (const(sa, half + 1), rand(sb)),
     ]
+
+
+@pytest.mark.parametrize("name,n,bits,tbits,t,sa,sb", CASES, ids=[c[0] for c in CASES])
+def test_oracle_multiply_is_the_integer_algorithm(name, n, bits, tbits, t, sa, sb):
+    primes = O.bfv_default(n) if bits is None else O.coeff_modulus_create(n, bits)
+    t = O.plain_batching(n, tbits) if t is None else t
+    o = O.Oracle(n, primes, t)
+    o.throw_on_transparent = False
+    if name.startswith("n2048_default_t"):
+        assert len(o.bsk) == o.K + 2  # |B| = K + 1: SEAL's extra auxiliary prime
+    q = [int(p) for p in primes[: o.K]]
+    rng = np.random.default_rng(n + (tbits if tbits is not None else t.bit_length()))
+    operands = random_and_extreme_operands(rng, q, n, sa, sb)
     if n >= 16384:
         operands = operands[:2]  # random + the extreme (9 s each in Python)
     for idx, (a, b) in enumerate(operands):

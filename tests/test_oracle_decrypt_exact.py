@@ -50,7 +50,8 @@ def _dot_over_the_integers(o, ct, s) -> list[int]:
     return [v % Q for v in acc]
 
 
-def _decrypt_over_the_integers(o, xs) -> tuple[np.ndarray, list[int]]:
+def _decrypt_over_the_integers(o, xs, turned: bool = False) -> tuple[np.ndarray, list[int]]:
+    """`turned`: the WRONG gamma branch (g = floor(gamma / 2) taken as negative), for tests/test_landing_cpu.py."""
     q = o.key_primes[: o.K]
     Q, terms = _crt_terms(q)
     t, gamma = o.t, o.gamma
@@ -62,7 +63,7 @@ def _decrypt_over_the_integers(o, xs) -> tuple[np.ndarray, list[int]]:
         assert (t * gamma * x - D) % Q == 0
         W = (t * gamma * x - D) // Q
         g = W % gamma
-        if g > gamma >> 1:
+        if (g >= gamma >> 1) if turned else (g > gamma >> 1):
             g -= gamma
         assert (W - g) % gamma == 0
         out[k] = ((W - g) // gamma) % t
