@@ -387,6 +387,26 @@ long hipbfv_batch_multiply_sum_relin(void *evaluator, const uint64_t *a, const u
 long hipbfv_batch_multiply_sum_relin_keys(void *evaluator, const uint64_t *a, const uint64_t *b, void *const *relin_key_sets,
                                           uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t groups,
                                           uint64_t terms, void *stream);
+/* Weighted sums of products: out3[g] = sum_t weights[t] (.) multiply(a[g][t], b[g][t]) -- any signed, integer-weighted quadratic
+ * form (4 n0 n2 - n1^2, ad - bc, sum x^2 - 2 sum xy + sum y^2) with one key switch per group.  Everything the three calls above
+ * say holds (layouts, b == a, chunks and slices, refusals, group-numbered transparent results); in addition:
+ *  - weights is a HOST array of `terms` entries, shared by every group and read before the call returns (the caller may free it
+ *    at once).  Any int32_t is a weight, 0 and INT32_MIN included.  NULL is HIPBFV_E_POINTER, refused like every other refusal
+ *    before anything is launched or written.
+ *  - Bits: w (.) c multiplies every word of residue row i by (w mod q_i), taken canonically in [0, q_i), mod q_i: what |w|
+ *    hipbfv_batch_add calls of the product would give, after hipbfv_batch_negate when w < 0.  The weight is applied to the
+ *    finished residues of a term inside the multiply's last kernel, just before they are added; out2[g] is
+ *    hipbfv_batch_relinearize of the sum.  With every weight 1 the calls run the launches of the unweighted ones.
+ *  - Noise: a weight multiplies the noise of its term by |w| (log2 |w| bits of budget); large weights are for exact modular
+ *    arithmetic on the words, not for results that must still decrypt.
+ *  - A weighted sum whose c1 (and c2) cancel to zero -- all weights 0, or (+1, -1) on equal terms -- is a transparent result. */
+long hipbfv_batch_multiply_sum_weighted(void *evaluator, const uint64_t *a, const uint64_t *b, const int32_t *weights,
+                                        uint64_t *out3, uint64_t groups, uint64_t terms, void *stream);
+long hipbfv_batch_multiply_sum_weighted_relin(void *evaluator, const uint64_t *a, const uint64_t *b, const int32_t *weights,
+                                              void *relin_keys, uint64_t *out2, uint64_t groups, uint64_t terms, void *stream);
+long hipbfv_batch_multiply_sum_weighted_relin_keys(void *evaluator, const uint64_t *a, const uint64_t *b, const int32_t *weights,
+                                                   void *const *relin_key_sets, uint64_t num_key_sets, const uint32_t *key_index,
+                                                   uint64_t *out2, uint64_t groups, uint64_t terms, void *stream);
 long hipbfv_batch_apply_galois_keys(void *evaluator, const uint64_t *ct2, uint32_t galois_elt, void *const *galois_key_sets,
                                     uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t count,
                                     void *stream);
@@ -679,6 +699,10 @@ long hipbfv_debug_rotate_items_keys_plan(uint64_t n, const int32_t *steps, const
  * earlier slice of the same group wrote.  *count = the number of sequences (E_INVALIDARG when it exceeds capacity). */
 long hipbfv_debug_multiply_sum_plan(uint64_t groups, uint64_t terms, uint64_t chunk, uint64_t *steps5, uint64_t capacity,
                                     uint64_t *count);
+/* Host only, no device access: the weight table of the weighted sums for the moduli `primes` (each in [2, 2^62)).
+ * out[(t * count + i) * 2] = weights[t] mod primes[i], canonical; out[... + 1] = floor(that * 2^64 / primes[i]). */
+long hipbfv_debug_weight_residues(const uint64_t *primes, uint64_t count, const int32_t *weights, uint64_t terms,
+                                  uint64_t *out);
 
 /* Per-kernel timing (HIP events recorded on the launch stream, around every kernel launch):
  * total milliseconds, number of launches and work units (residue polynomials for the NTT kernels,

@@ -678,6 +678,24 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
     for (const RelinearizationKeys* k : keys) hs.push_back(k ? k->get_handle() : nullptr);
     check(hipbfv_batch_multiply_sum_relin_keys(h_, a, b, hs.data(), hs.size(), key_index.data(), out2, key_index.size(), terms, stream));
   }
+  // Weighted sums: out[g] = sum_t weights[t] * a[g][t] * b[g][t]; one weight per term (weights.size() == terms), shared by every group.
+  // A weight multiplies its term's noise by |w|.
+  void multiply_sum_weighted(const uint64_t* a, const uint64_t* b, const std::vector<int32_t>& weights, uint64_t* out3, uint64_t groups,
+                             void* stream = nullptr) const {
+    check(hipbfv_batch_multiply_sum_weighted(h_, a, b, weights.data(), out3, groups, weights.size(), stream));
+  }
+  void multiply_sum_weighted_relin(const uint64_t* a, const uint64_t* b, const std::vector<int32_t>& weights, const RelinearizationKeys& rk,
+                                   uint64_t* out2, uint64_t groups, void* stream = nullptr) const {
+    check(hipbfv_batch_multiply_sum_weighted_relin(h_, a, b, weights.data(), rk.get_handle(), out2, groups, weights.size(), stream));
+  }
+  void multiply_sum_weighted_relin_keys(const uint64_t* a, const uint64_t* b, const std::vector<int32_t>& weights,
+                                        const std::vector<const RelinearizationKeys*>& keys, const std::vector<uint32_t>& key_index, uint64_t* out2,
+                                        void* stream = nullptr) const {
+    std::vector<void*> hs;
+    for (const RelinearizationKeys* k : keys) hs.push_back(k ? k->get_handle() : nullptr);
+    check(hipbfv_batch_multiply_sum_weighted_relin_keys(h_, a, b, weights.data(), hs.data(), hs.size(), key_index.data(), out2, key_index.size(),
+                                                        weights.size(), stream));
+  }
 };
 
 // The device pool (hipbfv.h, "Device pool"): host-resident batches u64[count][2][K][N] sharded over several GPUs, every input

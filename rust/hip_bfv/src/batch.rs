@@ -151,6 +151,29 @@ impl<'e> BatchEvaluator<'e> {
                                                           self.stream)
         })
     }
+    // ---- weighted sums: out[g] = sum_t weights[t] * a[g][t] * b[g][t]; one weight per term, shared by every group (a weight multiplies
+    // its term's noise by |w|) ----
+    pub fn multiply_sum_weighted(&self, a: DeviceBatch, b: DeviceBatch, weights: &[i32], out3: DeviceBatch) -> Result<()> {
+        let terms = weights.len() as u64;
+        Self::sum_shape_ok(&a, &b, terms, &out3)?;
+        check(unsafe { bindgen::hipbfv_batch_multiply_sum_weighted(self.h(), a.ptr, b.ptr, weights.as_ptr(), out3.ptr, out3.count, terms, self.stream) })
+    }
+    pub fn multiply_sum_weighted_relin(&self, a: DeviceBatch, b: DeviceBatch, weights: &[i32], rk: &RelinearizationKeys, out: DeviceBatch) -> Result<()> {
+        let terms = weights.len() as u64;
+        Self::sum_shape_ok(&a, &b, terms, &out)?;
+        check(unsafe { bindgen::hipbfv_batch_multiply_sum_weighted_relin(self.h(), a.ptr, b.ptr, weights.as_ptr(), rk.get_handle(), out.ptr, out.count, terms, self.stream) })
+    }
+    pub fn multiply_sum_weighted_relin_keys(&self, a: DeviceBatch, b: DeviceBatch, weights: &[i32], keys: &[Option<&RelinearizationKeys>], key_index: &[u32],
+                                            out: DeviceBatch) -> Result<()> {
+        let terms = weights.len() as u64;
+        Self::sum_shape_ok(&a, &b, terms, &out)?;
+        Self::key_index_ok(key_index, keys.len(), out.count)?;
+        let handles: Vec<*mut c_void> = keys.iter().map(|k| k.map_or(std::ptr::null_mut(), |k| k.get_handle())).collect();
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_sum_weighted_relin_keys(self.h(), a.ptr, b.ptr, weights.as_ptr(), handles.as_ptr(), handles.len() as u64, key_index.as_ptr(), out.ptr,
+                                                                   out.count, terms, self.stream)
+        })
+    }
     pub fn rotate_rows_keys(&self, a: DeviceBatch, steps: i32, keys: &[&GaloisKeys], key_index: &[u32], out: DeviceBatch) -> Result<()> {
         same_count(&a, &out)?;
         Self::key_index_ok(key_index, keys.len(), a.count)?;

@@ -224,6 +224,10 @@ _SIGNATURES = {
     "hipbfv_batch_multiply_sum_relin": [vp, vp, vp, vp, vp, u64, u64, vp],
     "hipbfv_batch_multiply_sum_relin_keys": [vp, vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64, u64, vp],
     "hipbfv_debug_multiply_sum_plan": [u64, u64, u64, u64p, u64, u64p],
+    "hipbfv_batch_multiply_sum_weighted": [vp, vp, vp, C.POINTER(C.c_int32), vp, u64, u64, vp],
+    "hipbfv_batch_multiply_sum_weighted_relin": [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, u64, u64, vp],
+    "hipbfv_batch_multiply_sum_weighted_relin_keys": [vp, vp, vp, C.POINTER(C.c_int32), vpp, u64, C.POINTER(C.c_uint32), vp, u64, u64, vp],
+    "hipbfv_debug_weight_residues": [u64p, u64, C.POINTER(C.c_int32), u64, u64p],
     "hipbfv_profile_enable": [vp, C.c_bool],
     "hipbfv_profile_reset": [vp],
     "hipbfv_profile_kernel_count": [C.POINTER(C.c_uint32)],

@@ -214,6 +214,40 @@ class BatchEvaluator:
         _check(_lib.load().hipbfv_batch_multiply_sum_relin_keys(self._h, _ptr(a), _ptr(b), hs, n, ip, _ptr(out), groups, terms, _stream()))
         return out
 
+    # ---- weighted sums of products: sum_t weights[t] * a[g, t] * b[g, t] (include/hipbfv.h) ----
+    @staticmethod
+    def _weights(weights, terms: int):
+        w = [int(x) for x in weights]
+        assert len(w) == terms, (len(w), terms)
+        assert all(-(1 << 31) <= x < (1 << 31) for x in w), "a weight is a 32-bit signed integer"
+        return (C.c_int32 * terms)(*w)
+
+    def multiply_sum_weighted(self, a: torch.Tensor, b: torch.Tensor, weights, out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[g] = sum_t weights[t] * a[g, t] * b[g, t] as size-3 ciphertexts: every row i of term t's product times (weights[t] mod q_i)
+        before it is added.  weights: `terms` host integers (32-bit signed), shared by every group; a weight multiplies its term's noise by |w|."""
+        groups, terms = self._sum_shape(a, b)
+        out = out if out is not None else self._new(groups, 3, a)
+        _check(_lib.load().hipbfv_batch_multiply_sum_weighted(self._h, _ptr(a), _ptr(b), self._weights(weights, terms), _ptr(out), groups, terms, _stream()))
+        return out
+
+    def multiply_sum_weighted_relin(self, a: torch.Tensor, b: torch.Tensor, weights, rk: RelinearizationKeys, out: torch.Tensor | None = None) -> torch.Tensor:
+        """relinearize(multiply_sum_weighted(a, b, weights)), [groups, 2, K, N]: one key switch per group."""
+        groups, terms = self._sum_shape(a, b)
+        out = out if out is not None else self._new(groups, 2, a)
+        _check(_lib.load().hipbfv_batch_multiply_sum_weighted_relin(self._h, _ptr(a), _ptr(b), self._weights(weights, terms), rk.get_handle(), _ptr(out),
+                                                                    groups, terms, _stream()))
+        return out
+
+    def multiply_sum_weighted_relin_keys(self, a: torch.Tensor, b: torch.Tensor, weights, key_sets: Sequence[RelinearizationKeys | None], key_index,
+                                         out: torch.Tensor | None = None) -> torch.Tensor:
+        """Group g is relinearised with key_sets[key_index[g]]; the weights are shared by every group."""
+        groups, terms = self._sum_shape(a, b)
+        out = out if out is not None else self._new(groups, 2, a)
+        hs, n, ip, _keep = self._key_sets(key_sets, key_index, groups)
+        _check(_lib.load().hipbfv_batch_multiply_sum_weighted_relin_keys(self._h, _ptr(a), _ptr(b), self._weights(weights, terms), hs, n, ip, _ptr(out),
+                                                                         groups, terms, _stream()))
+        return out
+
     def apply_galois_keys(self, ct: torch.Tensor, galois_elt: int, key_sets: Sequence[GaloisKeys], key_index, out: torch.Tensor | None = None) -> torch.Tensor:
         self._shape_ok(ct, 2)
         out = out if out is not None else self._new(ct.shape[0], 2, ct)
@@ -451,3 +485,13 @@ def multiply_sum_plan(groups: int, terms: int, chunk: int) -> list[tuple[int, in
     buf = (C.c_uint64 * (5 * max(1, n.value)))()
     _check(L.hipbfv_debug_multiply_sum_plan(groups, terms, chunk, buf, n.value, C.byref(n)))
     return [(buf[5 * i], buf[5 * i + 1], buf[5 * i + 2], buf[5 * i + 3], bool(buf[5 * i + 4])) for i in range(n.value)]
+
+
+def weight_residues(primes, weights) -> list[list[tuple[int, int]]]:
+    """The weight table of the weighted sums (host only): [term][prime] = (w mod q canonical, floor(that * 2^64 / q))."""
+    L = _lib.load()
+    p = (C.c_uint64 * len(primes))(*[int(q) for q in primes])
+    w = (C.c_int32 * len(weights))(*[int(x) for x in weights])
+    out = (C.c_uint64 * (2 * len(primes) * len(weights)))()
+    _check(L.hipbfv_debug_weight_residues(p, len(primes), w, len(weights), out))
+    return [[(out[2 * (t * len(primes) + i)], out[2 * (t * len(primes) + i) + 1]) for i in range(len(primes))] for t in range(len(weights))]

@@ -1867,7 +1867,51 @@ long hipbfv_batch_multiply_sum_relin_keys(void* h, const uint64_t* a, const uint
   return from_status(e->ev->multiply_sum_relin((const u64*)a, (const u64*)b, sel, (u64*)out2, groups, terms, (hipStream_t)stream));
 HIPBFV_END
 
-// the launch sequences of the two calls above for a chunk of `chunk` items (Evaluator::set_chunk_ops), host only
+// ---- the weighted forms: sum_t w_t * a_t * b_t; `weights` is a host array of `terms` entries shared by every group ----
+long hipbfv_batch_multiply_sum_weighted(void* h, const uint64_t* a, const uint64_t* b, const int32_t* weights, uint64_t* out3, uint64_t groups,
+                                        uint64_t terms, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!weights) return HIPBFV_E_POINTER;
+  MULTIPLY_SUM_ARGS_OR_RETURN(out3, 3);
+  if (!groups) return HIPBFV_S_OK;
+  return from_status(e->ev->multiply_sum_weighted((const u64*)a, (const u64*)b, weights, (u64*)out3, groups, terms, (hipStream_t)stream));
+HIPBFV_END
+
+long hipbfv_batch_multiply_sum_weighted_relin(void* h, const uint64_t* a, const uint64_t* b, const int32_t* weights, void* keys, uint64_t* out2,
+                                              uint64_t groups, uint64_t terms, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!weights) return HIPBFV_E_POINTER;
+  MULTIPLY_SUM_ARGS_OR_RETURN(out2, 2);
+  if (!groups) return HIPBFV_S_OK;
+  const u64* rk = key_or_null(keys, e, 0);
+  if (!rk) return from_status(kNoKey);
+  return from_status(e->ev->multiply_sum_relin((const u64*)a, (const u64*)b, rk, (u64*)out2, groups, terms, (hipStream_t)stream, weights));
+HIPBFV_END
+
+long hipbfv_batch_multiply_sum_weighted_relin_keys(void* h, const uint64_t* a, const uint64_t* b, const int32_t* weights, void* const* key_sets,
+                                                   uint64_t num_sets, const uint32_t* key_index, uint64_t* out2, uint64_t groups, uint64_t terms,
+                                                   void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!weights) return HIPBFV_E_POINTER;
+  MULTIPLY_SUM_ARGS_OR_RETURN(out2, 2);
+  const uint64_t count = groups;  // (one key per GROUP)
+  KEYSETS_OR_RETURN();
+  if (!groups) return HIPBFV_S_OK;
+  KEYSEL_OR_RETURN(sel, 0);
+  return from_status(e->ev->multiply_sum_relin((const u64*)a, (const u64*)b, sel, (u64*)out2, groups, terms, (hipStream_t)stream, weights));
+HIPBFV_END
+
+// the weight table of the three calls above for the given primes (evaluator.hpp weight_residues), host only
+long hipbfv_debug_weight_residues(const uint64_t* primes, uint64_t count, const int32_t* weights, uint64_t terms, uint64_t* out) HIPBFV_BEGIN
+  if (!primes || !weights || !out) return HIPBFV_E_POINTER;
+  for (uint64_t i = 0; i < count; i++)
+    if (primes[i] < 2 || primes[i] >> 62) return fail(HIPBFV_E_INVALIDARG, "a modulus must lie in [2, 2^62)");
+  static_assert(sizeof(MulOp) == 2 * sizeof(uint64_t), "MulOp is the pair the header documents");
+  weight_residues((const u64*)primes, count, weights, terms, reinterpret_cast<MulOp*>(out));
+  return HIPBFV_S_OK;
+HIPBFV_END
+
+// the launch sequences of the calls above for a chunk of `chunk` items (Evaluator::set_chunk_ops), host only
 long hipbfv_debug_multiply_sum_plan(uint64_t groups, uint64_t terms, uint64_t chunk, uint64_t* steps5, uint64_t capacity, uint64_t* count) HIPBFV_BEGIN
   if (!count || (!steps5 && capacity)) return HIPBFV_E_POINTER;
   if (!terms || !chunk) return fail(HIPBFV_E_INVALIDARG, "terms and chunk must not be zero");

@@ -431,6 +431,30 @@ int Evaluator::stage_keymap(const KeySel& sel, size_t count, size_t chunk, hipSt
   return kOk;
 }
 
+Evaluator::WeightLease::~WeightLease() {
+  if (!ev) return;
+  if (host) ev->pinned_.release(host, s);
+  if (dev) ev->pool_.release(dev, s);
+}
+
+int Evaluator::stage_weights(const int32_t* weights, size_t terms, hipStream_t s, WeightLease& lease) {
+  if (!weights || !terms) return kInvalidArg;
+  if (std::all_of(weights, weights + terms, [](int32_t w) { return w == 1; })) return kOk;
+  const DevCtx& h = ctx_->host();
+  const size_t bytes = terms * h.K * sizeof(MulOp);
+  lease.ev = this;
+  lease.s = s;
+  lease.host = pinned_.acquire(bytes);
+  lease.dev = pool_.acquire(std::max<size_t>(bytes, (size_t)1 << 20), s);  // (one size class for the small tables, as stage_keymap's)
+  if (!lease.host || !lease.dev) return kOutOfMemory;
+  u64 primes[kMaxKey];
+  for (u32 i = 0; i < h.K; i++) primes[i] = h.mod[i].q;
+  weight_residues(primes, h.K, weights, terms, static_cast<MulOp*>(lease.host));
+  HB_CHECK(hipMemcpyAsync(lease.dev, lease.host, bytes, hipMemcpyHostToDevice, s));
+  lease.wt = static_cast<const MulOp*>(lease.dev);
+  return kOk;
+}
+
 bool Evaluator::ks_split_for(size_t count) const {
   const DevCtx& h = ctx_->host();
   // (N = 32768 [r06]: integer-policy key primes only -- kernels_split.hip KS_DISPATCH; the multiply keeps the whole-polynomial kernels there)
@@ -488,7 +512,7 @@ int Evaluator::relinearize(const u64* ct3, const KeySel& rk, u64* out2, size_t c
 }
 
 // out3[g] = sum_t a[g][t] * b[g][t] (evaluator.hpp).  The path is multiply()'s choice for groups * terms items.
-int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch) {
+int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch, const MulOp* wt) {
   const DevCtx& h = ctx_->host();
   if (!terms) return kInvalidArg;
   if (h.logn > 15) return kUnsupported;
@@ -511,6 +535,12 @@ int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups
       for (size_t g = 0; g < st.groups; g++) {
         u64* o = out3 + (st.group0 + g) * out_words;
         const u64* t0 = stage + g * st.terms * out_words;
+        if (wt) {
+          // the weighted fold: out = (out or 0) + w_t * term, one scaled accumulate per term
+          for (size_t t = 0; t < st.terms; t++)
+            HB_LAUNCH(kKernEltwise, polys, launch_scaled_accumulate(ctx_->dev(), n, t || st.accumulate ? o : nullptr, t0 + t * out_words, wt + (st.term0 + t) * K, o, polys, s));
+          continue;
+        }
         size_t t = 0;
         if (!st.accumulate) {
           if (st.terms == 1)
@@ -536,20 +566,32 @@ int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups
     const size_t first = st.group0 * terms + st.term0, c = st.groups * st.terms;
     HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + first * in_words, b + first * in_words, ext, c, s, square ? 2u : 4u));
     HB_LAUNCH(kKernMulMid, c, launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square));
-    HB_LAUNCH(kKernMulTailSum, c * 3, launch_mul_tail_sum(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out3 + st.group0 * out_words, st.groups, st.terms, st.accumulate, s));
+    HB_LAUNCH(kKernMulTailSum, c * 3, launch_mul_tail_sum(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out3 + st.group0 * out_words, st.groups, st.terms, st.accumulate, s, wt ? wt + st.term0 * K : nullptr));
     return kOk;
   });
   if (rc) return rc;
   return watch ? note_result(out3, 3, K, groups, s) : (int)kOk;
 }
 
+int Evaluator::multiply_sum_weighted(const u64* a, const u64* b, const int32_t* weights, u64* out3, size_t groups, size_t terms, hipStream_t s) {
+  if (!terms || !weights) return kInvalidArg;
+  if (ctx_->host().logn > 15) return kUnsupported;
+  if (!groups) return kOk;
+  WeightLease wl;
+  if (int rc = stage_weights(weights, terms, s, wl)) return rc;
+  return multiply_sum(a, b, out3, groups, terms, s, true, wl.wt);
+}
+
 // one key switch per group: the size-3 sums go through a pooled buffer, chunk_ops() groups at a time
-int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s) {
+int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s, const int32_t* weights) {
   const DevCtx& h = ctx_->host();
   if (h.KK < 2 || !rk.present()) return kNoKey;
   if (!terms) return kInvalidArg;
   if (h.logn > 15) return kUnsupported;
   if (!groups) return kOk;
+  WeightLease wl;
+  if (weights)
+    if (int rc = stage_weights(weights, terms, s, wl)) return rc;
   const size_t K = h.K, n = h.n, block = std::min(groups, chunk_ops_);
   ScratchGuard sg(pool_, block * 3 * K * n * sizeof(u64), s);
   if (!sg.p) return kOutOfMemory;
@@ -557,7 +599,7 @@ int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, 
   for (size_t g0 = 0; g0 < groups; g0 += block) {
     const size_t c = std::min(block, groups - g0);
     const size_t off = g0 * terms * 2 * K * n;  // (b == a stays b + off == a + off: the squaring form)
-    if (int rc = multiply_sum(a + off, b + off, sum3, c, terms, s, false)) return rc;
+    if (int rc = multiply_sum(a + off, b + off, sum3, c, terms, s, false, wl.wt)) return rc;
     KeySel sel = rk;
     sel.first = rk.first + g0;
     if (int rc = relinearize(sum3, sel, out2 + g0 * 2 * K * n, c, s, nullptr, false)) return rc;

@@ -179,6 +179,19 @@ int plan_multiply_sum(size_t groups, size_t terms, size_t chunk, Visit&& visit) 
   return 0;
 }
 
+// The weight table of the weighted sums (Evaluator::multiply_sum with weights; hipbfv_debug_weight_residues prints it): out[t * count + i]
+// = {w_t mod primes[i], canonical in [0, q), and its Shoup quotient floor(r * 2^64 / q)}.  Any int32_t is a weight.
+inline void weight_residues(const u64* primes, size_t count, const int32_t* weights, size_t terms, MulOp* out) {
+  for (size_t t = 0; t < terms; t++)
+    for (size_t i = 0; i < count; i++) {
+      const u64 q = primes[i];
+      const int64_t w = weights[t];
+      const u64 m = (u64)(w < 0 ? -w : w) % q;
+      const u64 r = w < 0 && m ? q - m : m;
+      out[t * count + i] = MulOp{r, (u64)(((unsigned __int128)r << 64) / q)};
+    }
+}
+
 // Transparent-result watch of the batched path.  While a WatchScope is alive on the calling thread, every Evaluator
 // operation that produces ciphertexts records, in the device word it was given, the smallest batch index whose result is
 // transparent (all polynomials but the first are zero; 0xFFFFFFFF = none): the reference's SEAL build throws on such a
@@ -225,9 +238,17 @@ class Evaluator {
   // sum does not matter), written once per group.  Where multiply() takes the split kernels for groups * terms items, the last of them
   // sums in registers (launch_mul_tail_sum); otherwise multiply() runs into a staging buffer that the element-wise kernel folds.
   // The launch sequences are plan_multiply_sum's over chunk_ops().  A transparent term inside a non-transparent sum is not seen.
-  int multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch = true);
-  // out2[g] = relinearize(sum_t a[g][t] * b[g][t]): one key switch per GROUP; rk selects per group
-  int multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s);
+  // wt (optional; callers inside the class, which stage it): a DEVICE table MulOp[terms][K] of weights (weight_residues above), shared
+  // by every group -- out3[g] = sum_t w_t (.) a[g][t] * b[g][t], the weight applied to the finished canonical residues of a term
+  // just before they are added (mul_tail_sum_weighted_kernel; scaled_accumulate_kernel on the folded path).  A slice that starts at
+  // term0 reads the table from row term0.
+  int multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch = true, const MulOp* wt = nullptr);
+  // weights: a HOST array of `terms` entries, read before the call returns and staged once (stage_weights).  All weights 1: the call above.
+  int multiply_sum_weighted(const u64* a, const u64* b, const int32_t* weights, u64* out3, size_t groups, size_t terms, hipStream_t s);
+  // out2[g] = relinearize(sum_t a[g][t] * b[g][t]): one key switch per GROUP; rk selects per group.  weights (optional): as above,
+  // staged once for the whole call, not once per block of groups
+  int multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s,
+                         const int32_t* weights = nullptr);
   // out2 = (sigma_g(c0), 0) + switch_key(sigma_g(c1), key)
   int apply_galois(const u64* ct2, u32 galois_elt, const KeySel& key, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr);
   // every item by its OWN Galois element in one key-switch pass (mixed-step rotation batches): elts / keys are HOST arrays of `count`
@@ -320,6 +341,17 @@ class Evaluator {
   // item 0xFFFFFFFF, which the middle kernels drop.
   static constexpr u32 kKeyNone = 0xFFFFFFFFu;
   int stage_keymap(const KeySel& sel, size_t count, size_t chunk, hipStream_t s, KeyMapLease& lease, const u32* item_words = nullptr);
+  // the device weight table of one weighted call: a pinned block and one H2D copy on the call's stream, as stage_keymap's; both
+  // buffers go back to their pools behind the call's last launch.  wt stays nullptr when every weight is 1 (the unweighted launches).
+  struct WeightLease {
+    Evaluator* ev = nullptr;
+    hipStream_t s = nullptr;
+    void* dev = nullptr;
+    void* host = nullptr;
+    const MulOp* wt = nullptr;
+    ~WeightLease();
+  };
+  int stage_weights(const int32_t* weights, size_t terms, hipStream_t s, WeightLease& lease);
   PinnedPool pinned_;
   Context* ctx_;
   u32* status_dev_ = nullptr;

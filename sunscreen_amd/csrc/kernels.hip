@@ -1068,6 +1068,31 @@ __global__ __launch_bounds__(kCoefThreads) void eltwise_kernel(const DevCtx* __r
   *reinterpret_cast<u64x2_t*>(out + off) = r;
 }
 
+// out = acc + w * x mod q_i per residue row (the fold of Evaluator::multiply_sum's weighted sums where the whole-polynomial multiply
+// runs): wrow[i] = the weight mod q_i, canonical, with its Shoup quotient -- indexed by the row alone, a scalar load.  acc == nullptr
+// starts a sum (out = w * x); acc may be out.  Same layout and grid as eltwise_kernel.
+__global__ __launch_bounds__(kCoefThreads) void scaled_accumulate_kernel(const DevCtx* __restrict__ ctx, const u64* acc, const u64* __restrict__ x,
+                                                                         const MulOp* __restrict__ wrow, u64* out) {
+  typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
+  const u32 n = ctx->n, K = ctx->K;
+  const u32 k = 2u * (blockIdx.x * kCoefThreads + threadIdx.x);
+  const u32 res = blockIdx.y;
+  if (k >= n) return;
+  const u64 q = ctx->mod[res % K].q;
+  const MulOp w = wrow[res % K];
+  const size_t off = (size_t)res * n + k;
+  const u64x2_t v = *reinterpret_cast<const u64x2_t*>(x + off);
+  u64x2_t r;
+  r.x = mul_shoup(v.x, w, q);
+  r.y = mul_shoup(v.y, w, q);
+  if (acc) {
+    const u64x2_t a = *reinterpret_cast<const u64x2_t*>(acc + off);
+    r.x = add_mod(a.x, r.x, q);
+    r.y = add_mod(a.y, r.y, q);
+  }
+  *reinterpret_cast<u64x2_t*>(out + off) = r;
+}
+
 // c0 +/-= round(q/t * m)  (SEAL multiply_add_plain_with_scaling_variant); ct u64[ops][size][K][N]
 // plain u64[ops or 1][N] (values < t, zero padded); pstride = 0 broadcasts one plaintext
 __global__ __launch_bounds__(kCoefThreads) void plain_addsub_kernel(const DevCtx* __restrict__ ctx, u64* __restrict__ ct, size_t ctstride,
@@ -1390,6 +1415,12 @@ hipError_t launch_galois(const DevCtx* ctx, u32 n, u32 K, const u64* in, u64* ou
 hipError_t launch_eltwise(const DevCtx* ctx, u32 n, const u64* a, const u64* b, u64* out, size_t residue_polys, int mode, hipStream_t s) {
   // caller guarantees residue_polys <= 65535 and that `a` starts at a residue index that is a multiple of K
   eltwise_kernel<<<coef_grid(n / 2, (u32)residue_polys), kCoefThreads, 0, s>>>(ctx, a, b, out, mode);
+  return hipGetLastError();
+}
+
+hipError_t launch_scaled_accumulate(const DevCtx* ctx, u32 n, const u64* acc, const u64* x, const MulOp* wrow, u64* out, size_t residue_polys, hipStream_t s) {
+  // as launch_eltwise: residue_polys <= 65535, x starts at a residue index that is a multiple of K
+  scaled_accumulate_kernel<<<coef_grid(n / 2, (u32)residue_polys), kCoefThreads, 0, s>>>(ctx, acc, x, wrow, out);
   return hipGetLastError();
 }
 

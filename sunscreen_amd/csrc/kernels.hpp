@@ -82,8 +82,9 @@ hipError_t launch_mul_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, bool a
                            size_t ops, hipStream_t s, u32 poly0 = 0, u32 npolys = 3);
 // the summing form (Evaluator::multiply_sum): D = [groups][terms][3][R][N]; out3[g] = the sum over group g's terms of what launch_mul_tail
 // writes for each (canonical, u64[groups][3][K][N]); accumulate: added onto the rows already in out3.  groups <= 65535 (grid z).
+// wt (optional, the weighted sums): a DEVICE table MulOp[terms][K] -- term t's product enters the sum multiplied by wt[t][i] mod q_i
 hipError_t launch_mul_tail_sum(const DevCtx* ctx, const MulOp* twi, u32 logn, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out3,
-                               size_t groups, size_t terms, bool accumulate, hipStream_t s);
+                               size_t groups, size_t terms, bool accumulate, hipStream_t s, const MulOp* wt = nullptr);
 hipError_t launch_mulrelin_head(const DevCtx* ctx, const MulOp* twi, const MulOp* twf, u32 logn, int pack_mul, bool conv_grid, int pack_ks, u32 kneed,
                                 const u64* D, u64* T, size_t ops, hipStream_t s);
 // Per-member epilogue of a MERGED multiply + relinearize launch (the graph executor's members x batch items): item i of the launch is
@@ -107,6 +108,8 @@ hipError_t launch_ks_moddown(const DevCtx* ctx, u32 n, const u64* ACC, const u64
 hipError_t launch_mod_switch(const DevCtx* ctx, u32 n, const u64* in, u64* out, size_t polys, hipStream_t s);
 hipError_t launch_galois(const DevCtx* ctx, u32 n, u32 K, const u64* in, u64* out, size_t polys, u32 ginv, hipStream_t s);
 hipError_t launch_eltwise(const DevCtx* ctx, u32 n, const u64* a, const u64* b, u64* out, size_t residue_polys, int mode, hipStream_t s);
+// out = acc + w * x mod q per residue row (acc == nullptr: out = w * x); wrow = DEVICE MulOp[K], row r takes wrow[r % K]; acc may be out
+hipError_t launch_scaled_accumulate(const DevCtx* ctx, u32 n, const u64* acc, const u64* x, const MulOp* wrow, u64* out, size_t residue_polys, hipStream_t s);
 hipError_t launch_plain_addsub(const DevCtx* ctx, u32 n, u64* ct, size_t ctstride, const u64* plain, size_t pstride, size_t ops, int sub, hipStream_t s);
 hipError_t launch_plain_lift(const DevCtx* ctx, u32 n, const u64* plain, size_t pstride, u64* out, size_t ops, u32* nonzero, hipStream_t s);
 hipError_t launch_ct_plain(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, u32 logn, u32 K, bool any_d, bool any_i, const u64* pn, size_t pnstride,

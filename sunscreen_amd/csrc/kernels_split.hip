@@ -2398,9 +2398,10 @@ __global__ EDGE_BOUNDS(KMAX) void mul_tail_kernel(const DevCtx* __restrict__ ctx
 // once per group: the 3 K rows of a term never travel through HBM.
 // accumulate: the sums start from the words already in out (a group longer than a chunk arrives in slices); otherwise out is only written.
 // The sums are held as acc[k][i] = residue i of coefficient slot k.
-template <int L, int KMAX>
+// W: the weighted form (mul_tail_sum_weighted_kernel below) -- wrow[i] = this term's weight mod q_i with its Shoup quotient
+template <int L, int KMAX, bool W = false>
 __device__ __forceinline__ void mul_tail_sum_term_int(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base, const u64* __restrict__ d, u32 t,
-                                                      u64 (&acc)[4][KMAX]) {
+                                                      u64 (&acc)[4][KMAX], const MulOp* __restrict__ wrow = nullptr) {
   // the integer base: mul_tail_kernel's general arm -- the same walk over the K + S rows of D with the next row requested before the
   // current one is transformed, then one coefficient per trip through behz_floor_sk_coeff
   constexpr u32 N = 1u << L;
@@ -2461,7 +2462,12 @@ __device__ __forceinline__ void mul_tail_sum_term_int(const DevCtx* __restrict__
     u64 r[KMAX], a0[KMAX];
     behz_floor_sk_coeff<KMAX>(ctx, y[0], xb[0], r);
 #pragma unroll
-    for (int i = 0; i < KMAX; i++) a0[i] = (u32)i < K ? add_mod(acc[0][i], r[i], ctx->mod[i].q) : 0ull;
+    for (int i = 0; i < KMAX; i++) {
+      if constexpr (W)
+        a0[i] = (u32)i < K ? add_mod(acc[0][i], mul_shoup(r[i], wrow[i], ctx->mod[i].q), ctx->mod[i].q) : 0ull;
+      else
+        a0[i] = (u32)i < K ? add_mod(acc[0][i], r[i], ctx->mod[i].q) : 0ull;
+    }
 #pragma unroll
     for (int kk = 0; kk < 3; kk++) {
 #pragma unroll
@@ -2550,6 +2556,94 @@ __global__ __launch_bounds__(kHeadThreads, (kTailSumThroughOut<KMAX> ? 2 : 1)) v
         }
     } else {
       mul_tail_sum_term_int<L, KMAX>(ctx, twi_base, d, t, acc);
+    }
+  }
+  const BufRsrc ro = buf_rsrc(o);
+#pragma unroll
+  for (int i = 0; i < KMAX; i++)
+    if ((u32)i < K) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) st_tail_out<L>(buf_row(ro, (size_t)i * N), t, k, acc[k][i]);
+    }
+}
+
+// The weighted summing form (Evaluator::multiply_sum with weights: sum_t w_t * a_t * b_t): mul_tail_sum_kernel with every finished
+// canonical residue r of term t, prime i replaced by r * wt[t][i] mod q_i just before it is added.  wt = MulOp[terms][K] of this
+// launch's terms (the weight mod q_i, canonical, and its Shoup quotient), indexed by the term and the prime only: wave-uniform, scalar
+// loads.  A sibling and not a template parameter: mul_tail_sum_kernel's instantiations keep their names and their instructions.  The
+// through-output form scales row by row inside the i loop, so nothing beyond mul_tail_compute_d's registers and one row is live.
+template <int L, int KMAX, bool AUXD, int PACK, bool GRID>
+__global__ __launch_bounds__(kHeadThreads, (kTailSumThroughOut<KMAX> ? 2 : 1)) void mul_tail_sum_weighted_kernel(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base, const u64* __restrict__ D,
+                                                      u64* __restrict__ out, const MulOp* __restrict__ wt, u32 terms, u32 accumulate) {
+  constexpr u32 N = 1u << L;
+  constexpr bool mixed = !AUXD && PACK;
+  static_assert(!mixed || TAIL_MIXED_NC == 4, "the mixed summing tail finishes four coefficients at once (mul_tail_compute_mixed)");
+  const u32 t = blockIdx.x * kHeadThreads + threadIdx.x;
+  const u32 poly = blockIdx.y, group = blockIdx.z;
+  const u32 K = ctx->K, R = K + ctx->S;
+  u64* o = out + ((size_t)group * 3 + poly) * K * N;
+  const size_t term_words = (size_t)3 * R * N;
+  const u64* d = D + ((size_t)group * terms * 3 + poly) * R * N;
+  if constexpr (kTailSumThroughOut<KMAX>) {
+    static_assert(AUXD, "only the all-FP64 instantiation exists for 5..8 data primes");
+    const BufRsrc ro = buf_rsrc(o);
+#pragma unroll 1
+    for (u32 term = 0; term < terms; term++, d += term_words) {
+      u64 res[KMAX][4];
+      mul_tail_compute_d<L, KMAX, PACK, GRID>(ctx, twi_base, d, t, res);
+      const BufRsrc rin = buf_rsrc_opt(o, (accumulate | term) != 0);
+      const MulOp* __restrict__ wrow = wt + (size_t)term * K;
+#pragma unroll
+      for (int i = 0; i < KMAX; i++)
+        if ((u32)i < K) {
+          const u64 q = ctx->mod[i].q;
+          const MulOp w = wrow[i];
+          u64 v[4];
+#pragma unroll
+          for (int k = 0; k < 4; k++) v[k] = ld_tail_out<L>(buf_row(rin, (size_t)i * N), t, k);
+#pragma unroll
+          for (int k = 0; k < 4; k++) st_tail_out<L>(buf_row(ro, (size_t)i * N), t, k, add_mod(v[k], mul_shoup(res[i][k], w, q), q));
+        }
+    }
+    return;
+  }
+  u64 acc[4][KMAX];
+  {
+    const BufRsrc rin = buf_rsrc_opt(o, accumulate != 0);
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) {
+      const BufRow row = buf_row(rin, (size_t)((u32)i < K ? (u32)i : K - 1) * N);
+#pragma unroll
+      for (int k = 0; k < 4; k++) acc[k][i] = ld_tail_out<L>(row, t, k);
+    }
+  }
+#pragma unroll 1
+  for (u32 term = 0; term < terms; term++, d += term_words) {
+    const MulOp* __restrict__ wrow = wt + (size_t)term * K;
+    if constexpr (AUXD) {
+      u64 res[KMAX][4];
+      mul_tail_compute_d<L, KMAX, PACK, GRID>(ctx, twi_base, d, t, res);
+#pragma unroll
+      for (int i = 0; i < KMAX; i++)
+        if ((u32)i < K) {
+          const u64 q = ctx->mod[i].q;
+          const MulOp w = wrow[i];
+#pragma unroll
+          for (int k = 0; k < 4; k++) acc[k][i] = add_mod(acc[k][i], mul_shoup(res[i][k], w, q), q);
+        }
+    } else if constexpr (mixed) {
+      u64 res[4][KMAX];
+      mul_tail_compute_mixed<L, KMAX>(ctx, twi_base, d, t, res);
+#pragma unroll
+      for (int i = 0; i < KMAX; i++)
+        if ((u32)i < K) {
+          const u64 q = ctx->mod[i].q;
+          const MulOp w = wrow[i];
+#pragma unroll
+          for (int k = 0; k < 4; k++) acc[k][i] = add_mod(acc[k][i], mul_shoup(res[k][i], w, q), q);
+        }
+    } else {
+      mul_tail_sum_term_int<L, KMAX, true>(ctx, twi_base, d, t, acc, wrow);
     }
   }
   const BufRsrc ro = buf_rsrc(o);
@@ -3267,9 +3361,15 @@ hipError_t launch_mul_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, bool a
 // the instantiations of mul_tail_t, summing over the terms of a group
 template <int L>
 static hipError_t mul_tail_sum_t(const DevCtx* ctx, const MulOp* twi, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out3, size_t groups,
-                                 size_t terms, bool accumulate, hipStream_t s) {
+                                 size_t terms, bool accumulate, const MulOp* wt, hipStream_t s) {
   const dim3 grid((1u << L) / 4 / kHeadThreads, 3, (unsigned)groups);
-#define MTS(KM, AD, PK, GR) mul_tail_sum_kernel<L, KM, AD, PK, GR><<<grid, kHeadThreads, 0, s>>>(ctx, twi, D, out3, (u32)terms, accumulate ? 1u : 0u)
+#define MTS(KM, AD, PK, GR)                                                                                                                  \
+  do {                                                                                                                                       \
+    if (wt)                                                                                                                                  \
+      mul_tail_sum_weighted_kernel<L, KM, AD, PK, GR><<<grid, kHeadThreads, 0, s>>>(ctx, twi, D, out3, wt, (u32)terms, accumulate ? 1u : 0u); \
+    else                                                                                                                                     \
+      mul_tail_sum_kernel<L, KM, AD, PK, GR><<<grid, kHeadThreads, 0, s>>>(ctx, twi, D, out3, (u32)terms, accumulate ? 1u : 0u);              \
+  } while (0)
   if (kneed > 4) {
     if (pack == 2) { if (conv_grid) MTS(8, true, 2, true); else MTS(8, true, 2, false); }
     else if (pack) { if (conv_grid) MTS(8, true, 1, true); else MTS(8, true, 1, false); }
@@ -3286,9 +3386,9 @@ static hipError_t mul_tail_sum_t(const DevCtx* ctx, const MulOp* twi, bool aux_f
   return hipGetLastError();
 }
 hipError_t launch_mul_tail_sum(const DevCtx* ctx, const MulOp* twi, u32 logn, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out3,
-                               size_t groups, size_t terms, bool accumulate, hipStream_t s) {
+                               size_t groups, size_t terms, bool accumulate, hipStream_t s, const MulOp* wt) {
   if (!groups || groups > 65535 || !terms || terms > 0xFFFFFFFFull) return hipErrorInvalidValue;
-  SPLIT_DISPATCH(mul_tail_sum_t, ctx, twi, aux_f64, pack, conv_grid && aux_f64, kneed, D, out3, groups, terms, accumulate, s)
+  SPLIT_DISPATCH(mul_tail_sum_t, ctx, twi, aux_f64, pack, conv_grid && aux_f64, kneed, D, out3, groups, terms, accumulate, wt, s)
 }
 
 template <int L>
