@@ -407,6 +407,43 @@ long hipbfv_batch_multiply_sum_weighted_relin(void *evaluator, const uint64_t *a
 long hipbfv_batch_multiply_sum_weighted_relin_keys(void *evaluator, const uint64_t *a, const uint64_t *b, const int32_t *weights,
                                                    void *const *relin_key_sets, uint64_t num_key_sets, const uint32_t *key_index,
                                                    uint64_t *out2, uint64_t groups, uint64_t terms, void *stream);
+/* Prepared multiplicands: products that share their second operand -- a ciphertext matrix times a ciphertext vector (out[g] =
+ * sum_t A[g][t] * x[t], every x[t] used by all groups), one encrypted query scored against many records, one ciphertext times a
+ * batch.  hipbfv_Multiplicand_Create copies `count` ciphertexts (ct2: a device array u64[count][2][K][N]) and, where the parameter
+ * set has a split multiply (N = 4096 ... 16384), extends and forward-transforms both polynomials of each ONCE; the four calls
+ * below then extend and transform `a` alone.  Nothing is replicated in memory and nothing is transformed twice.
+ *  - The object: owned by the caller (hipbfv_Multiplicand_Destroy, which waits for the device); asynchronous on `stream` -- ct2
+ *    may be overwritten once the work queued on `stream` has passed it.  It records an event behind its last launch, and every call
+ *    that uses it makes its own stream wait on that event: the product may run on another stream without a host synchronisation.
+ *    hipbfv_Multiplicand_Count gives `count`, hipbfv_Multiplicand_Bytes the device memory it holds (the copy and, with a split
+ *    multiply, 2 (K + S) N words per ciphertext of transformed rows, S = the auxiliary base's size).  It may be used by any number
+ *    of calls, on any stream, from any evaluator of the context it was made with.
+ *  - b_index is a HOST array of `index_len` entries, read before the call returns: item i multiplies a[i] by prepared ciphertext
+ *    b_index[i % index_len]; in the sum forms i = g * terms + t.  {0} broadcasts one ciphertext, {0, ..., terms - 1} is the
+ *    matrix-vector product, index_len == count an arbitrary mapping.
+ *  - Bits: item i of hipbfv_batch_multiply_shared is, word for word, hipbfv_batch_multiply of a[i] with a copy of that ciphertext;
+ *    the other three equal hipbfv_batch_multiply_relin, hipbfv_batch_multiply_sum and hipbfv_batch_multiply_sum_relin on the
+ *    replicated array.  The path (split kernels or whole-polynomial kernels, fused relinearization, chunks and slices) is the
+ *    counterpart's for the same item count; off the split path the chunk's multiplicands are gathered from the object's copy.
+ *  - Refusals, all before anything is launched or written: a NULL a, output, multiplicand or b_index is HIPBFV_E_POINTER;
+ *    index_len == 0, terms == 0 or an index >= the object's count is HIPBFV_E_INVALIDARG (hipbfv_last_error names the first such
+ *    item); so is a multiplicand made by an evaluator of another context; a missing relinearization key fails as in the
+ *    counterpart.  Aliasing: out2 of hipbfv_batch_multiply_relin_shared may be exactly `a`; any other overlap of an output with `a`
+ *    is HIPBFV_E_INVALIDARG.  count == 0 / groups == 0 returns HIPBFV_S_OK with no launch; hipbfv_Multiplicand_Create with
+ *    count == 0 is HIPBFV_E_INVALIDARG.
+ *  - Transparent results are recorded as in the counterparts: by item number, by GROUP number in the sum forms. */
+long hipbfv_Multiplicand_Create(void *evaluator, const uint64_t *ct2, uint64_t count, void *stream, void **multiplicand);
+long hipbfv_Multiplicand_Destroy(void *multiplicand);
+long hipbfv_Multiplicand_Count(void *multiplicand, uint64_t *count);
+long hipbfv_Multiplicand_Bytes(void *multiplicand, uint64_t *bytes);
+long hipbfv_batch_multiply_shared(void *evaluator, const uint64_t *a, void *multiplicand, const uint32_t *b_index, uint64_t index_len,
+                                  uint64_t *out3, uint64_t count, void *stream);
+long hipbfv_batch_multiply_relin_shared(void *evaluator, const uint64_t *a, void *multiplicand, const uint32_t *b_index, uint64_t index_len,
+                                        void *relin_keys, uint64_t *out2, uint64_t count, void *stream);
+long hipbfv_batch_multiply_sum_shared(void *evaluator, const uint64_t *a, void *multiplicand, const uint32_t *b_index, uint64_t index_len,
+                                      uint64_t *out3, uint64_t groups, uint64_t terms, void *stream);
+long hipbfv_batch_multiply_sum_relin_shared(void *evaluator, const uint64_t *a, void *multiplicand, const uint32_t *b_index,
+                                            uint64_t index_len, void *relin_keys, uint64_t *out2, uint64_t groups, uint64_t terms, void *stream);
 long hipbfv_batch_apply_galois_keys(void *evaluator, const uint64_t *ct2, uint32_t galois_elt, void *const *galois_key_sets,
                                     uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t count,
                                     void *stream);

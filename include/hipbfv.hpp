@@ -520,6 +520,25 @@ class Decryptor : public detail::Handle<Decryptor_Destroy, detail::no_copy> {
   }
 };
 
+// A prepared second operand (BFVEvaluator::prepare_multiplicand): ciphertexts kept on the device, transformed once, usable by any
+// number of *_shared calls on any stream.  Not part of the reference crate's surface.
+class Multiplicand : public detail::Handle<hipbfv_Multiplicand_Destroy, detail::no_copy> {
+ public:
+  Multiplicand(const Multiplicand&) = delete;
+  Multiplicand(Multiplicand&&) = default;
+  explicit Multiplicand(void* h) : Handle(h) {}
+  uint64_t count() const {
+    uint64_t n = 0;
+    check(hipbfv_Multiplicand_Count(h_, &n));
+    return n;
+  }
+  uint64_t bytes() const {  // device memory held: the copy of the ciphertexts and their transformed rows
+    uint64_t n = 0;
+    check(hipbfv_Multiplicand_Bytes(h_, &n));
+    return n;
+  }
+};
+
 // ---- trait Evaluator (evaluator.rs:7-280) implemented by BFVEvaluator (bfv_evaluator.rs:27-244, evaluator_base.rs) ----
 class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
  public:
@@ -670,6 +689,30 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
   void multiply_sum_relin(const uint64_t* a, const uint64_t* b, const RelinearizationKeys& rk, uint64_t* out2, uint64_t groups, uint64_t terms,
                           void* stream = nullptr) const {
     check(hipbfv_batch_multiply_sum_relin(h_, a, b, rk.get_handle(), out2, groups, terms, stream));
+  }
+  // Prepared multiplicands (hipbfv.h): ct2 = u64[count][2][K][N] on the device is copied and transformed once; item i of a *_shared call
+  // multiplies a[i] by prepared ciphertext b_index[i % b_index.size()] (in the sum forms i = g * terms + t) -- the words of the call on the
+  // replicated operand.  out2 of multiply_relin_shared may be exactly a.
+  Multiplicand prepare_multiplicand(const uint64_t* ct2, uint64_t count, void* stream = nullptr) const {
+    void* m = nullptr;
+    check(hipbfv_Multiplicand_Create(h_, ct2, count, stream, &m));
+    return Multiplicand(m);
+  }
+  void multiply_shared(const uint64_t* a, const Multiplicand& m, const std::vector<uint32_t>& b_index, uint64_t* out3, uint64_t count,
+                       void* stream = nullptr) const {
+    check(hipbfv_batch_multiply_shared(h_, a, m.get_handle(), b_index.data(), b_index.size(), out3, count, stream));
+  }
+  void multiply_relin_shared(const uint64_t* a, const Multiplicand& m, const std::vector<uint32_t>& b_index, const RelinearizationKeys& rk,
+                             uint64_t* out2, uint64_t count, void* stream = nullptr) const {
+    check(hipbfv_batch_multiply_relin_shared(h_, a, m.get_handle(), b_index.data(), b_index.size(), rk.get_handle(), out2, count, stream));
+  }
+  void multiply_sum_shared(const uint64_t* a, const Multiplicand& m, const std::vector<uint32_t>& b_index, uint64_t* out3, uint64_t groups,
+                           uint64_t terms, void* stream = nullptr) const {
+    check(hipbfv_batch_multiply_sum_shared(h_, a, m.get_handle(), b_index.data(), b_index.size(), out3, groups, terms, stream));
+  }
+  void multiply_sum_relin_shared(const uint64_t* a, const Multiplicand& m, const std::vector<uint32_t>& b_index, const RelinearizationKeys& rk,
+                                 uint64_t* out2, uint64_t groups, uint64_t terms, void* stream = nullptr) const {
+    check(hipbfv_batch_multiply_sum_relin_shared(h_, a, m.get_handle(), b_index.data(), b_index.size(), rk.get_handle(), out2, groups, terms, stream));
   }
   // ... group g through keys[key_index[g]]; an entry of `keys` that no group names may be nullptr
   void multiply_sum_relin_keys(const uint64_t* a, const uint64_t* b, const std::vector<const RelinearizationKeys*>& keys,

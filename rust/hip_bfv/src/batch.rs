@@ -45,6 +45,32 @@ fn same_count(a: &DeviceBatch, b: &DeviceBatch) -> Result<()> {
     Ok(())
 }
 
+/// A prepared second operand ([`BatchEvaluator::prepare`]): ciphertexts kept on the device, transformed once, usable by any number
+/// of `*_shared` calls on any stream (the object carries an event).
+pub struct Multiplicand {
+    h: *mut c_void,
+}
+
+impl Multiplicand {
+    pub fn count(&self) -> Result<u64> {
+        let mut n = 0u64;
+        check(unsafe { bindgen::hipbfv_Multiplicand_Count(self.h, &mut n) })?;
+        Ok(n)
+    }
+    /// Device memory held: the copy of the ciphertexts and their transformed rows.
+    pub fn bytes(&self) -> Result<u64> {
+        let mut n = 0u64;
+        check(unsafe { bindgen::hipbfv_Multiplicand_Bytes(self.h, &mut n) })?;
+        Ok(n)
+    }
+}
+
+impl Drop for Multiplicand {
+    fn drop(&mut self) {
+        unsafe { bindgen::hipbfv_Multiplicand_Destroy(self.h) };
+    }
+}
+
 pub struct BatchEvaluator<'e> {
     eval: &'e BFVEvaluator,
     stream: *mut c_void,
@@ -172,6 +198,38 @@ impl<'e> BatchEvaluator<'e> {
         check(unsafe {
             bindgen::hipbfv_batch_multiply_sum_weighted_relin_keys(self.h(), a.ptr, b.ptr, weights.as_ptr(), handles.as_ptr(), handles.len() as u64, key_index.as_ptr(), out.ptr,
                                                                    out.count, terms, self.stream)
+        })
+    }
+    // ---- prepared multiplicands: a shared second operand extended and transformed once (include/hipbfv.h) ----
+    // Item i multiplies `a[i]` by prepared ciphertext `b_index[i % b_index.len()]`; in the sum forms i = g * terms + t.
+    /// Copies the size-2 ciphertexts of `ct` and, where the parameter set has a split multiply, transforms them once.
+    pub fn prepare(&self, ct: DeviceBatch) -> Result<Multiplicand> {
+        let mut h: *mut c_void = null_mut();
+        check(unsafe { bindgen::hipbfv_Multiplicand_Create(self.h(), ct.ptr, ct.count, self.stream, &mut h) })?;
+        Ok(Multiplicand { h })
+    }
+    pub fn multiply_shared(&self, a: DeviceBatch, m: &Multiplicand, b_index: &[u32], out3: DeviceBatch) -> Result<()> {
+        same_count(&a, &out3)?;
+        check(unsafe { bindgen::hipbfv_batch_multiply_shared(self.h(), a.ptr, m.h, b_index.as_ptr(), b_index.len() as u64, out3.ptr, a.count, self.stream) })
+    }
+    /// `out` may be exactly `a`.
+    pub fn multiply_relin_shared(&self, a: DeviceBatch, m: &Multiplicand, b_index: &[u32], rk: &RelinearizationKeys, out: DeviceBatch) -> Result<()> {
+        same_count(&a, &out)?;
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_relin_shared(self.h(), a.ptr, m.h, b_index.as_ptr(), b_index.len() as u64, rk.get_handle(), out.ptr, a.count, self.stream)
+        })
+    }
+    pub fn multiply_sum_shared(&self, a: DeviceBatch, m: &Multiplicand, b_index: &[u32], terms: u64, out3: DeviceBatch) -> Result<()> {
+        Self::sum_shape_ok(&a, &a, terms, &out3)?;
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_sum_shared(self.h(), a.ptr, m.h, b_index.as_ptr(), b_index.len() as u64, out3.ptr, out3.count, terms, self.stream)
+        })
+    }
+    pub fn multiply_sum_relin_shared(&self, a: DeviceBatch, m: &Multiplicand, b_index: &[u32], terms: u64, rk: &RelinearizationKeys, out: DeviceBatch) -> Result<()> {
+        Self::sum_shape_ok(&a, &a, terms, &out)?;
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_sum_relin_shared(self.h(), a.ptr, m.h, b_index.as_ptr(), b_index.len() as u64, rk.get_handle(), out.ptr, out.count, terms,
+                                                            self.stream)
         })
     }
     pub fn rotate_rows_keys(&self, a: DeviceBatch, steps: i32, keys: &[&GaloisKeys], key_index: &[u32], out: DeviceBatch) -> Result<()> {

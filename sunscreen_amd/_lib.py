@@ -228,6 +228,14 @@ _SIGNATURES = {
     "hipbfv_batch_multiply_sum_weighted_relin": [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, u64, u64, vp],
     "hipbfv_batch_multiply_sum_weighted_relin_keys": [vp, vp, vp, C.POINTER(C.c_int32), vpp, u64, C.POINTER(C.c_uint32), vp, u64, u64, vp],
     "hipbfv_debug_weight_residues": [u64p, u64, C.POINTER(C.c_int32), u64, u64p],
+    "hipbfv_Multiplicand_Create": [vp, vp, u64, vp, vpp],
+    "hipbfv_Multiplicand_Destroy": [vp],
+    "hipbfv_Multiplicand_Count": [vp, u64p],
+    "hipbfv_Multiplicand_Bytes": [vp, u64p],
+    "hipbfv_batch_multiply_shared": [vp, vp, vp, C.POINTER(C.c_uint32), u64, vp, u64, vp],
+    "hipbfv_batch_multiply_relin_shared": [vp, vp, vp, C.POINTER(C.c_uint32), u64, vp, vp, u64, vp],
+    "hipbfv_batch_multiply_sum_shared": [vp, vp, vp, C.POINTER(C.c_uint32), u64, vp, u64, u64, vp],
+    "hipbfv_batch_multiply_sum_relin_shared": [vp, vp, vp, C.POINTER(C.c_uint32), u64, vp, vp, u64, u64, vp],
     "hipbfv_profile_enable": [vp, C.c_bool],
     "hipbfv_profile_reset": [vp],
     "hipbfv_profile_kernel_count": [C.POINTER(C.c_uint32)],

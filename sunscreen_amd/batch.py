@@ -248,6 +248,54 @@ class BatchEvaluator:
                                                                          groups, terms, _stream()))
         return out
 
+    # ---- prepared multiplicands: a shared second operand transformed once (include/hipbfv.h) ----
+    def prepare(self, ct: torch.Tensor) -> "Multiplicand":
+        """ct: [count, 2, K, N].  The ciphertexts are copied and, where the parameter set has a split multiply, extended and
+        transformed once; asynchronous on the current stream.  The object may be used on any stream (it carries an event)."""
+        self._shape_ok(ct, 2)
+        h = C.c_void_p()
+        _check(_lib.load().hipbfv_Multiplicand_Create(self._h, _ptr(ct), ct.shape[0], _stream(), C.byref(h)))
+        return Multiplicand(h, self.ctx)
+
+    @staticmethod
+    def _b_index(b_index):
+        idx = np.ascontiguousarray(np.asarray(b_index, dtype=np.uint32)).reshape(-1)
+        return idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size, idx
+
+    def multiply_shared(self, a: torch.Tensor, m: "Multiplicand", b_index, out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[i] = a[i] * m[b_index[i % len(b_index)]] as size-3 ciphertexts: the words of multiply() on the replicated operand."""
+        self._shape_ok(a, 2)
+        out = out if out is not None else self._new(a.shape[0], 3, a)
+        ip, n, _keep = self._b_index(b_index)
+        _check(_lib.load().hipbfv_batch_multiply_shared(self._h, _ptr(a), m.get_handle(), ip, n, _ptr(out), a.shape[0], _stream()))
+        return out
+
+    def multiply_relin_shared(self, a: torch.Tensor, m: "Multiplicand", b_index, rk: RelinearizationKeys, out: torch.Tensor | None = None) -> torch.Tensor:
+        """multiply_relin() with the second operands taken from m; `out=a` is allowed."""
+        self._shape_ok(a, 2)
+        out = out if out is not None else self._new(a.shape[0], 2, a)
+        ip, n, _keep = self._b_index(b_index)
+        _check(_lib.load().hipbfv_batch_multiply_relin_shared(self._h, _ptr(a), m.get_handle(), ip, n, rk.get_handle(), _ptr(out), a.shape[0], _stream()))
+        return out
+
+    def multiply_sum_shared(self, a: torch.Tensor, m: "Multiplicand", b_index, out: torch.Tensor | None = None) -> torch.Tensor:
+        """a: [groups, terms, 2, K, N]; out[g] = sum_t a[g, t] * m[b_index[(g * terms + t) % len(b_index)]], [groups, 3, K, N].
+        b_index = range(terms): a ciphertext matrix times the prepared vector."""
+        groups, terms = self._sum_shape(a, a)
+        out = out if out is not None else self._new(groups, 3, a)
+        ip, n, _keep = self._b_index(b_index)
+        _check(_lib.load().hipbfv_batch_multiply_sum_shared(self._h, _ptr(a), m.get_handle(), ip, n, _ptr(out), groups, terms, _stream()))
+        return out
+
+    def multiply_sum_relin_shared(self, a: torch.Tensor, m: "Multiplicand", b_index, rk: RelinearizationKeys, out: torch.Tensor | None = None) -> torch.Tensor:
+        """relinearize(multiply_sum_shared(a, m, b_index)), [groups, 2, K, N]: one key switch per group."""
+        groups, terms = self._sum_shape(a, a)
+        out = out if out is not None else self._new(groups, 2, a)
+        ip, n, _keep = self._b_index(b_index)
+        _check(_lib.load().hipbfv_batch_multiply_sum_relin_shared(self._h, _ptr(a), m.get_handle(), ip, n, rk.get_handle(), _ptr(out), groups, terms,
+                                                                  _stream()))
+        return out
+
     def apply_galois_keys(self, ct: torch.Tensor, galois_elt: int, key_sets: Sequence[GaloisKeys], key_index, out: torch.Tensor | None = None) -> torch.Tensor:
         self._shape_ok(ct, 2)
         out = out if out is not None else self._new(ct.shape[0], 2, ct)
@@ -437,6 +485,41 @@ class BatchEvaluator:
         assert data.dim() == 2 and data.shape[1] == self.n
         _check(_lib.load().hipbfv_batch_ntt(self._h, _ptr(data), data.shape[0], nprimes, inverse, _stream()))
         return data
+
+
+class Multiplicand:
+    """A prepared second operand (BatchEvaluator.prepare): `count` ciphertexts kept on the device, transformed once."""
+
+    def __init__(self, handle, ctx: Context):
+        self._h = handle
+        self.ctx = ctx  # (keeps the context alive)
+
+    def get_handle(self):
+        return self._h
+
+    @property
+    def count(self) -> int:
+        n = C.c_uint64()
+        _check(_lib.load().hipbfv_Multiplicand_Count(self._h, C.byref(n)))
+        return n.value
+
+    @property
+    def nbytes(self) -> int:
+        """Device memory the object holds: the copy of the ciphertexts and their transformed rows."""
+        n = C.c_uint64()
+        _check(_lib.load().hipbfv_Multiplicand_Bytes(self._h, C.byref(n)))
+        return n.value
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            _lib.load().hipbfv_Multiplicand_Destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def rotate_items_plan(n: int, steps, present_elts) -> tuple[list[int], list[int], int]:

@@ -4718,3 +4718,6 @@ HIPBFV_END
 
 }  // extern "C"
 #pragma GCC visibility pop
+
+// ------------------------------------------------------------------ prepared multiplicands (capi_shared.hpp)
+#include "capi_shared.hpp"

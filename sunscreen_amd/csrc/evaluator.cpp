@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <memory>
 
 namespace hipbfv {
 
@@ -153,7 +154,7 @@ const char* kernel_name(int id) {
   static const char* names[kKernCount] = {"ntt_fwd",   "ntt_inv",    "behz_extend", "tensor",  "behz_floor_sk", "ks_decompose",
                                           "ks_mac",    "ks_moddown", "galois",      "eltwise", "plain",
                                           "ks_head",    "ks_mid",      "ks_tail", "mul_head",      "mul_mid",
-                                          "mul_tail",  "mul_tail_sum"};
+                                          "mul_prep",  "mul_tail",   "mul_tail_sum"};
   return id >= 0 && id < kKernCount ? names[id] : "?";
 }
 
@@ -333,40 +334,56 @@ int Evaluator::ntt(u64* data, size_t polys, u32 nprimes, bool inverse, hipStream
   return kOk;
 }
 
-int Evaluator::multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, size_t count, hipStream_t s, bool watch) {
+int Evaluator::multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, size_t count, hipStream_t s, bool watch, const SharedSel* sh) {
   const DevCtx& h = ctx_->host();
   if (sa < 2 || sb < 2 || sa + sb > 16) return kInvalidArg;
+  if (sh && (sa != 2 || sb != 2)) return kInvalidArg;
   if (h.logn > 15) return kUnsupported;
   const u32 n = h.n, K = h.K, S = h.S, R = K + S, sd = sa + sb - 1;
   // the per-coefficient kernels are instantiated for KMAX data primes and KMAX + 2 auxiliary primes
   const u32 kneed = std::max(K, S > 2 ? S - 2 : 0u);
   const bool split = split_mul_ && sa == 2 && sb == 2 && (kneed <= 4 || (kneed <= 8 && h.aux_f64)) && h.logn >= 12 && h.logn <= 14 &&
-                     !few_for_split_mul(count);
+                     !few_for_split_mul(count) && (!sh || sh->m->rows);
   // (the split kernels put the items on grid z; only the whole-polynomial launches count residue polynomials on one grid axis.
   // r06: the 3 x 54-bit multiply of 4096 items ran as 1820 + 1820 + 456 under the shared limit)
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, split ? 65535 : 65535 / (R * (sa + sb))));
   const size_t ext_words = (size_t)(sa + sb) * R * n, d_words = (size_t)sd * R * n;
   const size_t cc = std::min(chunk, count);  // a handle-level call (count = 1) reserves one op's scratch, not a chunk's
-  ScratchGuard sg(pool_, cc * (ext_words + d_words) * sizeof(u64), s);
+  // prepared multiplicands on the whole-polynomial path: the chunk's second operands are gathered behind D
+  const size_t gather_words = sh && !split ? (size_t)2 * K * n : 0;
+  SharedLease sl;
+  if (sh)
+    if (int rc = stage_shared(*sh, count, split, s, sl)) return rc;
+  ScratchGuard sg(pool_, cc * (ext_words + d_words + gather_words) * sizeof(u64), s);
   if (!sg.p) return kOutOfMemory;
   u64* ext = (u64*)sg.p;
   u64* D = ext + cc * ext_words;
+  u64* bstage = D + cc * d_words;
   std::vector<u32> mods;
   for (u32 i = 0; i < K; i++) mods.push_back(i);
   for (u32 j = 0; j < S; j++) mods.push_back(h.KK + j);
   const NttPlan plan = make_plan(1, mods);
   // x * x (Evaluator_Square, a program node with one operand twice): the split kernels extend and transform x once
-  const bool square = split && a == b;
+  const bool square = split && !sh && a == b;
   for (size_t off = 0; off < count; off += chunk) {
     const size_t c = std::min(chunk, count - off);
+    if (split && sh) {
+      // the two-polynomial head on `a`, the middle kernel that reads the prepared rows, the tail unchanged
+      HB_LAUNCH(kKernMulHead, c * 2, launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + off * 2 * K * n, a + off * 2 * K * n, ext, c, s, 2u));
+      HB_LAUNCH(kKernMulMid, c, launch_mul_mid_shared(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, sh->m->rows, sl.idx + off, D, c, s));
+      HB_LAUNCH(kKernMulTail, c * 3, launch_mul_tail(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out + off * 3 * K * n, c, s));
+      continue;
+    }
+    if (sh) HB_CHECK(launch_gather_items(sl.ptrs + off, bstage, gather_words, c, s));
+    const u64* bc = sh ? bstage : b + off * sb * K * n;
     if (split) {
       // head / middle / tail split transforms (kernels_split.hip): 3 launches instead of 5, 40 % less HBM traffic
-      HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + off * 2 * K * n, b + off * 2 * K * n, ext, c, s, square ? 2u : 4u));
+      HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + off * 2 * K * n, bc, ext, c, s, square ? 2u : 4u));
       HB_LAUNCH(kKernMulMid, c, launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square));
       HB_LAUNCH(kKernMulTail, c * 3, launch_mul_tail(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out + off * 3 * K * n, c, s));
       continue;
     }
-    HB_LAUNCH(kKernBehzExtend, c * (sa + sb), launch_behz_extend(ctx_->dev(), n, kneed, a + off * sa * K * n, sa, b + off * sb * K * n, sb, c, ext, s));
+    HB_LAUNCH(kKernBehzExtend, c * (sa + sb), launch_behz_extend(ctx_->dev(), n, kneed, a + off * sa * K * n, sa, bc, sb, c, ext, s));
     HB_LAUNCH(kKernNttFwd, c * (sa + sb) * R, launch_ntt(ctx_->dev(), h.tw_fwd, h.logn, ext, c * (sa + sb) * R, plan, false, 0, s));
     HB_LAUNCH(kKernTensor, c, launch_tensor(ctx_->dev(), n, R, ext, sa, sb, D, c, s));
     HB_LAUNCH(kKernNttInv, c * sd * R, launch_ntt(ctx_->dev(), h.tw_inv, h.logn, D, c * sd * R, plan, true, 1, s));
@@ -512,14 +529,16 @@ int Evaluator::relinearize(const u64* ct3, const KeySel& rk, u64* out2, size_t c
 }
 
 // out3[g] = sum_t a[g][t] * b[g][t] (evaluator.hpp).  The path is multiply()'s choice for groups * terms items.
-int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch, const MulOp* wt) {
+int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch, const MulOp* wt,
+                            const SharedSel* sh) {
   const DevCtx& h = ctx_->host();
   if (!terms) return kInvalidArg;
   if (h.logn > 15) return kUnsupported;
   if (!groups) return kOk;
   const u32 n = h.n, K = h.K, S = h.S, R = K + S;
   const u32 kneed = std::max(K, S > 2 ? S - 2 : 0u);
-  const bool split = split_mul_ && (kneed <= 4 || (kneed <= 8 && h.aux_f64)) && h.logn >= 12 && h.logn <= 14 && !few_for_split_mul(groups * terms);
+  const bool split = split_mul_ && (kneed <= 4 || (kneed <= 8 && h.aux_f64)) && h.logn >= 12 && h.logn <= 14 && !few_for_split_mul(groups * terms) &&
+                     (!sh || sh->m->rows);
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, split ? 65535 : 65535 / (R * 4)));
   const size_t in_words = (size_t)2 * K * n, out_words = (size_t)3 * K * n;
   const size_t cc = std::min(chunk, groups * terms);
@@ -531,7 +550,8 @@ int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups
     const size_t polys = (size_t)3 * K;
     const int rc = plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) -> int {
       const size_t first = st.group0 * terms + st.term0;
-      if (int r = multiply(a + first * in_words, 2, b + first * in_words, 2, stage, st.groups * st.terms, s, false)) return r;
+      const SharedSel sub = sh ? sh->at(first) : SharedSel();
+      if (int r = multiply(a + first * in_words, 2, sh ? nullptr : b + first * in_words, 2, stage, st.groups * st.terms, s, false, sh ? &sub : nullptr)) return r;
       for (size_t g = 0; g < st.groups; g++) {
         u64* o = out3 + (st.group0 + g) * out_words;
         const u64* t0 = stage + g * st.terms * out_words;
@@ -561,11 +581,19 @@ int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups
   if (!sg.p) return kOutOfMemory;
   u64* ext = (u64*)sg.p;
   u64* D = ext + cc * ext_words;
-  const bool square = a == b;  // sums of squares: the head extends and the middle kernel transforms x once
+  const bool square = !sh && a == b;  // sums of squares: the head extends and the middle kernel transforms x once
+  SharedLease sl;  // prepared multiplicands: one index table for the whole call, a launch sequence reads it from its first item
+  if (sh)
+    if (int rc = stage_shared(*sh, groups * terms, true, s, sl)) return rc;
   const int rc = plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) -> int {
     const size_t first = st.group0 * terms + st.term0, c = st.groups * st.terms;
-    HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + first * in_words, b + first * in_words, ext, c, s, square ? 2u : 4u));
-    HB_LAUNCH(kKernMulMid, c, launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square));
+    if (sh) {
+      HB_LAUNCH(kKernMulHead, c * 2, launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + first * in_words, a + first * in_words, ext, c, s, 2u));
+      HB_LAUNCH(kKernMulMid, c, launch_mul_mid_shared(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, sh->m->rows, sl.idx + first, D, c, s));
+    } else {
+      HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + first * in_words, b + first * in_words, ext, c, s, square ? 2u : 4u));
+      HB_LAUNCH(kKernMulMid, c, launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square));
+    }
     HB_LAUNCH(kKernMulTailSum, c * 3, launch_mul_tail_sum(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out3 + st.group0 * out_words, st.groups, st.terms, st.accumulate, s, wt ? wt + st.term0 * K : nullptr));
     return kOk;
   });
@@ -583,7 +611,8 @@ int Evaluator::multiply_sum_weighted(const u64* a, const u64* b, const int32_t* 
 }
 
 // one key switch per group: the size-3 sums go through a pooled buffer, chunk_ops() groups at a time
-int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s, const int32_t* weights) {
+int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s, const int32_t* weights,
+                                  const SharedSel* sh) {
   const DevCtx& h = ctx_->host();
   if (h.KK < 2 || !rk.present()) return kNoKey;
   if (!terms) return kInvalidArg;
@@ -599,7 +628,8 @@ int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, 
   for (size_t g0 = 0; g0 < groups; g0 += block) {
     const size_t c = std::min(block, groups - g0);
     const size_t off = g0 * terms * 2 * K * n;  // (b == a stays b + off == a + off: the squaring form)
-    if (int rc = multiply_sum(a + off, b + off, sum3, c, terms, s, false, wl.wt)) return rc;
+    const SharedSel sub = sh ? sh->at(g0 * terms) : SharedSel();
+    if (int rc = multiply_sum(a + off, sh ? nullptr : b + off, sum3, c, terms, s, false, wl.wt, sh ? &sub : nullptr)) return rc;
     KeySel sel = rk;
     sel.first = rk.first + g0;
     if (int rc = relinearize(sum3, sel, out2 + g0 * 2 * K * n, c, s, nullptr, false)) return rc;
@@ -615,9 +645,10 @@ bool Evaluator::member_tail_ok(size_t count) const {
 }
 
 int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t count, hipStream_t s, const u64* addend, const MemberTail* members,
-                              u32 per, const MemberHead* heads, bool heads_square) {
+                              u32 per, const MemberHead* heads, bool heads_square, const SharedSel* sh) {
   const DevCtx& h = ctx_->host();
   if (h.KK < 2 || !rk.present()) return kNoKey;
+  if (sh && (members || heads)) return kInvalidArg;
   if (members && (!member_tail_ok(count) || !per || addend)) return kInvalidArg;
   if (heads && !members) return kInvalidArg;
   const u32 n = h.n, K = h.K, KK = h.KK, S = h.S, R = K + S;
@@ -630,8 +661,20 @@ int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64*
   // 3 x 54-bit set): mulrelin_head_mixed / mulrelin_tail_mixed, 8-byte rows, one or two middle launches per policy
   const bool fused_m = !fused_d && fuse_mulrelin_ && fuse_head_ && split_mul_ && split_ks_ && !h.aux_f64 && h.aux_mixed && h.ks_split_ok && kneed <= 4 &&
                        h.logn >= 12 && h.logn <= 14 && !lane_split((int)h.logn) && !few_for_fused(count);
-  const bool fused = fused_d || fused_m;
-  const bool square = fused && (heads ? heads_square : a == b);  // x * x: the head extends and the middle kernel transforms x once
+  const bool fused = (fused_d || fused_m) && (!sh || sh->m->rows);
+  // x * x: the head extends and the middle kernel transforms x once.  Prepared multiplicands (sh) take the same two-polynomial head on
+  // `a` (b = a below) and launch_mul_mid_shared in place of launch_mul_mid.
+  const bool square = fused && (sh || (heads ? heads_square : a == b));
+  if (sh) b = a;
+  SharedLease sl;
+  if (sh && fused)
+    if (int rc = stage_shared(*sh, count, true, s, sl)) return rc;
+  // the middle launch of a chunk of c items from item off
+  const auto mul_mid = [&](const u64* ext, u64* D, size_t off, size_t c) -> hipError_t {
+    if (sh)
+      return launch_mul_mid_shared(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, sh->m->rows, sl.idx + off, D, c, s);
+    return launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square);
+  };
   if (fused) {
     const size_t ext_words = (size_t)4 * R * n, d_words = (size_t)3 * R * n, t_words = (size_t)KK * K * n, acc_words = (size_t)2 * KK * n, c2_words = (size_t)K * n;
     const size_t per_op = ext_words + d_words + t_words + acc_words + c2_words;
@@ -652,14 +695,14 @@ int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64*
       const size_t c = std::min(chunk, count - off);
       if (fused_m) {
         HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, false, 1, kneed, a + off * c2, b + off * c2, ext, c, s, square ? 2u : 4u));
-        HB_LAUNCH(kKernMulMid, c, launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square));
+        HB_LAUNCH(kKernMulMid, c, mul_mid(ext, D, off, c));
         HB_LAUNCH(kKernKsHead, c, launch_mulrelin_head_mixed(ctx_->dev(), h.tw_inv, h.tw_fwd, h.logn, D, T, c, s));
         HB_LAUNCH(kKernKsMid, c, launch_ks_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, h, T, rk.key, ACC, c, s, kl.at(off)));
         HB_LAUNCH(kKernKsTail, c, launch_mulrelin_tail_mixed(ctx_->dev(), h.tw_inv, h.logn, D, ACC, addend ? addend + off * c2 : nullptr, out2 + off * c2, c, s));
         continue;
       }
       HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, true, (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0), kneed, a + off * c2, b + off * c2, ext, c, s, square ? 2u : 4u, heads, (u32)off, per));
-      HB_LAUNCH(kKernMulMid, c, launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square));
+      HB_LAUNCH(kKernMulMid, c, mul_mid(ext, D, off, c));
       if (fuse_head_) {
         HB_LAUNCH(kKernKsHead, c, launch_mulrelin_head(ctx_->dev(), h.tw_inv, h.tw_fwd, h.logn, (int)h.pack_mul, h.conv_grid != 0, (int)h.pack_ks, kneed, D, T, c, s));
       } else {
@@ -677,7 +720,8 @@ int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64*
   if (!sg.p) return kOutOfMemory;
   for (size_t off = 0; off < count; off += chunk) {
     const size_t c = std::min(chunk, count - off);
-    int rc = multiply(a + off * c2, 2, b + off * c2, 2, (u64*)sg.p, c, s, false);
+    const SharedSel shc = sh ? sh->at(off) : SharedSel();
+    int rc = multiply(a + off * c2, 2, b + off * c2, 2, (u64*)sg.p, c, s, false, sh ? &shc : nullptr);
     if (rc) return rc;
     KeySel sub = rk;  // the chunk's items are items first + off ... of the selection
     sub.first = rk.first + off;
@@ -685,6 +729,140 @@ int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64*
     if (rc) return rc;
   }
   return note_result(out2, 2, h.K, count, s);
+}
+
+// ------------------------------------------------------------------ prepared multiplicands
+
+Multiplicand::~Multiplicand() {
+  if (ready) {
+    (void)hipEventSynchronize(ready);  // the launches that fill the buffers
+    (void)hipEventDestroy(ready);
+  }
+  if (ct) (void)hipFree(ct);  // (hipFree waits for the device: launches that still read the buffers finish first)
+  if (rows) (void)hipFree(rows);
+}
+
+bool Evaluator::split_mul_params() const {
+  const DevCtx& h = ctx_->host();
+  const u32 kneed = std::max(h.K, h.S > 2 ? h.S - 2 : 0u);
+  return split_mul_ && (kneed <= 4 || (kneed <= 8 && h.aux_f64)) && h.logn >= 12 && h.logn <= 14;
+}
+
+int Evaluator::prepare_multiplicand(const u64* ct2, size_t count, hipStream_t s, Multiplicand** out) {
+  const DevCtx& h = ctx_->host();
+  if (!ct2 || !out || !count || count > 0xFFFFFFFFull) return kInvalidArg;
+  if (h.logn > 15) return kUnsupported;
+  const u32 n = h.n, K = h.K, S = h.S, R = K + S;
+  const u32 kneed = std::max(K, S > 2 ? S - 2 : 0u);
+  const size_t ct_words = (size_t)2 * K * n, row_words = (size_t)2 * R * n;
+  std::unique_ptr<Multiplicand> m(new Multiplicand());
+  m->ctx = ctx_;
+  m->count = count;
+  if (hipMalloc((void**)&m->ct, count * ct_words * sizeof(u64)) != hipSuccess) {
+    (void)hipGetLastError();
+    m->ct = nullptr;
+    return kOutOfMemory;
+  }
+  m->bytes = count * ct_words * sizeof(u64);
+  if (split_mul_params()) {
+    if (hipMalloc((void**)&m->rows, count * row_words * sizeof(u64)) != hipSuccess) {
+      (void)hipGetLastError();
+      m->rows = nullptr;
+      return kOutOfMemory;
+    }
+    m->bytes += count * row_words * sizeof(u64);
+  }
+  HB_CHECK(hipEventCreateWithFlags(&m->ready, hipEventDisableTiming));
+  HB_CHECK(hipMemcpyAsync(m->ct, ct2, count * ct_words * sizeof(u64), hipMemcpyDeviceToDevice, s));
+  if (m->rows) {
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, 65535)), cc = std::min(chunk, count);
+    const size_t ext_words = (size_t)4 * R * n;  // (the head's layout: polys 2, 3 of an item stay unwritten and unread)
+    ScratchGuard sg(pool_, cc * ext_words * sizeof(u64), s);
+    if (!sg.p) return kOutOfMemory;
+    u64* ext = (u64*)sg.p;
+    for (size_t off = 0; off < count; off += chunk) {
+      const size_t c = std::min(chunk, count - off);
+      const u64* src = m->ct + off * ct_words;
+      HB_LAUNCH(kKernMulHead, c * 2, launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, src, src, ext, c, s, 2u));
+      HB_LAUNCH(kKernMulPrep, c, launch_mul_prep_mid(ctx_->dev(), h.tw_fwd, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, m->rows + off * row_words, c, s));
+    }
+  }
+  HB_CHECK(hipEventRecord(m->ready, s));
+  *out = m.release();
+  return kOk;
+}
+
+int Evaluator::check_shared(const SharedSel& sel, size_t items, size_t* bad) const {
+  if (!sel.m || !sel.index || !sel.period || sel.m->ctx != ctx_) return kInvalidArg;
+  for (size_t i = 0; i < std::min(items, sel.period); i++)
+    if (sel.index[(sel.first + i) % sel.period] >= sel.m->count) {
+      if (bad) *bad = i;
+      return kInvalidArg;
+    }
+  return kOk;
+}
+
+Evaluator::SharedLease::~SharedLease() {
+  if (!ev) return;
+  if (host) ev->pinned_.release(host, s);
+  if (dev) ev->pool_.release(dev, s);
+}
+
+int Evaluator::stage_shared(const SharedSel& sel, size_t items, bool rows, hipStream_t s, SharedLease& lease) {
+  if (!sel.m || !sel.index || !sel.period || !items) return kInvalidArg;
+  const size_t bytes = items * (rows ? sizeof(u32) : sizeof(u64*));
+  lease.ev = this;
+  lease.s = s;
+  lease.host = pinned_.acquire(bytes);
+  lease.dev = pool_.acquire(std::max<size_t>(bytes, (size_t)1 << 20), s);  // (one size class for the small tables, as stage_keymap's)
+  if (!lease.host || !lease.dev) return kOutOfMemory;
+  const size_t ct_words = (size_t)2 * ctx_->host().K * ctx_->host().n;
+  for (size_t i = 0; i < items; i++) {
+    const u32 k = sel.index[(sel.first + i) % sel.period];
+    if (k >= sel.m->count) return kInvalidArg;
+    if (rows)
+      static_cast<u32*>(lease.host)[i] = k;
+    else
+      static_cast<const u64**>(lease.host)[i] = sel.m->ct + (size_t)k * ct_words;
+  }
+  HB_CHECK(hipMemcpyAsync(lease.dev, lease.host, bytes, hipMemcpyHostToDevice, s));
+  if (rows)
+    lease.idx = static_cast<const u32*>(lease.dev);
+  else
+    lease.ptrs = static_cast<const u64* const*>(lease.dev);
+  return kOk;
+}
+
+int Evaluator::multiply_shared(const u64* a, const SharedSel& sh, u64* out3, size_t count, hipStream_t s) {
+  if (int rc = check_shared(sh, count, nullptr)) return rc;
+  if (!count) return kOk;
+  HB_CHECK(hipStreamWaitEvent(s, sh.m->ready, 0));
+  return multiply(a, 2, nullptr, 2, out3, count, s, true, &sh);
+}
+
+int Evaluator::multiply_relin_shared(const u64* a, const SharedSel& sh, const KeySel& rk, u64* out2, size_t count, hipStream_t s) {
+  if (ctx_->host().KK < 2 || !rk.present()) return kNoKey;
+  if (int rc = check_shared(sh, count, nullptr)) return rc;
+  if (!count) return kOk;
+  HB_CHECK(hipStreamWaitEvent(s, sh.m->ready, 0));
+  return multiply_relin(a, nullptr, rk, out2, count, s, nullptr, nullptr, 0, nullptr, false, &sh);
+}
+
+int Evaluator::multiply_sum_shared(const u64* a, const SharedSel& sh, u64* out3, size_t groups, size_t terms, hipStream_t s) {
+  if (!terms) return kInvalidArg;
+  if (int rc = check_shared(sh, groups * terms, nullptr)) return rc;
+  if (!groups) return kOk;
+  HB_CHECK(hipStreamWaitEvent(s, sh.m->ready, 0));
+  return multiply_sum(a, nullptr, out3, groups, terms, s, true, nullptr, &sh);
+}
+
+int Evaluator::multiply_sum_relin_shared(const u64* a, const SharedSel& sh, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s) {
+  if (ctx_->host().KK < 2 || !rk.present()) return kNoKey;
+  if (!terms) return kInvalidArg;
+  if (int rc = check_shared(sh, groups * terms, nullptr)) return rc;
+  if (!groups) return kOk;
+  HB_CHECK(hipStreamWaitEvent(s, sh.m->ready, 0));
+  return multiply_sum_relin(a, nullptr, rk, out2, groups, terms, s, nullptr, &sh);
 }
 
 // g^{-1} mod 2n (Newton iteration, g odd)

@@ -65,6 +65,7 @@ enum KernelId : int {
   kKernKsTail,
   kKernMulHead,
   kKernMulMid,
+  kKernMulPrep,  // the forward half alone (prepared multiplicands); kinds are read by name, so it sits beside its twin
   kKernMulTail,
   kKernMulTailSum,
   kKernCount
@@ -132,6 +133,36 @@ struct KeySel {
   KeySel(const u64* one) : key(one) {}  // NOLINT: every single-key call site passes its pointer
   bool per_item() const { return keys != nullptr; }
   bool present() const { return per_item() ? nkeys != 0 : key != nullptr; }
+};
+
+// A prepared multiplicand (Evaluator::prepare_multiplicand): `count` ciphertexts kept for products that share their second operand.
+//  ct   = a copy of the canonical ciphertexts, u64[count][2][K][N] (the paths that run the whole-polynomial kernels gather from it);
+//  rows = both polynomials of every ciphertext extended to all R = K + S residues and forward-transformed, u64[count][2][R][N], as the
+//         middle kernel holds them in front of the tensor product (kernels.hpp launch_mul_prep_mid) -- nullptr where the parameter
+//         set has no split multiply.
+// ready is recorded behind the last launch that fills the buffers; every call that uses the object makes its stream wait on it.
+struct Multiplicand {
+  Context* ctx = nullptr;
+  u64* ct = nullptr;
+  u64* rows = nullptr;
+  size_t count = 0;
+  size_t bytes = 0;
+  hipEvent_t ready = nullptr;
+  ~Multiplicand();
+};
+
+// Which prepared ciphertext each item of a *_shared call multiplies by: item i by m->ct[index[(first + i) % period]] (index: a HOST
+// array, every entry below m->count -- the callers check).
+struct SharedSel {
+  const Multiplicand* m = nullptr;
+  const u32* index = nullptr;
+  size_t period = 0;
+  size_t first = 0;
+  SharedSel at(size_t off) const {
+    SharedSel r = *this;
+    r.first += off;
+    return r;
+  }
 };
 
 // The invariant-noise outputs of Evaluator::decrypt (device memory, one entry per item): budget = SEAL's invariant_noise_budget,
@@ -221,7 +252,10 @@ class Evaluator {
   Context* ctx() const { return ctx_; }
 
   // ---- SURVEY 8a rows a1-a5, batched ----
-  int multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, size_t count, hipStream_t s, bool watch = true);
+  // sh (here, in multiply_relin, multiply_sum and multiply_sum_relin): the second operands are prepared ciphertexts (SharedSel above), b is
+  // unused.  The path is the one the call takes without it; where that is the split kernels, the head extends `a` alone and
+  // launch_mul_mid_shared reads the prepared rows, elsewhere the chunk's multiplicands are gathered from sh->m->ct.  The same words.
+  int multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, size_t count, hipStream_t s, bool watch = true, const SharedSel* sh = nullptr);
   // addend (optional, the three key-switching operations): ciphertexts u64[count][2][K][N] added to the results inside the last kernel
   // rk / key: one key for the whole batch (a device pointer converts) or a per-item selection (KeySel above)
   int relinearize(const u64* ct3, const KeySel& rk, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr, bool watch = true);
@@ -231,7 +265,8 @@ class Evaluator {
   // heads (with members): the members' operands where they are (kernels.hpp MemberHead) -- a and b are unused then, `square` says whether every
   // member multiplies a ciphertext by itself
   int multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr,
-                     const MemberTail* members = nullptr, u32 per = 0, const MemberHead* heads = nullptr, bool heads_square = false);
+                     const MemberTail* members = nullptr, u32 per = 0, const MemberHead* heads = nullptr, bool heads_square = false,
+                     const SharedSel* sh = nullptr);
   bool member_tail_ok(size_t count) const;
   // Sums of products with lazy relinearization: a, b = u64[groups][terms][2][K][N] (b == a: sums of squares),
   // out3[g] = sum_t a[g][t] * b[g][t] as size-3 ciphertexts -- word for word the sum of multiply()'s results (the order of a modular
@@ -242,13 +277,26 @@ class Evaluator {
   // by every group -- out3[g] = sum_t w_t (.) a[g][t] * b[g][t], the weight applied to the finished canonical residues of a term
   // just before they are added (mul_tail_sum_weighted_kernel; scaled_accumulate_kernel on the folded path).  A slice that starts at
   // term0 reads the table from row term0.
-  int multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch = true, const MulOp* wt = nullptr);
+  int multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch = true, const MulOp* wt = nullptr,
+                   const SharedSel* sh = nullptr);
   // weights: a HOST array of `terms` entries, read before the call returns and staged once (stage_weights).  All weights 1: the call above.
   int multiply_sum_weighted(const u64* a, const u64* b, const int32_t* weights, u64* out3, size_t groups, size_t terms, hipStream_t s);
   // out2[g] = relinearize(sum_t a[g][t] * b[g][t]): one key switch per GROUP; rk selects per group.  weights (optional): as above,
   // staged once for the whole call, not once per block of groups
   int multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s,
-                         const int32_t* weights = nullptr);
+                         const int32_t* weights = nullptr, const SharedSel* sh = nullptr);
+  // Prepared multiplicands: ct2 = u64[count][2][K][N] is copied and, where the parameter set has a split multiply, extended and
+  // transformed once (mul_head on two polynomials, mul_prep_mid).  Asynchronous on s; *out is owned by the caller (delete).
+  int prepare_multiplicand(const u64* ct2, size_t count, hipStream_t s, Multiplicand** out);
+  // kInvalidArg unless sel names an object of this context and every index is below its count (*bad: the first item that is not);
+  // nothing is launched
+  int check_shared(const SharedSel& sel, size_t items, size_t* bad) const;
+  // the four products over prepared multiplicands (include/hipbfv.h, hipbfv_batch_multiply_shared ...): the stream waits for the
+  // object's event, then the counterpart's launch sequence runs with sh
+  int multiply_shared(const u64* a, const SharedSel& sh, u64* out3, size_t count, hipStream_t s);
+  int multiply_relin_shared(const u64* a, const SharedSel& sh, const KeySel& rk, u64* out2, size_t count, hipStream_t s);
+  int multiply_sum_shared(const u64* a, const SharedSel& sh, u64* out3, size_t groups, size_t terms, hipStream_t s);
+  int multiply_sum_relin_shared(const u64* a, const SharedSel& sh, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s);
   // out2 = (sigma_g(c0), 0) + switch_key(sigma_g(c1), key)
   int apply_galois(const u64* ct2, u32 galois_elt, const KeySel& key, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr);
   // every item by its OWN Galois element in one key-switch pass (mixed-step rotation batches): elts / keys are HOST arrays of `count`
@@ -352,6 +400,20 @@ class Evaluator {
     ~WeightLease();
   };
   int stage_weights(const int32_t* weights, size_t terms, hipStream_t s, WeightLease& lease);
+  // the device table of one call over prepared multiplicands, staged as stage_keymap's: rows -- u32[items], item i's index (the split
+  // path: launch_mul_mid_shared reads idx + first item of the launch); otherwise a pointer table, item i's canonical ciphertext
+  // (launch_gather_items)
+  struct SharedLease {
+    Evaluator* ev = nullptr;
+    hipStream_t s = nullptr;
+    void* dev = nullptr;
+    void* host = nullptr;
+    const u32* idx = nullptr;
+    const u64* const* ptrs = nullptr;
+    ~SharedLease();
+  };
+  int stage_shared(const SharedSel& sel, size_t items, bool rows, hipStream_t s, SharedLease& lease);
+  bool split_mul_params() const;  // the parameter set has a split multiply at all (multiply()'s conditions but the item count)
   PinnedPool pinned_;
   Context* ctx_;
   u32* status_dev_ = nullptr;

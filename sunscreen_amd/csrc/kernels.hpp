@@ -78,6 +78,14 @@ hipError_t launch_mul_head(const DevCtx* ctx, const MulOp* twf, u32 logn, bool a
                            hipStream_t s, u32 npolys = 4, const MemberHead* members = nullptr, u32 first = 0, u32 per = 0);
 hipError_t launch_mul_mid(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d, u32 nd,
                           const unsigned char* res_i, u32 ni, const u64* ext, u64* D, size_t ops, hipStream_t s, bool square = false);
+// Prepared multiplicands: rows = u64[ciphertexts][2][R][N], both polynomials of a ciphertext extended and forward-transformed, 8-byte
+// lazy values in the middle kernel's register order (kernels_split.hip MulSharedGeom).  launch_mul_prep_mid writes them from ext (polys
+// 0, 1 of launch_mul_head with npolys = 2); launch_mul_mid_shared is launch_mul_mid with item i's second operand read from
+// rows[bidx[i]] (bidx: a DEVICE table of `ops` indices, each below the number of prepared ciphertexts).
+hipError_t launch_mul_prep_mid(const DevCtx* ctx, const MulOp* twf, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d, u32 nd,
+                               const unsigned char* res_i, u32 ni, const u64* ext, u64* rows, size_t ops, hipStream_t s);
+hipError_t launch_mul_mid_shared(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d,
+                                 u32 nd, const unsigned char* res_i, u32 ni, const u64* ext, const u64* rows, const u32* bidx, u64* D, size_t ops, hipStream_t s);
 hipError_t launch_mul_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out,
                            size_t ops, hipStream_t s, u32 poly0 = 0, u32 npolys = 3);
 // the summing form (Evaluator::multiply_sum): D = [groups][terms][3][R][N]; out3[g] = the sum over group g's terms of what launch_mul_tail

@@ -2026,6 +2026,228 @@ __global__ __launch_bounds__((MulMidGeom<L, POLICY_D, SQUARE, PACK>::TPB), (MulM
     mul_mid_body_batched<ArithI, L, false, kBlkEPT, 0, SQUARE>(dm, twf, twi, ext_r, ps, D_r, ps, smem, tid, blk);
 }
 
+// ---- prepared multiplicands (Evaluator::prepare_multiplicand, the *_shared products): the second operand's two polynomials are
+// extended and forward-transformed ONCE (mul_head with npolys = 2, then mul_prep_mid_kernel) and kept as the 8-byte lazy values the
+// middle kernel holds in front of the tensor product -- doubles for FP64-policy residues, u64 for integer ones, never packed.  A
+// product then runs the two-polynomial head on `a` alone and mul_mid_shared_kernel, which transforms a0, a1 and reads b^0, b^1.
+// rows = [ciphertext][2][R][NBLK][EPT * TPB], a thread's element e at e * TPB + tid (its register order: coalesced both ways);
+// writer and reader share MulSharedGeom, so the order is the same in both for every geometry.
+// Siblings of mul_mid_kernel and not parameters of it: its instantiations keep their names and their instructions.
+template <int L, bool POLICY_D>
+struct MulSharedGeom {
+  static constexpr int EPT = POLICY_D ? mid_ept_d(L, true) : kBlkEPT;  // two forward transforms: the squaring body's geometry
+  static constexpr bool TWO_REGIONS = EPT > kBlkEPT;                   // 16 elements per thread: d0 leaves before d1, d2 are formed
+  static constexpr int REGIONS = TWO_REGIONS ? 2 : 3;                  // otherwise the three inverse transforms advance together
+  static constexpr int TPB = SplitShape<L, EPT>::TPB;
+  static constexpr int WAVES = !POLICY_D ? MID_WAVES_I : TWO_REGIONS ? 2 : MID_WAVES_D(L);
+};
+
+// mul_mid_kernel's workgroup order (slice-major per XCD at N = 16384, ops padded to 8 there); false: a padding workgroup
+template <int L, int EPT>
+__device__ __forceinline__ bool mul_mid_coords(u32 b, const unsigned char* __restrict__ residues, u32 nres, u32 ops, u32& blk, u32& r, u32& op) {
+  using Sh = SplitShape<L, EPT>;
+  if constexpr (MUL_MID_SLICE(L)) {
+    const u32 xcd = b & 7u, slot = b >> 3;
+    const u32 per = (ops + 7u) >> 3;
+    op = (slot % per) * 8u + xcd;
+    const u32 ib = slot / per;
+    blk = ib % Sh::NBLK;
+    r = residue_of(residues, ib / Sh::NBLK);
+    return op < ops;
+  } else {
+    blk = b % Sh::NBLK;
+    r = residue_of(residues, (b / Sh::NBLK) % nres);
+    op = b / (Sh::NBLK * nres);
+    return true;
+  }
+}
+
+template <class A, int L, bool PACK, int EPT>
+__device__ __forceinline__ void mul_shared_load_pair(typename A::V (&v)[2][EPT], const typename A::V* ext_r, size_t poly_stride, u32 tid, u32 blk) {
+  using Sh = SplitShape<L, EPT>;
+  constexpr int RF0 = split_fwd_radix(L, 0), LOWF0 = split_fwd_low(L, 0);
+  using First = BlkPass<A, L, LOWF0, RF0, EPT>;
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const typename A::V* src = ext_r + (size_t)i * poly_stride;
+#pragma unroll
+    for (int g = 0; g < First::G; g++)
+#pragma unroll
+      for (int k = 0; k < (1 << RF0); k++) {
+        if constexpr (PACK && std::is_same<A, ArithD>::value)
+          v[i][g * (1 << RF0) + k] = nat_load<true, NtSites<L>::mul_mid_ld>(src, Sh::N, First::elem(tid, blk, g, k));
+        else
+          v[i][g * (1 << RF0) + k] = nt_ld<NtSites<L>::mul_mid_ld>(src + First::elem(tid, blk, g, k));
+      }
+  }
+}
+
+// bh: this thread's first word of b^0's row block; b^1's is bh_stride words further
+template <class A, int L, bool PACK, int EPT>
+__device__ __forceinline__ void mul_mid_shared_body(const DevMod& dm, const typename A::Tw* twf, const typename A::Tw* twi,
+                                                    const typename A::V* ext_r, size_t poly_stride, const typename A::V* bh, size_t bh_stride,
+                                                    typename A::V* D_r, size_t dpoly_stride, typename A::V* smem, u32 tid, u32 blk) {
+  using Sh = SplitShape<L, EPT>;
+  using V = typename A::V;
+  const A ar(dm);
+  const bool store_reduce = (dm.split_inv_mask & kPlanStoreReduce) != 0;
+  constexpr int RI = split_inv_radix(L, Sh::NPI - 1), LOWI = split_inv_low(L, Sh::NPI - 1);
+  using Out = BlkPass<A, L, LOWI, RI, EPT>;
+  auto store_poly = [&](int i, V(&dv)[EPT], u32 t) {
+    V* dst = D_r + (size_t)i * dpoly_stride;
+    if constexpr (PACK && std::is_same<A, ArithD>::value) {
+      if (store_reduce) reduce_all<A, EPT>(ar, dv);
+    }
+#pragma unroll
+    for (int g = 0; g < Out::G; g++)
+#pragma unroll
+      for (int k = 0; k < (1 << RI); k++) {
+        if constexpr (PACK && std::is_same<A, ArithD>::value)
+          nat_store<true, NtSites<L>::mul_mid_st>(dst, Sh::N, Out::elem(t, blk, g, k), dv[g * (1 << RI) + k]);
+        else
+          nt_st<NtSites<L>::mul_mid_st>(dst + Out::elem(t, blk, g, k), dv[g * (1 << RI) + k]);
+      }
+  };
+  const V* bh_p = bh;
+  auto load_b = [&](int p, V(&dst)[EPT]) {
+#pragma unroll
+    for (int e = 0; e < EPT; e++) dst[e] = bh_p[(size_t)p * bh_stride + (size_t)e * Sh::TPB];
+  };
+  V v[2][EPT];
+  mul_shared_load_pair<A, L, PACK, EPT>(v, ext_r, poly_stride, tid, blk);
+  mid_forward_multi<A, L, 2, EPT, MID_TW_PIPE(L)>(ar, v, smem, tid, blk, twf, dm.split_fwd_mask);
+  // (an opaque re-base of the row pointer: the loads after it are not scheduled above it)
+  auto pin_b = [&]() {
+    u32 zero = 0;
+    asm volatile("" : "+s"(zero) : : "memory");
+    bh_p = bh + zero;
+  };
+  if constexpr (EPT > kBlkEPT) {
+    // the sequence of the squaring body's MODE 2 with the sums of the general body's MODE 3: d0 = a0 b^0 leaves before
+    // d1 = a0 b^1 + a1 b^0 and d2 = a1 b^1 are formed; every b^ row is loaded just before its use (b^0 twice: L2 has it)
+    pin_b();
+    {
+      V d0[1][EPT];
+      {
+        V x[EPT];
+        load_b(0, x);
+#pragma unroll
+        for (int e = 0; e < EPT; e++) d0[0][e] = ar.mul_var(v[0][e], x[e]);
+      }
+      __syncthreads();  // the pair's last forward pass may still be reading the exchange buffer
+      mid_inverse_multi<A, L, 1, EPT, MID_TW_PIPE(L)>(ar, d0, smem, tid, blk, opaque_uniform(twi), dm.split_inv_mask);
+      store_poly(0, d0[0], tid);
+    }
+    pin_b();  // b^0 is fetched again below instead of being held across d0's inverse transform
+    // the store offsets are worked out again for d1, d2: kept from d0's stores across the second round they are 15 registers
+    // too many in the packed instantiation (60 bytes of scratch per lane)
+    u32 tid_st = tid;
+    asm volatile("" : "+v"(tid_st));
+    V d12[2][EPT];
+    {
+      V x[EPT];
+      load_b(1, x);
+#pragma unroll
+      for (int e = 0; e < EPT; e++) {
+        d12[0][e] = ar.mul_var(v[0][e], x[e]);  // a0 b1
+        d12[1][e] = ar.mul_var(v[1][e], x[e]);  // a1 b1
+      }
+    }
+    {
+      V x[EPT];
+      load_b(0, x);
+#pragma unroll
+      for (int e = 0; e < EPT; e++) d12[0][e] = ar.mul_add(v[1][e], x[e], d12[0][e]);  // + a1 b0
+    }
+    __syncthreads();
+    mid_inverse_multi<A, L, 2, EPT, MID_TW_PIPE(L)>(ar, d12, smem, tid, blk, opaque_uniform(twi), dm.split_inv_mask);
+    store_poly(1, d12[0], tid_st);
+    store_poly(2, d12[1], tid_st);
+  } else {
+    V d[3][EPT];
+    {
+      V b0[EPT], b1[EPT];
+      load_b(0, b0);
+      load_b(1, b1);
+#pragma unroll
+      for (int e = 0; e < EPT; e++) {
+        d[0][e] = ar.mul_var(v[0][e], b0[e]);
+        d[1][e] = ar.mul_add(v[0][e], b1[e], ar.mul_var(v[1][e], b0[e]));
+        d[2][e] = ar.mul_var(v[1][e], b1[e]);
+      }
+    }
+    __syncthreads();  // the last forward pass may still be reading the exchange buffer
+    mid_inverse_multi<A, L, 3, EPT, MID_TW_PIPE(L)>(ar, d, smem, tid, blk, twi, dm.split_inv_mask);
+#pragma unroll
+    for (int i = 0; i < 3; i++) store_poly(i, d[i], tid);
+  }
+}
+
+// grid as mul_mid_kernel's; ext = [ops][4][R][N] with polys 0, 1 written (launch_mul_head, npolys = 2); bidx[op] < the number of
+// prepared ciphertexts (checked on the host before anything is launched), wave-uniform
+template <int L, bool POLICY_D, bool PACK>
+__global__ __launch_bounds__((MulSharedGeom<L, POLICY_D>::TPB), (MulSharedGeom<L, POLICY_D>::WAVES)) void mul_mid_shared_kernel(
+    const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twf_base, const MulOp* __restrict__ twi_base, const u64* __restrict__ ext,
+    const u64* __restrict__ rows, const u32* __restrict__ bidx, u64* __restrict__ D, const unsigned char* __restrict__ residues, u32 nres, u32 ops) {
+  using Geo = MulSharedGeom<L, POLICY_D>;
+  using Sh = SplitShape<L, Geo::EPT>;
+  __shared__ u64 smem[Geo::REGIONS * Sh::BLOCK];
+  const u32 tid = threadIdx.x;
+  const u32 K = ctx->K, S = ctx->S, KK = ctx->KK, R = K + S;
+  u32 blk, r, op;
+  if (!mul_mid_coords<L, Geo::EPT>(blockIdx.x, residues, nres, ops, blk, r, op)) return;
+  const u32 m = r < K ? r : KK + (r - K);
+  const DevMod& dm = ctx->mod[m];
+  const u64* ext_r = ext + ((size_t)op * 4 * R + r) * Sh::N;
+  u64* D_r = D + ((size_t)op * 3 * R + r) * Sh::N;
+  const size_t ps = (size_t)R * Sh::N;
+  const u64* bh = rows + ((size_t)bidx[op] * 2 * R + r) * Sh::N + (size_t)blk * Sh::BLOCK + tid;
+  const MulOp* twf = twf_base + (size_t)m * Sh::N;
+  const MulOp* twi = twi_base + (size_t)m * Sh::N;
+  if constexpr (POLICY_D)
+    mul_mid_shared_body<ArithD, L, PACK, Geo::EPT>(dm, reinterpret_cast<const double*>(twf), reinterpret_cast<const double*>(twi),
+                                                   reinterpret_cast<const double*>(ext_r), ps, reinterpret_cast<const double*>(bh), ps,
+                                                   reinterpret_cast<double*>(D_r), ps, reinterpret_cast<double*>(smem), tid, blk);
+  else
+    mul_mid_shared_body<ArithI, L, false, kBlkEPT>(dm, twf, twi, ext_r, ps, bh, ps, D_r, ps, smem, tid, blk);
+}
+
+// the forward half alone: ext polys 0, 1 of op -> rows[op] (ops = prepared ciphertexts of this launch)
+template <int L, bool POLICY_D, bool PACK>
+__global__ __launch_bounds__((MulSharedGeom<L, POLICY_D>::TPB), (MulSharedGeom<L, POLICY_D>::WAVES)) void mul_prep_mid_kernel(
+    const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twf_base, const u64* __restrict__ ext, u64* __restrict__ rows,
+    const unsigned char* __restrict__ residues, u32 nres, u32 ops) {
+  using Geo = MulSharedGeom<L, POLICY_D>;
+  using Sh = SplitShape<L, Geo::EPT>;
+  __shared__ u64 smem[2 * Sh::BLOCK];
+  const u32 tid = threadIdx.x;
+  const u32 K = ctx->K, S = ctx->S, KK = ctx->KK, R = K + S;
+  u32 blk, r, op;
+  if (!mul_mid_coords<L, Geo::EPT>(blockIdx.x, residues, nres, ops, blk, r, op)) return;
+  const u32 m = r < K ? r : KK + (r - K);
+  const DevMod& dm = ctx->mod[m];
+  const u64* ext_r = ext + ((size_t)op * 4 * R + r) * Sh::N;
+  const size_t ps = (size_t)R * Sh::N;
+  u64* out = rows + ((size_t)op * 2 * R + r) * Sh::N + (size_t)blk * Sh::BLOCK + tid;
+  const MulOp* twf = twf_base + (size_t)m * Sh::N;
+  auto run = [&](auto ar, const auto* twf_a, const auto* ext_a, auto* out_a, auto* smem_a, auto pack) {
+    using A = decltype(ar);
+    constexpr int EPT = Geo::EPT;
+    typename A::V v[2][EPT];
+    mul_shared_load_pair<A, L, decltype(pack)::value, EPT>(v, ext_a, ps, tid, blk);
+    mid_forward_multi<A, L, 2, EPT, MID_TW_PIPE(L)>(ar, v, smem_a, tid, blk, twf_a, dm.split_fwd_mask);
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int e = 0; e < EPT; e++) out_a[(size_t)i * ps + (size_t)e * Sh::TPB] = v[i][e];
+  };
+  if constexpr (POLICY_D)
+    run(ArithD(dm), reinterpret_cast<const double*>(twf), reinterpret_cast<const double*>(ext_r), reinterpret_cast<double*>(out),
+        reinterpret_cast<double*>(smem), std::integral_constant<bool, PACK>{});
+  else
+    run(ArithI(dm), twf, ext_r, out, smem, std::false_type{});
+}
+
 // the tail's inverse stages + BEHZ scaling on the 4 coefficients thread t owns (EdgeGeom): canonical residues out
 // src: the residue row (not offset by t)
 template <class A, int L>
@@ -3329,6 +3551,36 @@ static hipError_t mul_mid_t(const DevCtx* ctx, const MulOp* twf, const MulOp* tw
 hipError_t launch_mul_mid(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d, u32 nd,
                           const unsigned char* res_i, u32 ni, const u64* ext, u64* D, size_t ops, hipStream_t s, bool square) {
   SPLIT_DISPATCH(mul_mid_t, ctx, twf, twi, res_dp, ndp, res_d, nd, res_i, ni, ext, D, ops, square, s)
+}
+
+// twi == nullptr: the forward half alone (mul_prep_mid_kernel: ext -> rows, bidx and D unused)
+template <int L>
+static hipError_t mul_mid_shared_t(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d, u32 nd,
+                                   const unsigned char* res_i, u32 ni, const u64* ext, u64* rows, const u32* bidx, u64* D, size_t ops, hipStream_t s) {
+  using Sh = SplitShape<L>;
+  if (((reinterpret_cast<uintptr_t>(res_dp) | reinterpret_cast<uintptr_t>(res_d) | reinterpret_cast<uintptr_t>(res_i)) & 3u) != 0) return hipErrorInvalidValue;
+  const size_t ops_g = MUL_MID_SLICE(L) ? (ops + 7) / 8 * 8 : ops;
+  constexpr unsigned TD = MulSharedGeom<L, true>::TPB, TI = MulSharedGeom<L, false>::TPB;
+  if (!twi) {
+    if (ndp) mul_prep_mid_kernel<L, true, true><<<dim3((unsigned)(ops_g * ndp * Sh::NBLK)), TD, 0, s>>>(ctx, twf, ext, rows, res_dp, ndp, (u32)ops);
+    if (nd) mul_prep_mid_kernel<L, true, false><<<dim3((unsigned)(ops_g * nd * Sh::NBLK)), TD, 0, s>>>(ctx, twf, ext, rows, res_d, nd, (u32)ops);
+    if (ni) mul_prep_mid_kernel<L, false, false><<<dim3((unsigned)(ops_g * ni * Sh::NBLK)), TI, 0, s>>>(ctx, twf, ext, rows, res_i, ni, (u32)ops);
+    return hipGetLastError();
+  }
+  if (ndp) mul_mid_shared_kernel<L, true, true><<<dim3((unsigned)(ops_g * ndp * Sh::NBLK)), TD, 0, s>>>(ctx, twf, twi, ext, rows, bidx, D, res_dp, ndp, (u32)ops);
+  if (nd) mul_mid_shared_kernel<L, true, false><<<dim3((unsigned)(ops_g * nd * Sh::NBLK)), TD, 0, s>>>(ctx, twf, twi, ext, rows, bidx, D, res_d, nd, (u32)ops);
+  if (ni) mul_mid_shared_kernel<L, false, false><<<dim3((unsigned)(ops_g * ni * Sh::NBLK)), TI, 0, s>>>(ctx, twf, twi, ext, rows, bidx, D, res_i, ni, (u32)ops);
+  return hipGetLastError();
+}
+hipError_t launch_mul_mid_shared(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d,
+                                 u32 nd, const unsigned char* res_i, u32 ni, const u64* ext, const u64* rows, const u32* bidx, u64* D, size_t ops, hipStream_t s) {
+  if (!twi || !rows || !bidx) return hipErrorInvalidValue;
+  SPLIT_DISPATCH(mul_mid_shared_t, ctx, twf, twi, res_dp, ndp, res_d, nd, res_i, ni, ext, const_cast<u64*>(rows), bidx, D, ops, s)
+}
+hipError_t launch_mul_prep_mid(const DevCtx* ctx, const MulOp* twf, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d, u32 nd,
+                               const unsigned char* res_i, u32 ni, const u64* ext, u64* rows, size_t ops, hipStream_t s) {
+  if (!rows) return hipErrorInvalidValue;
+  SPLIT_DISPATCH(mul_mid_shared_t, ctx, twf, (const MulOp*)nullptr, res_dp, ndp, res_d, nd, res_i, ni, ext, rows, (const u32*)nullptr, (u64*)nullptr, ops, s)
 }
 
 template <int L>
