@@ -302,7 +302,8 @@ long hipbfv_wire_decode_plaintext(const uint8_t *in, uint64_t in_size, uint8_t *
  * [ptr, ptr + count * words_per_item) (a plaintext operand: its plaintext width, one item when shared).  So the calls whose
  * output is wider or narrower than their input (multiply 2 + 2 -> 3 polynomials, relinearize 3 -> 2, mod_switch K -> K-1) take
  * no in-place form, and an output shifted against its input by any amount is refused.  The transforms either side of the
- * evaluator (encode, decode, decrypt, encrypt, plain_to_ntt, ct_to_ntt, dot_plain_ntt) accept no overlap at all.  So do the
+ * evaluator (encode, decode, decrypt, encrypt, plain_to_ntt, ct_to_ntt, dot_plain_ntt,
+ * dot_plain_ntt_queries) accept no overlap at all.  So do the
  * noise measures (noise_budget, decrypt_checked): no output may overlap `ct`, and no output may overlap another output (byte
  * ranges: budget is int32_t[count], noise double[count]); any overlap is HIPBFV_E_INVALIDARG before anything is launched.
  * hipbfv_batch_ntt works in place by definition. */
@@ -540,6 +541,17 @@ long hipbfv_batch_plain_to_ntt(void *evaluator, const uint64_t *plain, uint64_t 
 long hipbfv_batch_ct_to_ntt(void *evaluator, const uint64_t *ct, uint64_t size, uint64_t *ctn, uint64_t count, void *stream);
 long hipbfv_batch_dot_plain_ntt(void *evaluator, const uint64_t *ctn, uint64_t cols, const uint64_t *pntt, uint64_t rows, uint64_t *out,
                                 void *stream);
+/* Many queries against ONE pass over the database: every database word is loaded once and multiplied against a tile of queries.
+ * out[q] is, word for word, hipbfv_batch_dot_plain_ntt(ctn + q * cols * 2 * K * N, cols, pntt, rows) -- the reference's sequence of
+ * multiply_plain and add for query q (every step is exact modular arithmetic: tile shape and summation order cannot show).  out
+ * is laid out as hipbfv_batch_multiply_sum_relin_keys takes a[groups = queries][terms = rows].
+ * ctn: u64[queries][cols][2][K][N] (ct_to_ntt), pntt: u64[rows][cols][K][N] (plain_to_ntt),
+ * out: u64[queries][rows][2][K][N], coefficient form.
+ * A NULL pointer is HIPBFV_E_POINTER; cols == 0, rows == 0, an argument beyond 2^32 - 1 or any overlap of the output range with
+ * the ctn or pntt range is HIPBFV_E_INVALIDARG; queries == 0 is HIPBFV_S_OK.  Nothing is launched or written in any of these
+ * cases.  Asynchronous on `stream`. */
+long hipbfv_batch_dot_plain_ntt_queries(void *evaluator, const uint64_t *ctn, uint64_t queries, uint64_t cols, const uint64_t *pntt,
+                                        uint64_t rows, uint64_t *out, void *stream);
 long hipbfv_set_chunk_ops(void *evaluator, uint64_t chunk_ops);
 
 /* Batch executor for compiled FHE program graphs (replaces sunscreen_runtime/src/run.rs:100-357).
@@ -736,6 +748,14 @@ long hipbfv_debug_rotate_items_keys_plan(uint64_t n, const int32_t *steps, const
  * earlier slice of the same group wrote.  *count = the number of sequences (E_INVALIDARG when it exceeds capacity). */
 long hipbfv_debug_multiply_sum_plan(uint64_t groups, uint64_t terms, uint64_t chunk, uint64_t *steps5, uint64_t capacity,
                                     uint64_t *count);
+/* Host only, no device access: the product launches of hipbfv_batch_dot_plain_ntt_queries, 6 words per step
+ * {first_query, queries, first_row, rows, QT, RT}: one launch multiplies those queries against those rows, QT queries and RT rows
+ * per thread; QT == 1 names today's single-query kernel.  One query is one such step; otherwise the queries go in order, as many per
+ * launch as keep ceil(rows / RT) * ceil(queries / QT) at most 2^31 - 1 (a whole number of tiles; all of them in practice), and a
+ * last launch left with one query is a QT == 1 step.  Every step covers all rows.  rows == 0 or K == 0 is HIPBFV_E_INVALIDARG;
+ * *count = the number of steps (E_INVALIDARG when it exceeds capacity, nothing written past it). */
+long hipbfv_debug_dot_queries_plan(uint64_t queries, uint64_t rows, uint64_t K, uint64_t *steps6, uint64_t capacity,
+                                   uint64_t *count);
 /* Host only, no device access: the weight table of the weighted sums for the moduli `primes` (each in [2, 2^62)).
  * out[(t * count + i) * 2] = weights[t] mod primes[i], canonical; out[... + 1] = floor(that * 2^64 / primes[i]). */
 long hipbfv_debug_weight_residues(const uint64_t *primes, uint64_t count, const int32_t *weights, uint64_t terms,

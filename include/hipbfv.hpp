@@ -721,6 +721,13 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
     for (const RelinearizationKeys* k : keys) hs.push_back(k ? k->get_handle() : nullptr);
     check(hipbfv_batch_multiply_sum_relin_keys(h_, a, b, hs.data(), hs.size(), key_index.data(), out2, key_index.size(), terms, stream));
   }
+  // Q queries against ONE pass over a transformed database: ctn u64[queries][cols][2][K][N] (hipbfv_batch_ct_to_ntt), pntt
+  // u64[rows][cols][K][N] (hipbfv_batch_plain_to_ntt), out u64[queries][rows][2][K][N] in coefficient form -- what
+  // multiply_sum_relin_keys takes as a[groups = queries][terms = rows].  out[q] has the bits of the single-query product.
+  void dot_plain_ntt_queries(const uint64_t* ctn, uint64_t queries, uint64_t cols, const uint64_t* pntt, uint64_t rows, uint64_t* out,
+                             void* stream = nullptr) const {
+    check(hipbfv_batch_dot_plain_ntt_queries(h_, ctn, queries, cols, pntt, rows, out, stream));
+  }
   // Weighted sums: out[g] = sum_t weights[t] * a[g][t] * b[g][t]; one weight per term (weights.size() == terms), shared by every group.
   // A weight multiplies its term's noise by |w|.
   void multiply_sum_weighted(const uint64_t* a, const uint64_t* b, const std::vector<int32_t>& weights, uint64_t* out3, uint64_t groups,

@@ -177,6 +177,19 @@ impl<'e> BatchEvaluator<'e> {
                                                           self.stream)
         })
     }
+    /// `queries` queries against ONE pass over a transformed database.  `ctn`: `queries * cols` transformed size-2 ciphertexts
+    /// (query-major), `pntt`: `rows * cols` transformed plaintexts as a batch of size 1 (row-major), `out`: `queries * rows` size-2
+    /// ciphertexts -- what `multiply_sum_relin_keys` takes as `a` with `terms = rows`.  `out[q]` has the bits of the single-query product.
+    pub fn dot_plain_ntt_queries(&self, ctn: DeviceBatch, queries: u64, pntt: DeviceBatch, rows: u64, out: DeviceBatch) -> Result<()> {
+        let cols = if rows == 0 { 0 } else { pntt.count / rows };
+        if ctn.size != 2 || out.size != 2 || pntt.size != 1 || cols == 0 || pntt.count != rows * cols || queries.checked_mul(cols) != Some(ctn.count)
+            || queries.checked_mul(rows) != Some(out.count)
+        {
+            return Err(crate::Error::InvalidArgument(format!("{} query words, {} database words, {} outputs for {} queries and {} rows", ctn.count,
+                                                             pntt.count, out.count, queries, rows)));
+        }
+        check(unsafe { bindgen::hipbfv_batch_dot_plain_ntt_queries(self.h(), ctn.ptr, queries, cols, pntt.ptr, rows, out.ptr, self.stream) })
+    }
     // ---- weighted sums: out[g] = sum_t weights[t] * a[g][t] * b[g][t]; one weight per term, shared by every group (a weight multiplies
     // its term's noise by |w|) ----
     pub fn multiply_sum_weighted(&self, a: DeviceBatch, b: DeviceBatch, weights: &[i32], out3: DeviceBatch) -> Result<()> {

@@ -140,6 +140,8 @@ _SIGNATURES = {
     "hipbfv_batch_plain_to_ntt": [vp, vp, u64, vp, u64, vp],
     "hipbfv_batch_ct_to_ntt": [vp, vp, u64, vp, u64, vp],
     "hipbfv_batch_dot_plain_ntt": [vp, vp, u64, vp, u64, vp, vp],
+    "hipbfv_batch_dot_plain_ntt_queries": [vp, vp, u64, u64, vp, u64, vp, vp],
+    "hipbfv_debug_dot_queries_plan": [u64, u64, u64, u64p, u64, u64p],
     "hipbfv_batch_decode": [vp, vp, vp, u64, C.c_int, vp],
     "hipbfv_batch_decrypt": [vp, vp, C.c_uint32, vp, vp, u64, vp],
     "hipbfv_batch_noise_budget": [vp, vp, C.c_uint32, vp, vp, vp, u64, vp],

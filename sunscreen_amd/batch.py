@@ -479,6 +479,18 @@ class BatchEvaluator:
         _check(_lib.load().hipbfv_batch_dot_plain_ntt(self._h, _ptr(ctn), cols, _ptr(pntt), rows, _ptr(out), _stream()))
         return out
 
+    def dot_plain_ntt_queries(self, ctn: torch.Tensor, pntt: torch.Tensor) -> torch.Tensor:
+        """Q queries against ONE pass over the database.  ctn: int64[Q, cols, 2, K, N] (ct_to_ntt of each query), pntt:
+        int64[rows, cols, K, N] (plain_to_ntt) -> int64[Q, rows, 2, K, N]; out[q] has the bits of dot_plain_ntt(ctn[q], pntt).  The
+        result is laid out as multiply_sum_relin_keys takes a[groups = Q, terms = rows]."""
+        assert ctn.dim() == 5 and pntt.dim() == 4, (ctn.shape, pntt.shape)
+        queries, cols, rows = ctn.shape[0], ctn.shape[1], pntt.shape[0]
+        assert tuple(ctn.shape[2:]) == (2, self.K, self.n) and tuple(pntt.shape[1:]) == (cols, self.K, self.n), (ctn.shape, pntt.shape)
+        assert ctn.is_contiguous() and pntt.is_contiguous()
+        out = torch.empty((queries, rows, 2, self.K, self.n), dtype=torch.int64, device=ctn.device)
+        _check(_lib.load().hipbfv_batch_dot_plain_ntt_queries(self._h, _ptr(ctn), queries, cols, _ptr(pntt), rows, _ptr(out), _stream()))
+        return out
+
     # ---- a6: NTT entry points (BASELINE config 2) ----
     def ntt(self, data: torch.Tensor, nprimes: int, inverse: bool = False) -> torch.Tensor:
         """In-place negacyclic NTT of int64[polys, N]; polynomial p uses key-level prime p % nprimes."""
@@ -568,6 +580,19 @@ def multiply_sum_plan(groups: int, terms: int, chunk: int) -> list[tuple[int, in
     buf = (C.c_uint64 * (5 * max(1, n.value)))()
     _check(L.hipbfv_debug_multiply_sum_plan(groups, terms, chunk, buf, n.value, C.byref(n)))
     return [(buf[5 * i], buf[5 * i + 1], buf[5 * i + 2], buf[5 * i + 3], bool(buf[5 * i + 4])) for i in range(n.value)]
+
+
+def dot_queries_plan(queries: int, rows: int, K: int) -> list[tuple[int, int, int, int, int, int]]:
+    """The library's product launches for dot_plain_ntt_queries (host only): per launch (first query, queries, first row, rows, QT,
+    RT) -- those queries against those rows, QT queries and RT rows per thread.  QT == 1 is the single-query kernel of dot_plain_ntt.
+    One query is one such launch; otherwise all queries go into one launch of the query-tiled kernel (split only where row blocks x
+    query tiles would exceed 2^31 - 1 workgroups)."""
+    L = _lib.load()
+    n = C.c_uint64()
+    L.hipbfv_debug_dot_queries_plan(queries, rows, K, None, 0, C.byref(n))  # (the count; the call below raises what this one refused)
+    buf = (C.c_uint64 * (6 * max(1, n.value)))()
+    _check(L.hipbfv_debug_dot_queries_plan(queries, rows, K, buf, n.value, C.byref(n)))
+    return [tuple(int(buf[6 * i + k]) for k in range(6)) for i in range(n.value)]
 
 
 def weight_residues(primes, weights) -> list[list[tuple[int, int]]]:

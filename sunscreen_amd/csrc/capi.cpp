@@ -3634,6 +3634,36 @@ long hipbfv_batch_dot_plain_ntt(void* evaluator, const uint64_t* ctn, uint64_t c
   return from_status(ev->dot_plain_ntt((const u64*)ctn, (u32)cols, (const u64*)pntt, (u32)rows, (u64*)out, (hipStream_t)stream));
 HIPBFV_END
 
+// Q queries against one database in one pass (Evaluator::dot_plain_ntt_queries); every refusal comes before the first launch
+long hipbfv_batch_dot_plain_ntt_queries(void* evaluator, const uint64_t* ctn, uint64_t queries, uint64_t cols, const uint64_t* pntt, uint64_t rows,
+                                        uint64_t* out, void* stream) HIPBFV_BEGIN
+  Evaluator* ev = eval_of(evaluator);
+  if (!ev || !ctn || !pntt || !out) return HIPBFV_E_POINTER;
+  if (queries > 0xFFFFFFFFull || cols > 0xFFFFFFFFull || rows > 0xFFFFFFFFull) return fail(HIPBFV_E_INVALIDARG, "matrix too large");
+  if (!cols || !rows) return fail(HIPBFV_E_INVALIDARG, "cols and rows must not be zero");
+  const Context& c = *as<EvalObj>(evaluator, kMagicEval)->ctx;
+  ALIAS_OR_RETURN(cts(out, c.ct_words(2) * rows, queries), {cts(ctn, c.ct_words(2) * cols, queries), cts(pntt, c.ct_words(1) * cols, rows)}, false);
+  if (!queries) return HIPBFV_S_OK;
+  return from_status(ev->dot_plain_ntt_queries((const u64*)ctn, (u32)queries, (u32)cols, (const u64*)pntt, (u32)rows, (u64*)out, (hipStream_t)stream));
+HIPBFV_END
+
+// the product launches of the call above (evaluator.hpp plan_dot_queries), host only
+long hipbfv_debug_dot_queries_plan(uint64_t queries, uint64_t rows, uint64_t K, uint64_t* steps6, uint64_t capacity, uint64_t* count) HIPBFV_BEGIN
+  if (!count || (!steps6 && capacity)) return HIPBFV_E_POINTER;
+  uint64_t nsteps = 0;
+  const int rc = plan_dot_queries(queries, rows, K, dot_queries_tile(), [&](const DotQueriesStep& st) {
+    if (nsteps < capacity) {
+      uint64_t* o = steps6 + nsteps * 6;
+      o[0] = st.query0, o[1] = st.queries, o[2] = st.row0, o[3] = st.rows, o[4] = st.QT, o[5] = st.RT;
+    }
+    nsteps++;
+    return 0;
+  });
+  if (rc) return fail(HIPBFV_E_INVALIDARG, "rows and K must not be zero, queries and rows at most 2^32 - 1");
+  *count = nsteps;
+  return nsteps <= capacity ? HIPBFV_S_OK : fail(HIPBFV_E_INVALIDARG, "the plan has more steps than `capacity`; *count says how many");
+HIPBFV_END
+
 // ------------------------------------------------------------------ modulus switching (evaluator_base.rs: mod_switch_to_next)
 long Evaluator_ModSwitchToNext1(void* h, void* encrypted, void* destination, void* pool) HIPBFV_BEGIN
   (void)pool;

@@ -210,6 +210,38 @@ int plan_multiply_sum(size_t groups, size_t terms, size_t chunk, Visit&& visit) 
   return 0;
 }
 
+// The product launches of Evaluator::dot_plain_ntt_queries (Q queries against one transformed database), decided on the host:
+// step = the queries [query0, query0 + queries) against the rows [row0, row0 + rows) in ONE launch of dot_plain_q_kernel<RT, QT>, or,
+// where QT == 1, of the single-query dot_plain2_kernel<RT>.
+//  - one query runs the single-query kernel (kDotPlainRT rows per thread);
+//  - otherwise the tile is `tile` (dot_queries_tile()) and the queries go in order, as many per launch as keep
+//    ceil(rows / RT) * ceil(queries / QT) workgroups on grid x (2^31 - 1): a whole number of tiles, all queries in practice;
+//  - a last launch left with a single query runs the single-query kernel.
+// Every launch covers all rows.  K is validated only: today's rule does not depend on the number of residues.
+struct DotQueriesTile {
+  u32 RT, QT;
+};
+constexpr u32 kDotPlainRT = 4;  // launch_dot_plain's rows per thread
+constexpr DotQueriesTile kDotQueriesTiles[] = {{2, 2}, {1, 4}, {1, 2}};  // the instantiations; the first is the default
+// the tile in use: kDotQueriesTiles[0], or the one HIPBFV_DOT_QUERIES_TILE="<RT>x<QT>" names (tools/dot_plain_queries_timing.py)
+DotQueriesTile dot_queries_tile();
+struct DotQueriesStep {
+  u64 query0, queries, row0, rows;
+  u32 QT, RT;
+};
+template <class Visit>
+int plan_dot_queries(u64 queries, u64 rows, u64 K, DotQueriesTile tile, Visit&& visit) {
+  if (!rows || !K || queries > 0xFFFFFFFFull || rows > 0xFFFFFFFFull) return kInvalidArg;
+  if (queries == 1) return visit(DotQueriesStep{0, 1, 0, rows, 1, kDotPlainRT});
+  const u64 rowblocks = (rows + tile.RT - 1) / tile.RT;
+  const u64 per = std::max<u64>(1, 0x7FFFFFFFull / rowblocks) * tile.QT;
+  for (u64 q = 0; q < queries; q += per) {
+    const u64 c = std::min(per, queries - q);
+    if (int rc = visit(c == 1 ? DotQueriesStep{q, 1, 0, rows, 1, kDotPlainRT} : DotQueriesStep{q, c, 0, rows, tile.QT, tile.RT})) return rc;
+  }
+  return 0;
+}
+
 // The weight table of the weighted sums (Evaluator::multiply_sum with weights; hipbfv_debug_weight_residues prints it): out[t * count + i]
 // = {w_t mod primes[i], canonical in [0, q), and its Shoup quotient floor(r * 2^64 / q)}.  Any int32_t is a weight.
 inline void weight_residues(const u64* primes, size_t count, const int32_t* weights, size_t terms, MulOp* out) {
@@ -348,6 +380,9 @@ class Evaluator {
   int plain_to_ntt(const u64* plain, size_t pstride, u64* pntt, size_t count, hipStream_t s, int watch_zero = 0);
   int ct_to_ntt(const u64* ct, u32 size, u64* ctn, size_t count, hipStream_t s);
   int dot_plain_ntt(const u64* ctn, u32 cols, const u64* pntt, u32 rows, u64* out, hipStream_t s);
+  // `queries` queries against ONE database pass: ctn u64[queries][cols][2][K][N], out u64[queries][rows][2][K][N], out[q] word for
+  // word dot_plain_ntt(ctn + q * cols * 2 * K * N).  The product launches are plan_dot_queries' (one, in practice).
+  int dot_plain_ntt_queries(const u64* ctn, u32 queries, u32 cols, const u64* pntt, u32 rows, u64* out, hipStream_t s);
   // the graph executor's form: ctn u64[cols][batch][2][K][N] (transform domain), tab [rows][cols] device descriptors of
   // transform-domain plaintexts, out u64[rows][batch][2][K][N] in coefficient form
   int dot_plain_tab(const u64* ctn, u32 cols, const PlainNttRef* tab, u32 rows, u32 batch, u64* out, hipStream_t s);

@@ -227,6 +227,46 @@ int Evaluator::dot_plain_ntt(const u64* ctn, u32 cols, const u64* pntt, u32 rows
   return kOk;
 }
 
+DotQueriesTile dot_queries_tile() {
+  if (const char* env = std::getenv("HIPBFV_DOT_QUERIES_TILE")) {
+    char* end = nullptr;
+    const unsigned long rt = std::strtoul(env, &end, 10);
+    const unsigned long qt = end && *end == 'x' ? std::strtoul(end + 1, nullptr, 10) : 0;
+    for (const DotQueriesTile& t : kDotQueriesTiles)
+      if (t.RT == rt && t.QT == qt) return t;
+  }
+  return kDotQueriesTiles[0];
+}
+
+// Many queries, one pass over the database (dot_plain_q_kernel: each database word multiplied in registers against a tile of
+// queries).  out[q] is dot_plain_ntt's result for query q, bit for bit: the same exact modular sums in another order.
+int Evaluator::dot_plain_ntt_queries(const u64* ctn, u32 queries, u32 cols, const u64* pntt, u32 rows, u64* out, hipStream_t s) {
+  const DevCtx& h = ctx_->host();
+  if (h.logn > 15) return kUnsupported;
+  if (!cols || !rows) return kInvalidArg;
+  if (!queries) return kOk;
+  const u32 n = h.n, K = h.K;
+  const size_t ctw = (size_t)2 * K * n;
+  if (int rc = plan_dot_queries(queries, rows, K, dot_queries_tile(), [&](const DotQueriesStep& st) -> int {
+        const u64* c = ctn + (size_t)st.query0 * cols * ctw;
+        u64* o = out + (size_t)st.query0 * rows * ctw;
+        if (st.QT == 1)
+          HB_LAUNCH_CLIENT(kKernPlain, (size_t)rows * cols, launch_dot_plain(ctx_->dev(), n, K, c, cols, pntt, rows, o, s));
+        else
+          HB_LAUNCH_CLIENT(kKernPlain, (size_t)st.queries * rows * cols,
+                           launch_dot_plain_queries(ctx_->dev(), n, K, c, (u32)st.queries, cols, pntt, rows, o, st.RT, st.QT, s));
+        return kOk;
+      }))
+    return rc;
+  const NttPlan plan = range_plan(K);
+  const size_t polys = (size_t)queries * rows * 2 * K, step = (65535 / K) * K;
+  for (size_t off = 0; off < polys; off += step) {
+    const size_t c = std::min(step, polys - off);
+    HB_LAUNCH_CLIENT(kKernNttInv, c, launch_ntt(ctx_->dev(), h.tw_inv, h.logn, out + off * n, c, plan, true, 0, s));
+  }
+  return kOk;
+}
+
 // The graph executor's matrix-vector product (program_plan.cpp): as dot_plain_ntt with the plaintexts behind a descriptor table
 // and a batch dimension.
 int Evaluator::dot_plain_tab(const u64* ctn, u32 cols, const PlainNttRef* tab, u32 rows, u32 batch, u64* out, hipStream_t s) {

@@ -169,6 +169,9 @@ hipError_t launch_keygen_assemble(const DevCtx* ctx, u32 n, u32 KK, const u64* a
 hipError_t launch_keygen_square(const DevCtx* ctx, u32 n, u32 KK, const u64* in, u64* out, hipStream_t s);
 hipError_t launch_keygen_galois(const DevCtx* ctx, u32 n, u32 KK, const u64* in, u64* out, u32 ginv, hipStream_t s);
 hipError_t launch_dot_plain(const DevCtx* ctx, u32 n, u32 K, const u64* ctn, u32 cols, const u64* pntt, u32 rows, u64* acc, hipStream_t s);
+// many queries against one database (dot_plain_q_kernel<RT, QT>): ctn u64[queries][cols][2][K][N], acc u64[queries][rows][2][K][N]
+hipError_t launch_dot_plain_queries(const DevCtx* ctx, u32 n, u32 K, const u64* ctn, u32 queries, u32 cols, const u64* pntt, u32 rows, u64* acc, u32 RT,
+                                    u32 QT, hipStream_t s);
 hipError_t launch_crt_compose(const DevCtx* ctx, u32 n, u32 KC, const u64* consts, const u64* in, u64* out, u32 polys, hipStream_t s);
 hipError_t launch_crt_decompose(const DevCtx* ctx, u32 n, u32 KC, const u64* in, u64* out, u32 polys, hipStream_t s);
 hipError_t launch_add_key_level(const DevCtx* ctx, u32 n, u64* c, const u64* e, size_t residue_polys, hipStream_t s);

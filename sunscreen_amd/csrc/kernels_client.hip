@@ -788,7 +788,159 @@ __global__ __launch_bounds__(kClientThreads) void dot_plain_tab_kernel(const Dev
   }
 }
 
+// MANY queries against one database (Evaluator::dot_plain_ntt_queries): a database word is loaded once and multiplied, in registers,
+// against a tile of QT queries.  ctn u64[queries][cols][2][K][N]; pntt u64[rows][cols][K][N]; acc u64[queries][rows][2][K][N].
+//   acc[q][row][p][i][x] = sum_j ctn[q][j][p][i][x] * pntt[row][j][i][x] mod q_i
+// One thread = two adjacent coefficients of one residue, RT rows, QT queries, both polynomials: RT x QT x 2 x 2 lazy accumulators
+// (PirLazy above).  A column is one block of RT database words (non-temporal) and 2 QT query words, 16 bytes per lane each.  Two NAMED blocks
+// alternate -- B is requested, A is multiplied, A is requested again, B is multiplied -- so the look-ahead costs no register copies
+// (pir_dot_body's `cur = nxt` is about 5 of its 16 vector instructions per multiply-accumulate).  Rows beyond the matrix, queries
+// beyond `queries` and the column after the last are clamped to the last one: read twice, never stored or accumulated, no branch in
+// the loop body.  The dispatch index of PirGrid's "row block" walks the query tiles fastest, then the row blocks: the workgroups of
+// one (coefficient range, residue) slice stay on one XCD, the tiles of a row block next to each other.
+// The lazy accumulator of that kernel: the 128-bit sum L + M * 2^32 + H * 2^64 kept as three 64-bit columns, so that a
+// multiply-accumulate is four v_mad_u64_u32 and ONE carry instead of the compiler's 128-bit product and 128-bit add (about 15
+// vector instructions and 3 s_nop; counted in DESIGN 5.8).  With both factors below 2^61 (canonical residues; the bound behind
+// "sixteen products fit"), a = a1 * 2^32 + a0 has a1 < 2^29, so
+//   a0 * b0 < 2^64            goes to L; L's carry is worth 2^64 = bit 32 of M;
+//   a1 * b0, a0 * b1 < 2^61   go to M: four of them (two products) and two carries keep M below 2^64 once its upper half has been
+//                             moved to H, which fold() does after every two products;
+//   a1 * b1 < 2^58            goes to H: sixteen of them and the folded halves stay far below 2^64.
+// No column overflows, so value() is the exact sum: the words cannot differ from the 128-bit form's.
+struct PirLazy {
+  u64 L, M, H;
+  // (the empty asm statements hold no instruction: they keep the compiler from re-associating the four sums, which otherwise
+  // turns every v_mad_u64_u32 into a multiply by itself and a 64-bit add)
+  __device__ __forceinline__ void mac(u64 a, u64 b) {
+    const u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
+    u64 l = (u64)a0 * b0 + L;
+    asm("" : "+v"(l));
+    u64 m = ((u64)((u32)(M >> 32) + (u32)(l < L)) << 32) | (u32)M;  // L's carry: 2^64
+    L = l;
+    m = (u64)a1 * b0 + m;
+    asm("" : "+v"(m));
+    m = (u64)a0 * b1 + m;
+    asm("" : "+v"(m));
+    M = m;
+    u64 h = (u64)a1 * b1 + H;
+    asm("" : "+v"(h));
+    H = h;
+  }
+  __device__ __forceinline__ void fold() {
+    H += M >> 32;
+    M &= 0xFFFFFFFFull;
+  }
+  __device__ __forceinline__ u128 value() const { return (u128)L + ((u128)M << 32) + ((u128)H << 64); }
+};
+template <int RT, int QT>
+struct PirQBlock {
+  pir_u64x2 c[QT][2], pv[RT];
+};
+template <int RT, int QT>
+__global__ __launch_bounds__(kClientThreads) void dot_plain_q_kernel(const DevCtx* __restrict__ ctx, const u64* __restrict__ ctn, u32 queries, u32 cols,
+                                                                     const u64* __restrict__ pntt, u32 rows, u64* __restrict__ acc) {
+  const u32 n = ctx->n, K = ctx->K;
+  const PirGrid pg;
+  const u32 x = 2 * (pg.xblock() * kClientThreads + threadIdx.x);
+  const u32 i = pg.residue(), QB = (queries + QT - 1) / QT;
+  const u32 q0 = (pg.rowblock() % QB) * QT, r0 = (pg.rowblock() / QB) * RT;
+  if (x >= n) return;
+  const DevMod& dm = ctx->mod[i];
+  const size_t in_row = (size_t)i * n + x, pw = (size_t)K * n;  // pw: words of one polynomial, the column stride of the database
+  const u64* qp[QT];  // column 0 of query q0 + t (clamped) and of row r0 + r (clamped)
+  const u64* rp[RT];
+#pragma unroll
+  for (int t = 0; t < QT; t++) qp[t] = ctn + (size_t)(q0 + t < queries ? q0 + t : queries - 1) * cols * 2 * pw + in_row;
+#pragma unroll
+  for (int r = 0; r < RT; r++) rp[r] = pntt + (size_t)(r0 + r < rows ? r0 + r : rows - 1) * cols * pw + in_row;
+  auto fetch = [&](PirQBlock<RT, QT>& blk, u32 j) {
+#pragma unroll
+    for (int t = 0; t < QT; t++) {
+      const u64* cj = qp[t] + (size_t)j * 2 * pw;
+      blk.c[t][0] = *as_global(reinterpret_cast<const pir_u64x2*>(cj));
+      blk.c[t][1] = *as_global(reinterpret_cast<const pir_u64x2*>(cj + pw));
+    }
+#pragma unroll
+    for (int r = 0; r < RT; r++) blk.pv[r] = __builtin_nontemporal_load(as_global(reinterpret_cast<const pir_u64x2*>(rp[r] + (size_t)j * pw)));
+  };
+  PirLazy a[QT][RT][2][2];  // [query][row][polynomial][coefficient]
+#pragma unroll
+  for (int t = 0; t < QT; t++)
+#pragma unroll
+    for (int r = 0; r < RT; r++)
+#pragma unroll
+      for (int e = 0; e < 4; e++) a[t][r][e >> 1][e & 1] = PirLazy{0, 0, 0};
+  auto mac = [&](const PirQBlock<RT, QT>& blk) {
+#pragma unroll
+    for (int r = 0; r < RT; r++)
+#pragma unroll
+      for (int t = 0; t < QT; t++)
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+          a[t][r][p][0].mac(blk.c[t][p].x, blk.pv[r].x);
+          a[t][r][p][1].mac(blk.c[t][p].y, blk.pv[r].y);
+        }
+  };
+  auto each = [&](auto&& f) {
+#pragma unroll
+    for (int t = 0; t < QT; t++)
+#pragma unroll
+      for (int r = 0; r < RT; r++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) f(a[t][r][e >> 1][e & 1]);
+  };
+  PirQBlock<RT, QT> A, B;
+  fetch(A, 0);
+  u32 j = 0, since = 0;  // products accumulated since the last reduction: below 2^122 each, sixteen fit 128 bits
+  for (; j + 2 <= cols; j += 2) {
+    fetch(B, j + 1);
+    mac(A);
+    fetch(A, j + 2 < cols ? j + 2 : cols - 1);  // in flight while B is multiplied; after the last pair a re-read nobody uses
+    mac(B);
+    each([](PirLazy& s) { s.fold(); });
+    since += 2;
+    if (since == 16u) {
+      since = 0;
+      each([&](PirLazy& s) { s = PirLazy{reduce128_fast(s.value(), dm), 0, 0}; });
+    }
+  }
+  if (j < cols) mac(A);  // an odd number of columns: the last one is in A (at most the fifteenth product since a reduction)
+#pragma unroll
+  for (int t = 0; t < QT; t++) {
+    if (q0 + t < queries) {
+#pragma unroll
+      for (int r = 0; r < RT; r++) {
+        if (r0 + r < rows) {
+          u64* dst = acc + ((size_t)(q0 + t) * rows + (r0 + r)) * 2 * pw + in_row;
+#pragma unroll
+          for (int p = 0; p < 2; p++) {
+            pir_u64x2 o;
+            o.x = reduce128_fast(a[t][r][p][0].value(), dm), o.y = reduce128_fast(a[t][r][p][1].value(), dm);
+            *reinterpret_cast<pir_u64x2*>(dst + p * pw) = o;
+          }
+        }
+      }
+    }
+  }
+}
+
 // ---- launchers ----
+// (RT, QT) must be one of the instantiated tiles (evaluator.hpp kDotQueriesTiles); row blocks x query tiles ride on grid x
+hipError_t launch_dot_plain_queries(const DevCtx* ctx, u32 n, u32 K, const u64* ctn, u32 queries, u32 cols, const u64* pntt, u32 rows, u64* acc, u32 RT,
+                                    u32 QT, hipStream_t s) {
+  if (!RT || !QT) return hipErrorInvalidValue;
+  const u64 blocks = (u64)((rows + RT - 1) / RT) * ((queries + QT - 1) / QT);
+  if (!blocks || blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  const dim3 grid = PirGrid::grid((n / 2 + kClientThreads - 1) / kClientThreads, K, (u32)blocks);
+#define HB_DOTQ(RT_, QT_)                                                                                            \
+  if (RT == RT_ && QT == QT_) {                                                                                      \
+    dot_plain_q_kernel<RT_, QT_><<<grid, kClientThreads, 0, s>>>(ctx, ctn, queries, cols, pntt, rows, acc);          \
+    return hipGetLastError();                                                                                        \
+  }
+  HB_DOTQ(2, 2) HB_DOTQ(1, 4) HB_DOTQ(1, 2)
+#undef HB_DOTQ
+  return hipErrorInvalidValue;
+}
 hipError_t launch_dot_plain_tab(const DevCtx* ctx, u32 n, u32 K, const u64* ctn, u32 cols, const PlainNttRef* tab, u32 rows, u32 batch, u64* acc, hipStream_t s) {
   constexpr int RT = 4;
   // grid z <= 65535: row blocks go in slices

@@ -104,6 +104,23 @@ def pir_lookup(ev, col_query, row_query, db_ntt, relin_keys):
     return prod
 
 
+def pir_lookup_queries(ev, col_queries, row_queries, db_ntt, relin_key_sets, key_index):
+    """`lookup` of examples/pir for Q clients against ONE database in three calls: ct_to_ntt of every column query,
+    dot_plain_ntt_queries (the transformed database streams through once for all clients), multiply_sum_relin_keys with
+    groups = Q and terms = rows (client c's sum is relinearised with relin_key_sets[key_index[c]]).
+
+    col_queries: int64[Q, cols, 2, K, N], row_queries: int64[Q, rows, 2, K, N] (device), db_ntt: int64[rows, cols, K, N] from
+    BatchEvaluator.plain_to_ntt, key_index: Q host integers.  Returns int64[Q, 2, K, N].
+
+    The row side is the LAZILY relinearised sum: one key switch per client, with the bits of
+    relinearize(sum_i multiply(col_i, row_query_i)).  It is not the reference's order, which relinearises after every row's multiply
+    (pir_lookup, pir_lookup_graph); both decrypt to the same entry."""
+    q, cols = col_queries.shape[0], col_queries.shape[1]
+    ctn = ev.ct_to_ntt(col_queries.reshape((q * cols,) + tuple(col_queries.shape[2:]))).reshape(col_queries.shape)
+    col = ev.dot_plain_ntt_queries(ctn, db_ntt)
+    return ev.multiply_sum_relin_keys(col, row_queries, relin_key_sets, key_index)
+
+
 def pir_lookup_sharded(ev, col_query, row_query_local, db_ntt_local, relin_keys, root: int = 0):
     """examples/pir with the database sharded by ROW over the ranks (SURVEY 8d config 5a, 8e "Exception"): this rank holds
     rows [lo, hi) of the transform-domain database and the matching slice of the row query; `pir_lookup` over them leaves one
