@@ -19,7 +19,9 @@ polynomial 0 (2) of the product is a function of a0[k] (a1[k]) alone: candidates
 harvested from the oracle (land_multiply_output; floor(t D / q) - u' with u' in [0, K) the fast conversion's overflow, so +1 is found
 among D near j q / t, and a SMALL D never gives 0 or +1: its u' is at least 1).  The gamma residue of decrypt's rounding is a linear
 form of (y_0, y_1) mod gamma: the nearest point of a two-dimensional lattice coset puts it on any target (land_gamma).
-tests/test_gpu_landing_multiply.py runs these.
+tests/test_gpu_landing_multiply.py runs these.  Section I hands the same operands to the prepared-multiplicand products (in both
+roles: the oracle's multiply is symmetric) and to the weighted sums, with weight vectors chosen so that the sums of weighted residues
+pass through exactly q_i and q_i - 1 and end on 0, q_i - 1 and 1 (weighted_sum_case); tests/test_gpu_landing_shared.py runs those.
 
 What the method cannot reach: polynomial 1 of a stand-alone key switch or rotation (it is ks1 alone), polynomial 1 of a product by
 (1, 1) (a0 + a1 is not free once a0 and a1 are spent; it is compared all the same), and alpha_sk's own branch in the
@@ -168,6 +170,7 @@ SETS = {
     "U1024": _create(1024, [50, 30, 30, 50, 50]),
     "W2048": _create(2048, [60, 60, 60, 60]),                                  # 60-bit primes, K = 3
     "W4096": _create(4096, [60, 60, 60]),                                      # 60-bit primes, K = 2
+    "S4096": _create(4096, [30, 30, 40, 40]),                                  # 30-bit primes at n = 4096: an int32 weight wraps them
 }
 
 
@@ -919,3 +922,105 @@ def gamma_case(L: "Landing", items: int = 2, size: int = 2):
         return np.stack(cts), phases, tg
 
     return L.cached(("gamma", items, size), make)
+
+
+# ------------------------------------------------------------- I: prepared multiplicands and weighted sums on landed operands
+def with_decoy(L: "Landing", ops, salt: int = 0):
+    """(prepared uint64[len(ops) + 1][2][K][n], index): the ciphertexts to prepare with one fresh encryption that no item uses at
+    place 1 and the operands in REVERSED order around it, and the index that names operand i.  Never the identity, never a constant
+    step: a wrong index, a wrong row stride or a dropped index gives other words."""
+    m = len(ops)
+    places = [p for p in range(m + 1) if p != 1][::-1]
+    prepared = np.empty((m + 1,) + ops[0].shape, dtype=np.uint64)
+    prepared[1] = L.cached(("decoy", salt), lambda: L.fresh(L.rng(95 + salt), 1)[0])
+    for i, p in enumerate(places):
+        prepared[p] = ops[i]
+    return prepared, places
+
+
+def floor_operands(L: "Landing") -> np.ndarray:
+    """uint64[4][2][K][n]: the two operands of floor_case and the two of output_case (what is multiplied by (1, 1))."""
+    return np.ascontiguousarray(np.concatenate([floor_case(L)[0], output_case(L)[0]]))
+
+
+NINE_INDEX = [6, 2, 9, 4, 1, 3, 8, 5, 7]
+
+
+def nine_case(L: "Landing"):
+    """(a uint64[9][2][K][n], prepared uint64[10][2][K][n], index, refs): nine items over nine prepared ciphertexts and a decoy at
+    place 0.  Places 1 ... 4 hold the four multiplicands of mtilde_case (item: its first operand), place 5 holds (1, 1) (item: the
+    floor operand with every row at q - 1), places 6 ... 9 the four floor operands (item: (1, 1)).  refs[i] = ("head" | "floor", k):
+    item i's product is product k of that family (BFV's tensor is symmetric).  At n = 16384 nine operations make the slice-major
+    workgroup order run with per = 2."""
+    ma, mb = mtilde_case(L)
+    fo = floor_operands(L)
+    ones = ones_ct(L, 1)[0]
+    prepared = np.stack([L.cached(("decoy", 9), lambda: L.fresh(L.rng(104), 1)[0])] + list(mb) + [ones] + list(fo))
+    role = {p: (ma[p - 1], ("head", p - 1)) for p in range(1, 5)}
+    role[5] = (fo[1], ("floor", 1))
+    role.update({p: (ones, ("floor", p - 6)) for p in range(6, 10)})
+    a = np.stack([role[p][0] for p in NINE_INDEX])
+    return a, prepared, list(NINE_INDEX), [role[p][1] for p in NINE_INDEX]
+
+
+def output_sum_products(L: "Landing", groups: int = 2, terms: int = 3) -> np.ndarray:
+    """uint64[groups][terms][3][K][n]: the oracle's product of every term of output_sum_case with (1, 1), once per process."""
+
+    def make():
+        a = output_sum_case(L, groups, terms)[0]
+        ones = ones_ct(L, 1)[0]
+        return np.stack([np.stack([L.o.multiply(a[g, j], ones) for j in range(terms)]) for g in range(groups)])
+
+    return L.cached(("output sum products", groups, terms), make)
+
+
+WEIGHT_VECTORS = [(1, -1, 1), ((1 << 31) - 1, -((1 << 31) - 1), 1), (-(1 << 31), (1 << 31) - 1, 1), (3, -2, -1)]
+SUM_EVENTS = ("raw q", "raw q - 1", "final 0", "final q - 1", "final 1", "zero weight", "raw q in polynomial 1")
+
+
+def modulus_weights(L: "Landing") -> list:
+    """Weights of the size of a 30-bit prime q_1 of the set: (q_1, -q_1, 1) is 0 modulo q_1 alone in its first two terms;
+    (2 q_1 - 2^31, 2^31 - 1, -2^31) has two weights above q_1 in absolute value and a first one that is -2^31 modulo q_1."""
+    q1 = next(q for q in L.primes if q.bit_length() == 30)
+    return [(q1, -q1, 1), (2 * q1 - (1 << 31), (1 << 31) - 1, -(1 << 31))]
+
+
+def weighted_sum_case(L: "Landing", weights, groups: int = 2, terms: int = 3):
+    """(a uint64[groups][terms][2][K][n], expected uint64[groups][3][K][n], events {name: int[K]}): the operands of output_sum_case
+    (to be multiplied by (1, 1)), the sums sum_t (w_t mod q_i) p_t mod q_i of the oracle's products p_t row by row in Python
+    integers (DESIGN 5.6.1's definition), and how often each edge is met on polynomials 0 and 2, per residue row.  The kernels
+    (mul_tail_sum_weighted_kernel's four bodies, scaled_accumulate_kernel) all add in term order, the first term onto 0:
+    raw_t = acc_{t-1} + (p_t w_t mod q_i), acc_t = raw_t reduced; that order is counted.
+    "raw q" / "raw q - 1": a raw_t that is exactly q_i (the `>= q` compare) / q_i - 1; "final 0" / "final q - 1" / "final 1": the
+    stored word; "zero weight": a weighted residue of 0 from a nonzero product word.  Polynomial 1 (a0 + a1 through the floor: small
+    integers too, not chosen) meets a raw sum of q_i under some weights as well; that is counted apart, "raw q in polynomial 1", so
+    that a vector with no raw q_i ANYWHERE is known.
+    Polynomials 0 and 2 are also derived from `kinds` and the weights alone; the two derivations must agree."""
+    weights = tuple(int(w) for w in weights)
+    assert len(weights) == terms
+
+    def make():
+        a, kinds = output_sum_case(L, groups, terms)
+        prods = output_sum_products(L, groups, terms)
+        P = [int(q) for q in L.primes]
+        expected = np.zeros((groups, 3, L.K, L.n), dtype=np.uint64)
+        events = {e: np.zeros(L.K, dtype=np.int64) for e in SUM_EVENTS}
+        for i, q in enumerate(P):
+            acc = np.zeros((groups, 3, L.n), dtype=object)
+            for j, w in enumerate(weights):
+                p = _obj(prods[:, j, :, i])
+                wr = p * (w % q) % q
+                raw = acc + wr
+                events["raw q"][i] += int((raw[:, ::2] == q).sum())
+                events["raw q - 1"][i] += int((raw[:, ::2] == q - 1).sum())
+                events["zero weight"][i] += int(((wr[:, ::2] == 0) & (p[:, ::2] != 0)).sum())
+                events["raw q in polynomial 1"][i] += int((raw[:, 1] == q).sum())
+                acc = raw % q
+            expected[:, :, i] = _u64(acc)
+            for name, v in (("final 0", 0), ("final q - 1", q - 1), ("final 1", 1)):
+                events[name][i] += int((acc[:, ::2] == v).sum())
+            from_kinds = sum(_obj(kinds[:, j]) * w for j, w in enumerate(weights)) % q  # [groups][2][n]
+            assert (from_kinds == acc[:, ::2]).all(), ("the sums from the kinds and from the oracle's products differ", L.pid, weights, i)
+        return a, expected, events
+
+    return L.cached(("weighted sum", weights, groups, terms), make)

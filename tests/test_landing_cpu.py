@@ -360,3 +360,106 @@ def test_gamma_residues_land_and_only_the_turned_branch_differs(pid, t):
             assert (o.decrypt(ct[i], L.sk) == want).all(), i
             turned, _ = _decrypt_over_the_integers(o, phases[i], turned=True)
             assert ((turned != want) == (np.array(targets[i], dtype=object) == gamma >> 1)).all(), i
+
+
+# ---- I: prepared multiplicands and weighted sums (tests/test_gpu_landing_shared.py) ------------------------------------------
+SHARED_SETS = ["P1", "P3", "P4", "P5", "W4096", "W2048", "U1024"]
+
+
+@pytest.mark.parametrize("pid", SHARED_SETS)
+def test_the_oracle_multiply_is_symmetric_on_the_crafted_operands(pid):
+    """BFV's tensor is symmetric: multiply(b, a) has the words of multiply(a, b).  One product of the oracle then serves the crafted
+    operand in the prepared role and in the role of `a`; shown here per set, on a crafted head pair and on a floor operand by (1, 1),
+    before tests/test_gpu_landing_shared.py relies on it."""
+    L = landing(pid)
+    o = L.o
+    a, b = LD.mtilde_case(L)
+    for i in (1, 3):  # edge times random, edge times all-rows-at-q-1
+        assert (o.multiply(b[i], a[i]) == o.multiply(a[i], b[i])).all(), (pid, "head", i)
+    if pid != "U1024":
+        fo, ones = LD.floor_operands(L), LD.ones_ct(L, 1)[0]
+        for i in (0, 3):
+            assert (o.multiply(ones, fo[i]) == o.multiply(fo[i], ones)).all(), (pid, "floor", i)
+
+
+def test_with_decoy_never_gives_the_identity():
+    L = landing("P1")
+    for m in (1, 4, 6):
+        ops = [np.full((2, L.K, L.n), 10 + i, dtype=np.uint64) for i in range(m)]
+        prepared, index = LD.with_decoy(L, ops)
+        assert len(prepared) == m + 1 and 1 not in index and sorted(index + [1]) == list(range(m + 1))
+        assert all((prepared[p] == ops[i]).all() for i, p in enumerate(index))
+        assert m == 1 or (index != list(range(m)) and len({index[i + 1] - index[i] for i in range(m - 1)}) > 1)
+        assert not any((prepared[1] == x).all() for x in ops)
+    assert LD.with_decoy(L, [ops[0]])[1] == [0]  # the broadcast index beside the decoy
+
+
+def test_the_nine_items_use_every_prepared_ciphertext_through_a_map_that_is_not_the_identity():
+    L = landing("P4")
+    a, prepared, index, refs = LD.nine_case(L)
+    assert a.shape[0] == 9 and prepared.shape[0] == 10 and len(index) == 9
+    assert sorted(index) == list(range(1, 10)) and 0 not in index                    # all nine, never the decoy
+    assert all(index[i] != i for i in range(9)) and len({index[i + 1] - index[i] for i in range(8)}) > 2
+    assert (9 + 7) >> 3 == 2 and (10 + 7) >> 3 == 2                                  # per = 2 in the product and in prepare
+    assert sorted(refs) == sorted([("head", k) for k in range(4)] + [("floor", 1)] + [("floor", k) for k in range(4)])
+    ma, mb = LD.mtilde_case(L)
+    fo, ones = LD.floor_operands(L), LD.ones_ct(L, 1)[0]
+    for i, (family, k) in enumerate(refs):  # item i and its prepared ciphertext ARE the pair of product k, in either order
+        x, y = (ma[k], mb[k]) if family == "head" else (fo[k], ones)
+        got = (a[i], prepared[index[i]])
+        assert all((g == w).all() for g, w in zip(got, (x, y))) or all((g == w).all() for g, w in zip(got, (y, x))), i
+    assert not any((prepared[0] == p).all() for p in prepared[1:])
+
+
+WEIGHTED_SETS = ["P3", "P4", "P5", "W4096", "W2048", "U1024", "S4096"]
+
+
+@pytest.mark.parametrize("pid", WEIGHTED_SETS)
+def test_weighted_sums_land_and_meet_every_event_in_every_row(pid):
+    """weighted_sum_case: the sums in Python integers are the oracle's negate / add chains where the weights are small, polynomials
+    0 and 2 follow from the kinds and the weights alone (asserted inside the builder), and the weight vectors together put a raw
+    sum of exactly q_i, one of q_i - 1, a final 0, q_i - 1 and 1 in front of every residue row; the modulus-sized weights add a
+    weighted residue of 0 from a nonzero product in the row of q_1 alone."""
+    L = landing(pid)
+    o, P, n = L.o, L.primes, L.n
+    if pid == "S4096":
+        assert [q.bit_length() for q in P] == [30, 30, 40] and n == 4096
+    prods = LD.output_sum_products(L)
+    a, kinds = LD.output_sum_case(L)
+    groups, terms = a.shape[:2]
+    slots = groups * 2 * n
+    vectors = list(LD.WEIGHT_VECTORS) + (LD.modulus_weights(L) if pid in ("U1024", "S4096") else [])
+    total = {e: np.zeros(L.K, dtype=np.int64) for e in LD.SUM_EVENTS}
+    for w in vectors:
+        ops, want, events = LD.weighted_sum_case(L, w)
+        assert ops is a and want.shape == (groups, 3, L.K, n)
+        print(pid, w, {e: [int(v) for v in c] for e, c in events.items()})
+        for e in LD.SUM_EVENTS:
+            total[e] += events[e]
+        if max(abs(x) for x in w) <= 3:  # the definition, pinned to the oracle: |w| additions of the (negated) product
+            for g in range(groups):
+                acc = None
+                for j, x in enumerate(w):
+                    base = o.negate(prods[g, j]) if x < 0 else prods[g, j]
+                    for _ in range(abs(x)):
+                        acc = base if acc is None else o.add(acc, base)
+                assert (acc == want[g]).all(), (pid, w, g)
+        if w == (1, -1, 1):  # two of the three orders of (0, -1, -1) pass through exactly q and end on 0
+            assert all(2 * slots // 3 <= c <= 2 * slots // 3 + 2 for c in events["raw q"]) and (events["final 0"] == events["raw q"]).all()
+            if pid == "P3":
+                assert slots == 32768 and set(events["raw q"]) == {21845} and set(events["raw q - 1"]) == {32769}
+        if w == (3, -2, -1) and pid == "P3":
+            assert set(events["final q - 1"]) == {10923} and set(events["raw q - 1"]) == {21846}
+    for e in LD.SUM_EVENTS[:5]:
+        assert (total[e] > 0).all(), (pid, e, total[e])
+    if pid in ("U1024", "S4096"):
+        row = P.index(LD.modulus_weights(L)[0][0])
+        assert total["zero weight"][row] > 0 and all(total["zero weight"][i] == 0 for i in range(L.K) if i != row), total["zero weight"]
+        assert all(abs(x) > P[row] for x in LD.modulus_weights(L)[1][1:])  # above the modulus: (w mod q_1) is not w
+    else:
+        assert (total["zero weight"] == 0).all()
+    # the unweighted sums of tests/test_gpu_landing_multiply.py are the all-ones case of the same builder: q - 2 everywhere
+    if pid in ("P3", "P4"):
+        qm2 = np.array(P, dtype=np.uint64)[:, None] - 2
+        ones_sum = LD.weighted_sum_case(L, (1, 1, 1))[1]
+        assert (ones_sum[:, 0] == qm2).all() and (ones_sum[:, 2] == qm2).all()
