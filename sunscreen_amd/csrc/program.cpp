@@ -433,6 +433,23 @@ KeySel ProgramKeys::galois_sel(u32 elt) const {
   return sel;
 }
 
+int rotate_rows_planned(Evaluator& ev, const ProgramKeys& keys, const u64* in, int steps, u64* out, size_t batch, hipStream_t s) {
+  Context* ctx = ev.ctx();
+  const RowRotation r = plan_row_rotation((u32)ctx->n(), steps, [&](u32 elt) { return keys.galois_sel(elt).present(); });
+  if (r.kind == RowRotation::kTooLarge) return kInvalidArg;
+  if (r.kind == RowRotation::kNoKey) return kNoKey;
+  if (r.kind == RowRotation::kCopy) {
+    if (in != out && hipMemcpyAsync(out, in, batch * ctx->ct_words(2) * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess) return kHipError;
+    return kOk;
+  }
+  return run_row_rotation(r, in, out, [&](u32 elt, const u64* cur, u64* o) { return ev.apply_galois(cur, elt, keys.galois_sel(elt), o, batch, s); });
+}
+
+bool Program::literal_fits(const PlainLiteral& lit, const Context& ctx) {
+  const std::vector<u64>& kp = ctx.key_primes();
+  return lit.n == ctx.n() && lit.t == ctx.host().t && lit.primes.size() == kp.size() && std::equal(kp.begin(), kp.end(), lit.primes.begin());
+}
+
 int Program::run(Evaluator& ev, size_t batch, const ProgramInput* inputs, size_t num_inputs, const ProgramKeys& keys,
                  u64* const* outputs, size_t num_outputs_given, hipStream_t s,
                  std::string* err) const {
@@ -491,20 +508,6 @@ int Program::run_serial(Evaluator& ev, size_t batch, const ProgramInput* inputs,
     for (void* p : live) pool.release(p, s);
     return fail(code, m);
   };
-  auto galois_key = [&](u32 elt) -> KeySel { return keys.galois_sel(elt); };
-  // rotate `in` by `steps` into `out` following SEAL's rotate_internal: planned over the run's keys, then launched
-  auto rotate = [&](const u64* in, int steps, u64* out) -> int {
-    const RowRotation r = plan_row_rotation((u32)n, steps, [&](u32 elt) { return galois_key(elt).present(); });
-    if (r.kind == RowRotation::kTooLarge) return kInvalidArg;
-    if (r.kind == RowRotation::kNoKey) return kNoKey;
-    if (r.kind == RowRotation::kCopy) {
-      if (in != out && hipMemcpyAsync(out, in, batch * ctx->ct_words(2) * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return kHipError;
-      return kOk;
-    }
-    return run_row_rotation(r, in, out, [&](u32 elt, const u64* cur, u64* o) { return ev.apply_galois(cur, elt, galois_key(elt), o, batch, s); });
-  };
-
   size_t out_idx = 0;
   std::vector<int> out_slot(nn, -1);
   for (int i = 0; i < nn; i++)
@@ -565,9 +568,7 @@ int Program::run_serial(Evaluator& ev, size_t batch, const ProgramInput* inputs,
         continue;
       case kOpLiteralPlaintext: {
         const PlainLiteral& lit = literals_[nd.arg];
-        const std::vector<u64>& kp = ctx->key_primes();
-        if (lit.n != n || lit.t != ctx->host().t || lit.primes.size() != kp.size() || !std::equal(kp.begin(), kp.end(), lit.primes.begin()))
-          return cleanup(kInvalidArg, "plaintext literal was built for different encryption parameters");
+        if (!literal_fits(lit, *ctx)) return cleanup(kInvalidArg, "plaintext literal was built for different encryption parameters");
         u64* dev = (u64*)pool.acquire(n * sizeof(u64), s);
         if (!dev) return cleanup(kOutOfMemory, "scratch allocation failed");
         live.push_back(dev);
@@ -706,13 +707,13 @@ int Program::run_serial(Evaluator& ev, size_t batch, const ProgramInput* inputs,
         {
           const int steps = nd.op == kOpShiftLeft ? k : -k;
           const u32 elt = steps ? ev.galois_elt_from_step(steps) : 0;
-          const KeySel key = elt ? galois_key(elt) : KeySel();
+          const KeySel key = elt ? keys.galois_sel(elt) : KeySel();
           const u64* addend = key.present() ? addend_for(id) : nullptr;  // single key switch: the Add can ride along
           if (addend) {
             rc = ev.apply_galois(L->ct, elt, key, out, batch, s, addend);
             if (!rc) folded[add_user[id]] = id;
           } else {
-            rc = rotate(L->ct, steps, out);
+            rc = rotate_rows_planned(ev, keys, L->ct, steps, out, batch, s);
           }
         }
         v.ct = out;
@@ -723,7 +724,7 @@ int Program::run_serial(Evaluator& ev, size_t batch, const ProgramInput* inputs,
         if (L->size != 2) return cleanup(kInvalidArg, "rotation needs a size-2 ciphertext");
         if (!ctx->batching()) return cleanup(kUnsupported, "encryption parameters do not support batching");
         const u32 elt = 2 * (u32)n - 1;
-        const KeySel key = galois_key(elt);
+        const KeySel key = keys.galois_sel(elt);
         if (!key.present()) return cleanup(kNoKey, "Galois key for the column rotation is missing");
         v.size = 2;
         u64* out = alloc_ct(2);

@@ -61,6 +61,9 @@ struct ProgramKeys {
   mutable std::map<u32, std::vector<const u64*>> tables_;  // host pointer tables handed out by galois_sel (alive for the run)
 };
 
+// rotate `in` by `steps` into `out` following SEAL's rotate_internal: planned over the run's keys, then launched (both executors)
+int rotate_rows_planned(Evaluator& ev, const ProgramKeys& keys, const u64* in, int steps, u64* out, size_t batch, hipStream_t s);
+
 class Program {
  public:
   int add_node(OpKind op, u64 arg);
@@ -86,11 +89,12 @@ class Program {
                  std::string* err) const;
   // Level-scheduled execution: every node that is ready runs in the same round (run.rs:372-472 runs them concurrently on
   // rayon); ready nodes of one kind become ONE batched launch, Add / Sub / Negate trees become n-ary sums, sums of
-  // ciphertext-plaintext products stay in the transform domain.
+  // ciphertext-plaintext products stay in the transform domain.  One run is a PlanRun object (program_plan.cpp).
   int run_plan(Evaluator& ev, size_t batch, const ProgramInput* inputs, size_t num_inputs, const ProgramKeys& keys,
                u64* const* outputs, size_t num_outputs, hipStream_t s,
                std::string* err) const;
   struct Plan;
+  struct PlanRun;
   // one line per step of the schedule: "<kind> members=<m> ..." (diagnostics; tests/test_program_plan_cpu.py reads it)
   int describe(std::string* out) const;
 
@@ -105,6 +109,8 @@ class Program {
     std::vector<u64> primes;  // Params::coeff_modulus (key-level primes)
     std::vector<u64> coeffs;
   };
+  // false when the literal was built for other encryption parameters than the context's (both executors refuse to run it)
+  static bool literal_fits(const PlainLiteral& lit, const Context& ctx);
   bool topo_order(std::vector<int>* order) const;
   std::shared_ptr<const Plan> plan() const;  // built on first use, dropped whenever the graph changes
   void drop_plan();

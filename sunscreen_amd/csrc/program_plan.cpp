@@ -3,7 +3,7 @@
 // The reference runs a compiled FheProgram with `traverse` (sunscreen_runtime/src/run.rs:372-472): every node whose
 // operands are complete is spawned on the rayon pool, so all ready nodes run concurrently, each as one SEAL call on one
 // ciphertext.  On a GPU "concurrently" means "in one launch": this file turns the graph -- once per Program, cached --
-// into a PLAN of rounds, and a run walks the plan:
+// into a PLAN of rounds, and a run (Program::run_plan: one PlanRun object, a member function per step kind) walks the plan:
 //
 //   * Add / Sub / Negate trees whose inner nodes have a single user collapse into n-ary signed sums (exact canonical
 //     arithmetic: any association order gives the bits of the node-by-node evaluation, run.rs:217-236,283-311); all sums
@@ -53,6 +53,7 @@ enum StepKind : int {
   kStepPlainOp,     // AddPlaintext / SubPlaintext / MultiplyPlaintext outside a transform-domain sum: one member
   kStepOutput,      // OutputCiphertext: copy unless the producer wrote the caller's buffer directly
 };
+const char* const kStepNames[] = {"sum", "plain_matrix", "mul_relin", "multiply", "relinearize", "rotate", "plain_op", "output"};  // (describe, StepTrace)
 
 struct Term {
   int slot;
@@ -711,10 +712,9 @@ int Program::describe(std::string* out) const {
     *out = "error: " + P.err;
     return P.rc;
   }
-  static const char* names[] = {"sum", "plain_matrix", "mul_relin", "multiply", "relinearize", "rotate", "plain_op", "output"};
   std::string t;
   for (const Plan::Step& st : P.steps) {
-    t += names[st.kind];
+    t += kStepNames[st.kind];
     t += " members=" + std::to_string(st.node.size());
     if (st.kind == kStepNary) t += " terms=" + std::to_string(st.terms.size());
     if (st.kind == kStepLinComb) t += " columns=" + std::to_string(st.cts.size());
@@ -794,7 +794,7 @@ struct TableArena {
     if (host) (void)hipHostFree(host);
   }
 };
-// Two arenas per host thread, used alternately (thread_local in run_plan; a thread that ends gives its pinned memory back, ADVICE
+// Two arenas per host thread, used alternately (thread_local in PlanRun::setup; a thread that ends gives its pinned memory back, ADVICE
 // r03): while the device still copies run i's tables out of one, the host builds run i + 1's in the other, and a scheduled run
 // returns without a stream synchronisation of its own.
 struct TableArenas {
@@ -805,12 +805,629 @@ struct TableArenas {
 
 constexpr size_t merge_max_batch() { return 32; }  // (measured in r03: DESIGN.md, the scheduled executor)
 
+// an environment switch is on when its value starts with '1'.  Read per run (not cached): the tests flip them inside one process.
+bool env_on(const char* name) {
+  const char* e = std::getenv(name);
+  return e && e[0] == '1';
+}
+
+double now_us() {
+  struct timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
+}
+// HIPBFV_PROGRAM_TRACE=1: drain the stream after every step and print where the time goes (diagnostics only)
+struct StepTrace {
+  bool on;
+  hipStream_t s;
+  const char* name;
+  size_t members;
+  double t0 = on ? now_us() : 0.0;
+  ~StepTrace() {
+    if (!on) return;
+    const double t1 = now_us();
+    (void)hipStreamSynchronize(s);
+    const double t2 = now_us();
+    fprintf(stderr, "[program] %-12s members=%zu host %.0f us, drained after %.0f us\n", name, members, t1 - t0, t2 - t0);
+  }
+};
+
 }  // namespace
+
+// One run of a plan: the state the steps share, the helpers they use and one member function per step kind.  A run that succeeds
+// ends in finish(); a run that ends anywhere else is undone by the destructor, so a failure exit is `return fail(code, message)`
+// and nothing more -- an early return cannot leak scratch-pool blocks or side-stream events.
+struct Program::PlanRun {
+  // ---- slot storage: blocks with reference counts (members of a merged launch share one block; a folded Add shares its producer's) ----
+  struct Block {
+    void* ptr;
+    int refs;
+    bool owned;
+  };
+  struct SideProduct {
+    const u64* base = nullptr;      // the product's output block (rows x batch ciphertexts)
+    size_t rows = 0;
+    std::vector<size_t> row_end;    // chunk c covers rows [row_end[c - 1], row_end[c])
+    std::vector<hipEvent_t> done;   // recorded on the side stream behind chunk c
+    bool noted = false;
+  };
+  struct PlainVal {
+    const u64* ptr = nullptr;
+    size_t stride = 0;
+    int kind = 1;
+  };
+
+  const Program& prog;
+  const Plan& P;
+  Evaluator& ev;
+  Context* const ctx;
+  ScratchPool& pool;
+  const ProgramInput* const inputs;
+  const ProgramKeys& keys;
+  u64* const* const outputs;
+  const hipStream_t s;
+  std::string* const err;
+  const size_t batch, num_inputs, n, K, poly;
+  const KeySel relin_key;
+  // the switches (env_on): HIPBFV_PROGRAM_TRACE (StepTrace), HIPBFV_PIR_OVERLAP (side_product), HIPBFV_NO_MEMBER_TAILS: the sums around fused products as
+  // launches of their own (the cross-check arm), HIPBFV_NO_MERGED_PRODUCTS: merged product launches below merge_max_batch() only (r03 ... r06 s26)
+  const bool small, trace, side_enabled, member_tails, merge_products;
+  std::vector<Block> blocks;
+  std::vector<const u64*> sp;
+  std::vector<int> block_of;
+  std::vector<char> direct_written;
+  std::vector<void*> temps;  // staging buffers released when the run ends (stream-ordered)
+  SideProduct side;
+  bool side_consumer = false;  // this step takes the side product chunk by chunk (takes_side_product)
+  std::unordered_map<int, PlainVal> literal_val;
+  TableArena* arena = nullptr;
+  bool tables_used = false, failed = false, finished = false;
+  // which sums were folded into their producer at run time: (step, member) -> the slot that carries the result
+  std::vector<std::vector<int>> folded_into;
+
+  PlanRun(const Program& prog, const Plan& P, Evaluator& ev, size_t batch, const ProgramInput* inputs, size_t num_inputs, const ProgramKeys& keys,
+          u64* const* outputs, size_t num_outputs, hipStream_t s, std::string* err)
+      : prog(prog), P(P), ev(ev), ctx(ev.ctx()), pool(ev.scratch()), inputs(inputs), keys(keys), outputs(outputs), s(s), err(err),
+        batch(batch), num_inputs(num_inputs), n(ctx->n()), K(ctx->K()), poly(K * n), relin_key(keys.relin_sel()), small(batch <= merge_max_batch()),
+        trace(env_on("HIPBFV_PROGRAM_TRACE")), side_enabled(env_on("HIPBFV_PIR_OVERLAP")), member_tails(!env_on("HIPBFV_NO_MEMBER_TAILS")),
+        merge_products(!env_on("HIPBFV_NO_MERGED_PRODUCTS") || small), sp(P.nslots, nullptr), block_of(P.nslots, -1), direct_written(num_outputs, 0),
+        folded_into(P.steps.size()) {
+    for (int sl = 0; sl < P.nslots; sl++)  // program arguments (checked by run_plan)
+      if (P.slot_input[sl] >= 0) sp[sl] = inputs[P.slot_input[sl]].ptr;
+  }
+  PlanRun(const PlanRun&) = delete;
+
+  // the first message of a run stands: a step's own where it has one, else the general one of the loop over steps
+  int fail(int code, const char* m) {
+    if (err && !failed) *err = m;
+    failed = true;
+    return code;
+  }
+  void release_all() {
+    for (Block& b : blocks)
+      if (b.owned && b.refs > 0) pool.release(b.ptr, s);
+    for (void* t : temps) pool.release(t, s);
+  }
+  ~PlanRun() {
+    if (finished) return;
+    // (nothing of the side stream may still run when the run's buffers go back to the pool)
+    for (hipEvent_t e : side.done) {
+      (void)hipEventSynchronize(e);
+      (void)hipEventDestroy(e);
+    }
+    release_all();
+    (void)hipStreamSynchronize(s);  // descriptor tables of this run live in this thread's arena
+  }
+  int finish() {
+    if (int rc = side_flush()) return fail(rc, "operation failed");
+    release_all();
+    finished = true;
+    // the descriptor tables were copied from this thread's pinned arena: an event behind the copies guards its reuse (two runs from
+    // now: TableArenas) -- the run itself does not wait for the device
+    if (tables_used && !arena->mark(s)) return fail(kHipError, "stream synchronisation failed");
+    return kOk;
+  }
+
+  int new_block(size_t words) {
+    void* p = pool.acquire(words * sizeof(u64), s);
+    if (!p) return -1;
+    blocks.push_back(Block{p, 0, true});
+    return (int)blocks.size() - 1;
+  }
+  void bind(int slot, int blk, const u64* ptr) {
+    sp[slot] = ptr;
+    block_of[slot] = blk;
+    if (blk >= 0) blocks[blk].refs++;
+  }
+  void unbind(int slot) {
+    const int blk = block_of[slot];
+    if (blk < 0) return;
+    block_of[slot] = -1;
+    if (--blocks[blk].refs == 0 && blocks[blk].owned) pool.release(blocks[blk].ptr, s);
+  }
+  // a member's own output buffer: the caller's output buffer when the value only feeds an OutputCiphertext node
+  u64* alloc_member(int slot) {
+    const int d = P.slot_direct[slot];
+    if (d >= 0) {
+      direct_written[d] = 1;
+      blocks.push_back(Block{outputs[d], 0, false});
+      bind(slot, (int)blocks.size() - 1, outputs[d]);
+      return outputs[d];
+    }
+    const int blk = new_block(batch * (size_t)P.slot_size[slot] * poly);
+    if (blk < 0) return nullptr;
+    bind(slot, blk, (const u64*)blocks[blk].ptr);
+    return (u64*)blocks[blk].ptr;
+  }
+  // plaintext literals uploaded once per run (program arguments are used as they are: plain_of), then this thread's table arena
+  int setup() {
+    if (!P.literal_nodes.empty()) {
+      u64* dev = (u64*)pool.acquire(P.literal_nodes.size() * n * sizeof(u64), s);
+      if (!dev) return fail(kOutOfMemory, "scratch allocation failed");
+      temps.push_back(dev);
+      std::vector<u64> host(P.literal_nodes.size() * n, 0);
+      for (size_t i = 0; i < P.literal_nodes.size(); i++) {
+        const PlainLiteral& lit = prog.literals_[prog.nodes_[P.literal_nodes[i]].arg];
+        if (!literal_fits(lit, *ctx)) return fail(kInvalidArg, "plaintext literal was built for different encryption parameters");
+        std::copy(lit.coeffs.begin(), lit.coeffs.end(), host.begin() + i * n);
+        literal_val[P.literal_nodes[i]] = PlainVal{dev + i * n, 0, 1};
+      }
+      // ordered after earlier users of the recycled buffer on this stream; drained so `host` may go out of scope
+      if (hipMemcpyAsync(dev, host.data(), host.size() * sizeof(u64), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(kHipError, "copy failed");
+    }
+    // ---- descriptor tables: pinned host arena -> one device buffer per table ----
+    thread_local TableArenas arenas;
+    arena = &arenas.next();
+    if (!arena->wait_idle()) return fail(kHipError, "event synchronisation failed");
+    arena->used = 0;
+    // reserve the worst case up front so that the host pointers handed out stay valid for the whole run
+    size_t need = 0;
+    for (const Plan::Step& st : P.steps)
+      need += (st.node.size() + 1 + st.terms.size() / 8) * sizeof(NaryOut) + 2 * st.terms.size() * sizeof(NaryTerm) + st.plain.size() * sizeof(PlainNttRef) +
+              (st.a.size() + st.b.size() + st.cts.size() + 4) * sizeof(u64*) + 512;
+    if (!arena->reserve(need + 4096)) return fail(kOutOfMemory, "descriptor table allocation failed");
+    return kOk;
+  }
+  const char* plain_of(int node, PlainVal* out) {
+    const Node& nd = prog.nodes_[node];
+    if (nd.op == kOpLiteralPlaintext) {
+      *out = literal_val[node];
+      return nullptr;
+    }
+    if (nd.arg >= num_inputs) return "input index out of range";
+    const ProgramInput& in = inputs[nd.arg];
+    if ((in.kind != 1 && in.kind != 2) || !in.ptr) return "argument is not a plaintext";
+    *out = PlainVal{in.ptr, in.stride, in.kind};
+    return nullptr;
+  }
+  // a table is either copied into the arena (stage_table) or built in place there (stage_begin / stage_commit: the 1 MB
+  // plaintext table of a 256 x 256 lookup is written once instead of built, then copied)
+  unsigned char* stage_begin(size_t bytes) {
+    const size_t off = (arena->used + 63) & ~(size_t)63;
+    arena->used = off + ((bytes + 7) / 8) * 8;
+    return arena->host + off;
+  }
+  const void* stage_commit(const unsigned char* hp, size_t bytes) {  // returns the DEVICE copy
+    const size_t words = (bytes + 7) / 8;
+    void* dev = pool.acquire(words * 8, s);
+    if (!dev) return nullptr;
+    temps.push_back(dev);
+    // a kernel, not hipMemcpyAsync: a copy enqueued on the caller's stream waits for the stream to drain on the HOST when that
+    // stream is the null stream (PyTorch's default), and every drained launch queue costs the device idle time
+    if (launch_copy_words((const u64*)hp, (u64*)dev, words, s) != hipSuccess) return nullptr;
+    tables_used = true;
+    return dev;
+  }
+  const void* stage_table(const void* src, size_t bytes) {
+    unsigned char* hp = stage_begin(bytes);
+    std::memcpy(hp, src, bytes);
+    return stage_commit(hp, bytes);
+  }
+
+  bool adjacent(const std::vector<int>& slots, size_t words_each) const {  // the slots' buffers follow each other in memory, in order
+    for (size_t m = 1; m < slots.size(); m++)
+      if (sp[slots[m]] != sp[slots[0]] + m * words_each) return false;
+    return true;
+  }
+  // the slots' buffers, words_each words each, into ONE array through a staged pointer table.  *dst == nullptr: the array is acquired
+  // here, behind the table (the order of pool calls decides the addresses, and with them what a later merged launch finds adjacent).
+  int gather(const std::vector<int>& slots, size_t words_each, u64** dst) {
+    std::vector<const u64*> tab(slots.size());
+    for (size_t m = 0; m < slots.size(); m++) tab[m] = sp[slots[m]];
+    const u64* const* dtab = (const u64* const*)stage_table(tab.data(), tab.size() * sizeof(u64*));
+    if (!*dst && (*dst = (u64*)pool.acquire(slots.size() * words_each * sizeof(u64), s))) temps.push_back(*dst);
+    if (!dtab || !*dst) return kOutOfMemory;
+    for (size_t off = 0; off < slots.size(); off += 65535) {
+      const size_t c = std::min<size_t>(65535, slots.size() - off);
+      if (launch_gather_items(dtab + off, *dst + off * words_each, words_each, c, s) != hipSuccess) return kHipError;
+    }
+    return kOk;
+  }
+  // operands of a merged launch as ONE array: used in place when the members' buffers are adjacent and in order, staged otherwise
+  int as_array(const std::vector<int>& slots, size_t words_each, const u64** out) {
+    u64* stage = nullptr;
+    if (!adjacent(slots, words_each))
+      if (int rc = gather(slots, words_each, &stage)) return rc;
+    *out = stage ? stage : sp[slots[0]];
+    return kOk;
+  }
+  const u64* try_fold(const Plan::Step& st, size_t m) {  // the addend to hand to the key-switching kernel, or nullptr
+    return st.fold.empty() || st.fold[m].other_slot < 0 ? nullptr : sp[st.fold[m].other_slot];
+  }
+  // member `nary_member` of sum step `nary_step` (a Plan::Fold or a Plan::LinFold) was written by its producer: `slot` carries it
+  template <class AnyFold>
+  void mark_folded(const AnyFold& f, int slot) {
+    auto& v = folded_into[f.nary_step];
+    if (v.empty()) v.assign(P.steps[f.nary_step].node.size(), -1);
+    v[f.nary_member] = slot;
+  }
+  // the buffer a key-switching member writes when its Add is folded: the sum's own destination
+  u64* alloc_for_fold(const Plan::Step& st, size_t m) {
+    const Plan::Fold& f = st.fold[m];
+    const int sum_slot = P.steps[f.nary_step].out[f.nary_member];
+    u64* p = alloc_member(sum_slot);  // binds the SUM's slot; the member's own slot aliases it
+    if (!p) return nullptr;
+    bind(st.out[m], block_of[sum_slot], p);
+    return p;
+  }
+  // ---- r06: the plaintext-matrix product on a side stream (examples/pir) ----
+  // The product of a LinComb step streams the database at 6+ TB/s and hardly uses the vector units; the merged multiply +
+  // relinearize that consumes its rows is bound by them.  When that is the very next step, the product runs on a SIDE stream in
+  // row chunks and the main stream takes each chunk's rows through the multiply as soon as its event has passed: chunk c + 1 of
+  // the product streams while chunk c is multiplied (measured with the batch primitives in r05: +2...4 %, same bits --
+  // tools/pir_overlap_probe.py).  Anything else that follows waits for every chunk first (`side_flush`).
+  // OPT-IN (HIPBFV_PIR_OVERLAP=1, read per run): measured inside this executor it LOSES -- examples/pir, 512 x 256 entries at
+  // n = 16384, interleaved on one box (profiles/r06_s11_ab_pir_overlap*.txt): serial 3.93 M entries/s, 2 chunks 3.84 M, 4 chunks
+  // 3.75 M, 8 chunks 3.48 M.  The probe's +2...4 % was against a CHUNKED serial schedule; the executor's serial schedule is one
+  // 512-row product and one 512-member multiply, and next to a concurrent multiply the product stream slows down by more (22.2 ->
+  // 24.6 ms) than the multiply hides.  Kept exercised by tests/test_gpu_program.py.
+  hipStream_t side_stream() {
+    thread_local hipStream_t streams[16] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    hipStream_t& ss = streams[dev & 15];
+    if (!ss && hipStreamCreateWithFlags(&ss, hipStreamNonBlocking) != hipSuccess) ss = nullptr;
+    return ss;
+  }
+  void side_drop() {
+    for (hipEvent_t e : side.done) (void)hipEventDestroy(e);
+    side = SideProduct{};
+  }
+  // the main stream waits for every outstanding chunk (a consumer other than the pipelined multiply, or the end of the run)
+  int side_flush() {
+    if (!side.base) return kOk;
+    int rc2 = kOk;
+    for (hipEvent_t e : side.done)
+      if (hipStreamWaitEvent(s, e, 0) != hipSuccess) rc2 = kHipError;
+    if (!rc2 && !side.noted) rc2 = ev.note_result(side.base, 2, (u32)K, side.rows * batch, s);
+    side_drop();
+    return rc2;
+  }
+  // the one consumer that takes the side product chunk by chunk: a merged multiply + relinearize right behind it (run_key_switch)
+  bool takes_side_product(const Plan::Step& st) const {
+    const size_t members = st.node.size();
+    if (!(side.base && st.kind == kStepMulRelin && small && members > 1 && members == side.rows && !st.square)) return false;
+    bool as_a = true, as_b = true;  // member m's left (or right) operand is row m of the product, in place
+    for (size_t m = 0; m < members; m++) {
+      as_a = as_a && sp[st.a[m]] == side.base + m * batch * 2 * poly;
+      as_b = as_b && sp[st.b[m]] == side.base + m * batch * 2 * poly;
+    }
+    return as_a || as_b;
+  }
+
+  int run_sum(size_t si, const Plan::Step& st) {
+    // A long sum (examples/pir: 256 products into one ciphertext) is one output per thread column: its terms are added
+    // one after the other.  Sums of more than kLongSum terms go in two levels -- partial sums of kSumChunk terms, which
+    // are many independent outputs, then the sum of the partials (modular addition is associative: same bits).
+    constexpr u32 kLongSum = 32, kSumChunk = 16;
+    std::vector<NaryOut> pre_outs, outs;
+    std::vector<NaryTerm> pre_terms, terms;
+    u32 max_size = 0, pre_max = 0;
+    const std::vector<int>& fv = folded_into[si];
+    for (size_t m = 0; m < st.node.size(); m++) {
+      if (!fv.empty() && fv[m] >= 0) continue;  // its producer already added the other operand and wrote this slot
+      const int osl = st.out[m];
+      u64* o = alloc_member(osl);
+      if (!o) return fail(kOutOfMemory, "out of device memory");
+      const u32 count = st.first[m + 1] - st.first[m], osz = P.slot_size[osl];
+      NaryOut d{o, (u32)terms.size(), count, osz, 0};
+      max_size = std::max(max_size, osz);
+      if (count > kLongSum) {
+        const u32 chunks = (count + kSumChunk - 1) / kSumChunk;
+        u64* part = (u64*)pool.acquire((size_t)chunks * batch * osz * poly * sizeof(u64), s);
+        if (!part) return fail(kOutOfMemory, "out of device memory");
+        temps.push_back(part);
+        pre_max = std::max(pre_max, osz);
+        for (u32 c = 0; c < chunks; c++) {
+          const NaryOut pd{part + (size_t)c * batch * osz * poly, (u32)pre_terms.size(), std::min(kSumChunk, count - c * kSumChunk), osz, 0};
+          for (u32 t = 0; t < pd.count; t++) {
+            const Term& tm = st.terms[st.first[m] + c * kSumChunk + t];
+            pre_terms.push_back(NaryTerm{sp[tm.slot], P.slot_size[tm.slot], tm.sign});
+          }
+          pre_outs.push_back(pd);
+          terms.push_back(NaryTerm{pd.out, osz, 1});
+        }
+        d.count = chunks;
+      } else {
+        for (u32 t = st.first[m]; t < st.first[m + 1]; t++) terms.push_back(NaryTerm{sp[st.terms[t].slot], P.slot_size[st.terms[t].slot], st.terms[t].sign});
+      }
+      outs.push_back(d);
+    }
+    if (outs.empty()) return kOk;
+    if (!pre_outs.empty()) {
+      const NaryOut* dpo = (const NaryOut*)stage_table(pre_outs.data(), pre_outs.size() * sizeof(NaryOut));
+      const NaryTerm* dpt = (const NaryTerm*)stage_table(pre_terms.data(), pre_terms.size() * sizeof(NaryTerm));
+      if (!dpo || !dpt) return fail(kOutOfMemory, "descriptor table allocation failed");
+      ev.profiler().begin(kKernEltwise, pre_outs.size() * batch * pre_max * K, s);
+      const hipError_t e = launch_nary_sum(ctx->dev(), (u32)n, (u32)K, dpo, dpt, (u32)pre_outs.size(), pre_max, (u32)batch, s);
+      ev.profiler().end(s);
+      if (e != hipSuccess) return fail(kHipError, "operation failed");
+    }
+    const NaryOut* douts = (const NaryOut*)stage_table(outs.data(), outs.size() * sizeof(NaryOut));
+    const NaryTerm* dterms = (const NaryTerm*)stage_table(terms.data(), terms.size() * sizeof(NaryTerm));
+    if (!douts || !dterms) return fail(kOutOfMemory, "descriptor table allocation failed");
+    ev.profiler().begin(kKernEltwise, outs.size() * batch * max_size * K, s);
+    const hipError_t e = launch_nary_sum(ctx->dev(), (u32)n, (u32)K, douts, dterms, (u32)outs.size(), max_size, (u32)batch, s);
+    ev.profiler().end(s);
+    if (e != hipSuccess) return fail(kHipError, "operation failed");
+    return ev.note_nary(douts, (u32)outs.size(), (u32)batch, s);
+  }
+  // r06: products with a linear fold (Plan::LinFold) or a caller's buffer to write take each member's destination, multiplier and
+  // signed addend from a table in their last kernel (kernels.hpp MemberTail): the sums around the products and the copies into the
+  // outputs cost no pass of their own (examples/chi_sq: 2 x^2, 2 y^2, 4 n0 n2 - n1^2, x y).  Members [m0, m1) in one launch.
+  static bool has_lin(const Plan::Step& st, size_t m) { return !st.lin.empty() && st.lin[m].mult != 0; }
+  int tail_launch(const Plan::Step& st, size_t m0, size_t m1) {
+    const size_t cnt = m1 - m0;
+    std::vector<MemberHead> heads(cnt);  // the operands where they are (no gather into one array)
+    for (size_t m = m0; m < m1; m++) heads[m - m0] = MemberHead{sp[st.a[m]], sp[st.square ? st.a[m] : st.b[m]]};
+    std::vector<MemberTail> tab(cnt);
+    for (size_t m = m0; m < m1; m++) {
+      const Plan::LinFold* lf = has_lin(st, m) ? &st.lin[m] : nullptr;
+      const int target = lf ? P.steps[lf->nary_step].out[lf->nary_member] : st.out[m];
+      u64* o = alloc_member(target);  // the caller's buffer when the value is a program output
+      if (!o) return (int)kOutOfMemory;
+      if (lf) {
+        bind(st.out[m], block_of[target], o);  // (nothing reads the bare product: every use of it is inside the sum)
+        mark_folded(*lf, st.out[m]);
+      }
+      const bool has_other = lf && lf->other_slot >= 0;
+      tab[m - m0] = MemberTail{o, has_other ? sp[lf->other_slot] : nullptr, lf ? (u32)lf->mult : 1u, has_other ? lf->sign : 0};
+    }
+    const MemberTail* dtab = (const MemberTail*)stage_table(tab.data(), tab.size() * sizeof(MemberTail));
+    const MemberHead* dheads = (const MemberHead*)stage_table(heads.data(), heads.size() * sizeof(MemberHead));
+    if (!dtab || !dheads) return (int)kOutOfMemory;
+    KeySel sub = relin_key;  // (member-major item numbering: member m0's items start at m0 * batch)
+    sub.first = relin_key.first + m0 * batch;
+    int r = ev.multiply_relin(nullptr, nullptr, sub, nullptr, cnt * batch, s, nullptr, dtab, (u32)batch, dheads, st.square);
+    for (size_t m = 0; m < cnt && !r; m++) r = ev.note_result(tab[m].out, 2, (u32)K, batch, s);
+    return r;
+  }
+  // kStepMulRelin, kStepRelin and kStepGalois: the members that end in a key switch
+  int run_key_switch(size_t, const Plan::Step& st) {
+    const size_t members = st.node.size();
+    const bool is_mul = st.kind == kStepMulRelin, is_rot = st.kind == kStepGalois;
+    if (!is_rot && !relin_key.present() && !(st.kind == kStepRelin && st.out_size == 2)) return fail(kNoKey, "operation failed");
+    u32 elt = 0;
+    KeySel gkey;
+    if (is_rot) {
+      if (!ctx->batching()) return fail(kUnsupported, "encryption parameters do not support batching");
+      elt = st.swap ? 2 * (u32)n - 1 : (st.rot_steps ? ev.galois_elt_from_step(st.rot_steps) : 0);
+      if (st.swap || st.rot_steps) {
+        if (!elt) return fail(kInvalidArg, "operation failed");
+        gkey = keys.galois_sel(elt);
+        if (st.swap && !gkey.present()) return fail(kNoKey, "Galois key for the column rotation is missing");
+      }
+    }
+    const u32 in_size = st.kind == kStepRelin ? st.out_size : 2;
+    const size_t in_words = batch * in_size * poly, out_words = batch * 2 * poly;
+    const bool direct_ks = is_mul || (st.kind == kStepRelin && in_size == 3) || (is_rot && gkey.present());
+    const bool tails_on = is_mul && !side_consumer && member_tails;
+    int rc = kOk;
+    // With both tables a merged launch costs nothing to set up (operands and results stay where they are), so the ready products
+    // of a round run as ONE launch sequence at every batch size, not only below merge_max_batch(): examples/chi_sq at one GPU's
+    // share of 128 sets runs 384 + 256 + 128 items instead of six launches of 128.
+    if (tails_on && members > 1 && members <= 64 && merge_products && ev.member_tail_ok(members * batch)) return tail_launch(st, 0, members);
+    if (small && members > 1 && direct_ks) {
+      // ONE launch sequence over members x batch ciphertexts
+      const u64 *A = nullptr, *B2 = nullptr;
+      if ((rc = as_array(st.a, in_words, &A))) return fail(rc, "operation failed");
+      if (is_mul && !st.square && (rc = as_array(st.b, in_words, &B2))) return fail(rc, "operation failed");
+      const int blk = new_block(members * out_words);
+      if (blk < 0) return fail(kOutOfMemory, "out of device memory");
+      u64* out = (u64*)blocks[blk].ptr;
+      for (size_t m = 0; m < members; m++) bind(st.out[m], blk, out + m * out_words);
+      const size_t count = members * batch;
+      if (side_consumer && is_mul) {
+        // rows of the side-stream product, chunk by chunk: the main stream waits for chunk c's event only, so the product's
+        // later chunks stream while this one is multiplied
+        size_t r0 = 0;
+        for (size_t c = 0; c < side.done.size() && !rc; c++) {
+          const size_t r1 = side.row_end[c];
+          if (hipStreamWaitEvent(s, side.done[c], 0) != hipSuccess) rc = kHipError;
+          KeySel sub = relin_key;
+          sub.first = relin_key.first + r0 * batch;
+          if (!rc) rc = ev.multiply_relin(A + r0 * batch * 2 * poly, B2 + r0 * batch * 2 * poly, sub, out + r0 * batch * 2 * poly, (r1 - r0) * batch, s);
+          r0 = r1;
+        }
+        if (!rc) rc = ev.note_result(side.base, 2, (u32)K, side.rows * batch, s);
+        side.noted = true;
+        side_drop();
+        return rc;
+      }
+      return is_mul ? ev.multiply_relin(A, st.square ? A : B2, relin_key, out, count, s)
+           : is_rot ? ev.apply_galois(A, elt, gkey, out, count, s)
+                    : ev.relinearize(A, relin_key, out, count, s);
+    }
+    for (size_t m = 0; m < members && !rc; m++) {
+      if (tails_on && has_lin(st, m) && !(small && members > 1) && ev.member_tail_ok(batch)) {  // (a merged launch has no tables: whole or not at all)
+        rc = tail_launch(st, m, m + 1);
+        continue;
+      }
+      const u64* addend = direct_ks ? try_fold(st, m) : nullptr;
+      u64* out = addend ? alloc_for_fold(st, m) : alloc_member(st.out[m]);
+      if (!out) return fail(kOutOfMemory, "out of device memory");
+      const u64* a = sp[st.a[m]];
+      if (is_mul)
+        rc = ev.multiply_relin(a, sp[st.b[m]], relin_key, out, batch, s, addend);
+      else if (st.kind == kStepRelin && in_size == 2)
+        rc = hipMemcpyAsync(out, a, out_words * sizeof(u64), hipMemcpyDeviceToDevice, s) == hipSuccess ? (int)kOk : (int)kHipError;
+      else if (st.kind == kStepRelin)
+        rc = ev.relinearize(a, relin_key, out, batch, s, addend);
+      else if (gkey.present())
+        rc = ev.apply_galois(a, elt, gkey, out, batch, s, addend);
+      else
+        rc = rotate_rows_planned(ev, keys, a, st.rot_steps, out, batch, s);
+      if (addend && !rc) mark_folded(st.fold[m], st.out[m]);
+    }
+    return rc;
+  }
+
+  int run_multiply(size_t, const Plan::Step& st) {
+    u64* out = alloc_member(st.out[0]);
+    if (!out) return fail(kOutOfMemory, "out of device memory");
+    return ev.multiply(sp[st.a[0]], P.slot_size[st.a[0]], sp[st.b[0]], P.slot_size[st.b[0]], out, batch, s);
+  }
+
+  int run_plain_op(size_t, const Plan::Step& st) {
+    PlainVal pv;
+    if (const char* m = plain_of(st.plain[0], &pv)) return fail(kInvalidArg, m);
+    const u32 sz = P.slot_size[st.a[0]];
+    if (pv.kind == 2 && st.plain_op != kOpMultiplyPlaintext)
+      return fail(kInvalidArg, "a transform-domain plaintext argument can only be an operand of MultiplyPlaintext");
+    u64* out = alloc_member(st.out[0]);
+    if (!out) return fail(kOutOfMemory, "out of device memory");
+    if (st.plain_op == kOpAddPlaintext) return ev.add_plain(sp[st.a[0]], sz, pv.ptr, pv.stride, out, batch, s);
+    if (st.plain_op == kOpSubPlaintext) return ev.sub_plain(sp[st.a[0]], sz, pv.ptr, pv.stride, out, batch, s);
+    if (pv.kind == 1) return ev.multiply_plain(sp[st.a[0]], sz, pv.ptr, pv.stride, out, batch, s);
+    return ev.multiply_plain_ntt(sp[st.a[0]], sz, pv.ptr, pv.stride, out, batch, s);
+  }
+  // the product of run_plain_matrix on the side stream, in row chunks, when the next step is the merged multiply + relinearize of
+  // these rows.  *pipelined stays false when it is not taken: the caller launches the product on the main stream.
+  int side_product(size_t si, const Plan::Step& st, const u64* staged, const PlainNttRef* dtab, u64* out, bool* pipelined) {
+    const size_t cols = st.cts.size(), rows = st.node.size(), ct_words = batch * 2 * poly;
+    if (!(side_enabled && small && rows >= 64 && si + 1 < P.steps.size())) return kOk;
+    const Plan::Step& nx = P.steps[si + 1];
+    if (!(nx.kind == kStepMulRelin && nx.node.size() == rows && !nx.square)) return kOk;
+    bool as_a = true, as_b = true;  // member m of the multiply takes row m of this product, as its left or its right operand, rows in order
+    for (size_t m = 0; m < rows; m++) as_a = as_a && nx.a[m] == st.out[m], as_b = as_b && nx.b[m] == st.out[m];
+    hipStream_t ss = as_a || as_b ? side_stream() : nullptr;
+    if (!ss) return kOk;
+    const size_t kChunks = [] { const char* e = std::getenv("HIPBFV_PIR_CHUNKS"); const long v = e ? atol(e) : 2; return (size_t)(v >= 1 && v <= 64 ? v : 2); }();
+    hipEvent_t ready = nullptr;
+    bool ok = hipEventCreateWithFlags(&ready, hipEventDisableTiming) == hipSuccess && hipEventRecord(ready, s) == hipSuccess &&
+              hipStreamWaitEvent(ss, ready, 0) == hipSuccess;  // the staged ciphertexts and the table were enqueued on `s`
+    if (ready) (void)hipEventDestroy(ready);
+    if (!ok) return kOk;
+    side.base = out;
+    side.rows = rows;
+    int rc = kOk;
+    for (size_t c = 0; c < kChunks && ok; c++) {
+      const size_t r0 = rows * c / kChunks, r1 = rows * (c + 1) / kChunks;
+      if ((rc = ev.dot_plain_tab(staged, (u32)cols, dtab + r0 * cols, (u32)(r1 - r0), (u32)batch, out + r0 * ct_words, ss))) break;
+      hipEvent_t e = nullptr;
+      ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess && hipEventRecord(e, ss) == hipSuccess;
+      if (e) side.done.push_back(e);
+      side.row_end.push_back(r1);
+    }
+    if (rc || !ok) {  // launched chunks finish on the side stream; wait for them here and fail the run
+      (void)hipStreamSynchronize(ss);
+      return fail(rc ? rc : (int)kHipError, "operation failed");
+    }
+    *pipelined = true;
+    return kOk;
+  }
+  // kStepLinComb: out[row] = sum_j cts[j] (.) plain[row][j]: transform the ciphertexts once, accumulate in the transform domain, one inverse per row
+  int run_plain_matrix(size_t si, const Plan::Step& st) {
+    const size_t cols = st.cts.size(), rows = st.node.size();
+    const size_t ct_words = batch * 2 * poly;
+    int rc = kOk;
+    // The ciphertexts first: their copy and transforms need no table, so the device works on them while the host builds the
+    // plaintext table below (65 536 descriptors for a 256 x 256 database: ~0.15 ms during which the device used to idle).
+    // Always a copy: the transform runs in place.  Adjacent operands are copied with one memcpy.
+    u64* ctn = (u64*)pool.acquire(cols * ct_words * sizeof(u64), s);
+    if (!ctn) return fail(kOutOfMemory, "out of device memory");
+    temps.push_back(ctn);
+    if (adjacent(st.cts, ct_words)) {
+      if (hipMemcpyAsync(ctn, sp[st.cts[0]], cols * ct_words * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(kHipError, "copy failed");
+    } else if ((rc = gather(st.cts, ct_words, &ctn))) {
+      return fail(rc, rc == kOutOfMemory ? "descriptor table allocation failed" : "operation failed");
+    }
+    if ((rc = ev.ct_to_ntt(ctn, 2, ctn, cols * batch, s))) return fail(rc, "operation failed");
+    // Then the plaintexts (host work, then one table upload).  Transform-domain arguments are used as they are; coefficient-form ones
+    // are lifted and transformed now (runs of adjacent plaintexts in one call), and an all-zero one raises the
+    // transparent-result failure SEAL's multiply_plain raises.
+    const size_t entries = rows * cols;
+    PlainNttRef* const tab = reinterpret_cast<PlainNttRef*>(stage_begin(entries * sizeof(PlainNttRef)));  // built in place in the pinned arena
+    size_t need_ntt = 0;
+    const Node* const nodes = prog.nodes_.data();  // (locals: the loop runs once per database entry, and its stores could alias members)
+    const ProgramInput* const ins = inputs;
+    const size_t nins = num_inputs;
+    for (size_t e = 0; e < entries; e++) {
+      const Node& nd = nodes[st.plain[e]];
+      if (nd.op == kOpInputPlaintext && nd.arg < nins && ins[nd.arg].kind == 2 && ins[nd.arg].ptr) {  // the common case, kept tight
+        tab[e] = PlainNttRef{ins[nd.arg].ptr, (u64)ins[nd.arg].stride};
+        continue;
+      }
+      PlainVal v;
+      if (const char* m = plain_of(st.plain[e], &v)) return fail(kInvalidArg, m);
+      tab[e] = PlainNttRef{nullptr, 0};  // filled below
+      need_ntt += v.stride ? batch : 1;
+    }
+    if (need_ntt) {
+      u64* pscratch = (u64*)pool.acquire(need_ntt * poly * sizeof(u64), s);
+      if (!pscratch) return fail(kOutOfMemory, "out of device memory");
+      temps.push_back(pscratch);
+      size_t pos = 0;
+      for (size_t e = 0; e < entries;) {
+        if (tab[e].ptr) {
+          e++;
+          continue;
+        }
+        PlainVal v;
+        (void)plain_of(st.plain[e], &v);
+        if (v.stride) {  // per-item plaintexts u64[batch][N]
+          if ((rc = ev.plain_to_ntt(v.ptr, v.stride, pscratch + pos * poly, batch, s, 1))) return fail(rc, "operation failed");
+          tab[e] = PlainNttRef{pscratch + pos * poly, (u64)poly};
+          pos += batch;
+          e++;
+          continue;
+        }
+        size_t run = 1;  // shared plaintexts that sit next to each other in memory: one lift + transform launch for the run
+        while (e + run < entries && !tab[e + run].ptr) {
+          PlainVal w;
+          (void)plain_of(st.plain[e + run], &w);
+          if (w.stride || w.ptr != v.ptr + run * n) break;
+          run++;
+        }
+        if ((rc = ev.plain_to_ntt(v.ptr, n, pscratch + pos * poly, run, s, 2))) return fail(rc, "operation failed");
+        for (size_t r = 0; r < run; r++) tab[e + r] = PlainNttRef{pscratch + (pos + r) * poly, 0};
+        pos += run;
+        e += run;
+      }
+    }
+    const PlainNttRef* dtab = (const PlainNttRef*)stage_commit(reinterpret_cast<const unsigned char*>(tab), entries * sizeof(PlainNttRef));
+    if (!dtab) return fail(kOutOfMemory, "descriptor table allocation failed");
+    const int blk = new_block(rows * ct_words);
+    if (blk < 0) return fail(kOutOfMemory, "out of device memory");
+    u64* out = (u64*)blocks[blk].ptr;
+    for (size_t m = 0; m < rows; m++) bind(st.out[m], blk, out + m * ct_words);
+    bool pipelined = false;
+    if ((rc = side_product(si, st, ctn, dtab, out, &pipelined)) || pipelined) return rc;
+    if ((rc = ev.dot_plain_tab(ctn, (u32)cols, dtab, (u32)rows, (u32)batch, out, s))) return fail(rc, "operation failed");
+    return ev.note_result(out, 2, (u32)K, rows * batch, s);
+  }
+
+  int run_output(size_t, const Plan::Step& st) {
+    if (direct_written[st.out_index]) return kOk;
+    const hipError_t e = hipMemcpyAsync(outputs[st.out_index], sp[st.a[0]], batch * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, s);
+    return e == hipSuccess ? (int)kOk : fail(kHipError, "copy failed");
+  }
+};
 
 int Program::run_plan(Evaluator& ev, size_t batch, const ProgramInput* inputs, size_t num_inputs, const ProgramKeys& keys,
                       u64* const* outputs, size_t num_outputs_given, hipStream_t s,
                       std::string* err) const {
-  const KeySel relin_key = keys.relin_sel();
   auto fail = [&](int code, const char* m) {
     if (err) *err = m;
     return code;
@@ -823,659 +1440,35 @@ int Program::run_plan(Evaluator& ev, size_t batch, const ProgramInput* inputs, s
   // the table-driven kernels put (output, item) on grid z: hipbfv_Program_Run hands over at most this many input sets per call
   // (larger batches are a sequence of runs over offset pointers, capi.cpp)
   if (batch > 32768) return fail(kInvalidArg, "more than 32768 input sets in one scheduled run");
-  Context* ctx = ev.ctx();
-  const DevCtx& h = ctx->host();
-  const size_t n = ctx->n(), K = ctx->K();
-  const size_t poly = K * n;
-  ScratchPool& pool = ev.scratch();
-
-  // ---- slot storage: blocks with reference counts (members of a merged launch share one block; a folded Add shares its producer's) ----
-  struct Block {
-    void* ptr;
-    int refs;
-    bool owned;
-  };
-  std::vector<Block> blocks;
-  std::vector<const u64*> sp(P.nslots, nullptr);
-  std::vector<int> block_of(P.nslots, -1);
-  std::vector<char> direct_written(num_outputs_given, 0);
-  std::vector<void*> temps;  // staging buffers released when the run ends (stream-ordered)
-  struct SideProduct {
-    const u64* base = nullptr;      // the product's output block (rows x batch ciphertexts)
-    size_t rows = 0;
-    std::vector<size_t> row_end;    // chunk c covers rows [row_end[c - 1], row_end[c])
-    std::vector<hipEvent_t> done;   // recorded on the side stream behind chunk c
-    bool noted = false;
-  } side;
-  auto cleanup = [&](int code, const char* m) {
-    // (nothing of the side stream may still run when the run's buffers go back to the pool)
-    for (hipEvent_t e : side.done) {
-      (void)hipEventSynchronize(e);
-      (void)hipEventDestroy(e);
-    }
-    side.done.clear();
-    side.base = nullptr;
-    for (Block& b : blocks)
-      if (b.owned && b.refs > 0) pool.release(b.ptr, s);
-    for (void* t : temps) pool.release(t, s);
-    (void)hipStreamSynchronize(s);  // descriptor tables of this run live in this thread's arena
-    return fail(code, m);
-  };
-  auto new_block = [&](size_t words) -> int {
-    void* p = pool.acquire(words * sizeof(u64), s);
-    if (!p) return -1;
-    blocks.push_back(Block{p, 0, true});
-    return (int)blocks.size() - 1;
-  };
-  auto bind = [&](int slot, int blk, const u64* ptr) {
-    sp[slot] = ptr;
-    block_of[slot] = blk;
-    if (blk >= 0) blocks[blk].refs++;
-  };
-  auto unbind = [&](int slot) {
-    const int blk = block_of[slot];
-    if (blk < 0) return;
-    block_of[slot] = -1;
-    if (--blocks[blk].refs == 0 && blocks[blk].owned) pool.release(blocks[blk].ptr, s);
-  };
-  auto slot_words = [&](int slot) { return batch * (size_t)P.slot_size[slot] * poly; };
-  // a member's own output buffer: the caller's output buffer when the value only feeds an OutputCiphertext node
-  auto alloc_member = [&](int slot) -> u64* {
-    const int d = P.slot_direct[slot];
-    if (d >= 0) {
-      direct_written[d] = 1;
-      blocks.push_back(Block{outputs[d], 0, false});
-      bind(slot, (int)blocks.size() - 1, outputs[d]);
-      return outputs[d];
-    }
-    const int blk = new_block(slot_words(slot));
-    if (blk < 0) return nullptr;
-    bind(slot, blk, (const u64*)blocks[blk].ptr);
-    return (u64*)blocks[blk].ptr;
-  };
-
-  // ---- program arguments ----
-  for (int sl = 0; sl < P.nslots; sl++) {
-    const int arg = P.slot_input[sl];
+  for (int arg : P.slot_input) {
     if (arg < 0) continue;
     if ((size_t)arg >= num_inputs) return fail(kInvalidArg, "input index out of range");
     if (inputs[arg].kind != 0 || !inputs[arg].ptr) return fail(kInvalidArg, "argument is not a ciphertext");
-    sp[sl] = inputs[arg].ptr;
   }
-  // plaintext operands: program arguments as they are, literals uploaded once per run
-  struct PlainVal {
-    const u64* ptr = nullptr;
-    size_t stride = 0;
-    int kind = 1;
-  };
-  std::unordered_map<int, PlainVal> literal_val;
-  if (!P.literal_nodes.empty()) {
-    const std::vector<u64>& kp = ctx->key_primes();
-    u64* dev = (u64*)pool.acquire(P.literal_nodes.size() * n * sizeof(u64), s);
-    if (!dev) return fail(kOutOfMemory, "scratch allocation failed");
-    temps.push_back(dev);
-    std::vector<u64> host(P.literal_nodes.size() * n, 0);
-    for (size_t i = 0; i < P.literal_nodes.size(); i++) {
-      const PlainLiteral& lit = literals_[nodes_[P.literal_nodes[i]].arg];
-      if (lit.n != n || lit.t != h.t || lit.primes.size() != kp.size() || !std::equal(kp.begin(), kp.end(), lit.primes.begin()))
-        return cleanup(kInvalidArg, "plaintext literal was built for different encryption parameters");
-      std::copy(lit.coeffs.begin(), lit.coeffs.end(), host.begin() + i * n);
-      literal_val[P.literal_nodes[i]] = PlainVal{dev + i * n, 0, 1};
-    }
-    // ordered after earlier users of the recycled buffer on this stream; drained so `host` may go out of scope
-    if (hipMemcpyAsync(dev, host.data(), host.size() * sizeof(u64), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return cleanup(kHipError, "copy failed");
-  }
-  auto plain_of = [&](int node, PlainVal* out) -> const char* {
-    const Node& nd = nodes_[node];
-    if (nd.op == kOpLiteralPlaintext) {
-      *out = literal_val[node];
-      return nullptr;
-    }
-    if (nd.arg >= num_inputs) return "input index out of range";
-    const ProgramInput& in = inputs[nd.arg];
-    if ((in.kind != 1 && in.kind != 2) || !in.ptr) return "argument is not a plaintext";
-    *out = PlainVal{in.ptr, in.stride, in.kind};
-    return nullptr;
-  };
-
-  // ---- descriptor tables: pinned host arena -> one device buffer per table ----
-  thread_local TableArenas arenas;
-  TableArena& arena = arenas.next();
-  if (!arena.wait_idle()) return cleanup(kHipError, "event synchronisation failed");
-  arena.used = 0;
-  bool tables_used = false;
-  // reserve the worst case up front so that the host pointers handed out stay valid for the whole run
-  {
-    size_t need = 0;
-    for (const Plan::Step& st : P.steps) {
-      need += (st.node.size() + 1 + st.terms.size() / 8) * sizeof(NaryOut) + 2 * st.terms.size() * sizeof(NaryTerm) + st.plain.size() * sizeof(PlainNttRef) +
-              (st.a.size() + st.b.size() + st.cts.size() + 4) * sizeof(u64*) + 512;
-    }
-    if (!arena.reserve(need + 4096)) return cleanup(kOutOfMemory, "descriptor table allocation failed");
-  }
-  // a table is either copied into the arena (stage_table) or built in place there (stage_begin / stage_commit: the 1 MB
-  // plaintext table of a 256 x 256 lookup is written once instead of built, then copied)
-  auto stage_begin = [&](size_t bytes) -> unsigned char* {
-    const size_t off = (arena.used + 63) & ~(size_t)63;
-    arena.used = off + ((bytes + 7) / 8) * 8;
-    return arena.host + off;
-  };
-  auto stage_commit = [&](const unsigned char* hp, size_t bytes) -> const void* {  // returns the DEVICE copy
-    const size_t words = (bytes + 7) / 8;
-    void* dev = pool.acquire(words * 8, s);
-    if (!dev) return nullptr;
-    temps.push_back(dev);
-    // a kernel, not hipMemcpyAsync: a copy enqueued on the caller's stream waits for the stream to drain on the HOST when that
-    // stream is the null stream (PyTorch's default), and every drained launch queue costs the device idle time
-    if (launch_copy_words((const u64*)hp, (u64*)dev, words, s) != hipSuccess) return nullptr;
-    tables_used = true;
-    return dev;
-  };
-  auto stage_table = [&](const void* src, size_t bytes) -> const void* {
-    unsigned char* hp = stage_begin(bytes);
-    std::memcpy(hp, src, bytes);
-    return stage_commit(hp, bytes);
-  };
-
-  auto galois_key = [&](u32 elt) -> KeySel { return keys.galois_sel(elt); };
-  // rotate `in` by `steps` into `out` following SEAL's rotate_internal: planned over the run's keys, then launched
-  auto rotate = [&](const u64* in, int steps, u64* out) -> int {
-    const RowRotation r = plan_row_rotation((u32)n, steps, [&](u32 elt) { return galois_key(elt).present(); });
-    if (r.kind == RowRotation::kTooLarge) return kInvalidArg;
-    if (r.kind == RowRotation::kNoKey) return kNoKey;
-    if (r.kind == RowRotation::kCopy) {
-      if (in != out && hipMemcpyAsync(out, in, batch * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess) return kHipError;
-      return kOk;
-    }
-    return run_row_rotation(r, in, out, [&](u32 elt, const u64* cur, u64* o) { return ev.apply_galois(cur, elt, galois_key(elt), o, batch, s); });
-  };
-
-  // operands of a merged launch as ONE array: used in place when the members' buffers are adjacent and in order, staged otherwise
-  auto as_array = [&](const std::vector<int>& slots, size_t words_each, const u64** out) -> int {
-    bool adjacent = true;
-    for (size_t m = 1; m < slots.size() && adjacent; m++) adjacent = sp[slots[m]] == sp[slots[0]] + m * words_each;
-    if (adjacent) {
-      *out = sp[slots[0]];
-      return kOk;
-    }
-    std::vector<const u64*> tab(slots.size());
-    for (size_t m = 0; m < slots.size(); m++) tab[m] = sp[slots[m]];
-    const u64* const* dtab = (const u64* const*)stage_table(tab.data(), tab.size() * sizeof(u64*));
-    u64* stage = (u64*)pool.acquire(slots.size() * words_each * sizeof(u64), s);
-    if (!dtab || !stage) return kOutOfMemory;
-    temps.push_back(stage);
-    for (size_t off = 0; off < slots.size(); off += 65535) {
-      const size_t c = std::min<size_t>(65535, slots.size() - off);
-      if (launch_gather_items(dtab + off, stage + off * words_each, words_each, c, s) != hipSuccess) return kHipError;
-    }
-    *out = stage;
-    return kOk;
-  };
-
-  // which sums were folded into their producer at run time: (step, member) -> the slot that carries the result
-  std::vector<std::vector<int>> folded_into(P.steps.size());
-  auto try_fold = [&](const Plan::Step& st, size_t m) -> const u64* {  // the addend to hand to the key-switching kernel, or nullptr
-    if (st.fold.empty() || st.fold[m].other_slot < 0) return nullptr;
-    return sp[st.fold[m].other_slot];
-  };
-  auto mark_folded = [&](const Plan::Step& st, size_t m) {
-    const Plan::Fold& f = st.fold[m];
-    auto& v = folded_into[f.nary_step];
-    if (v.empty()) v.assign(P.steps[f.nary_step].node.size(), -1);
-    v[f.nary_member] = st.out[m];
-  };
-  // the buffer a key-switching member writes when its Add is folded: the sum's own destination
-  auto alloc_for_fold = [&](const Plan::Step& st, size_t m) -> u64* {
-    const Plan::Fold& f = st.fold[m];
-    const int sum_slot = P.steps[f.nary_step].out[f.nary_member];
-    u64* p = alloc_member(sum_slot);  // binds the SUM's slot; the member's own slot aliases it
-    if (!p) return nullptr;
-    bind(st.out[m], block_of[sum_slot], p);
-    return p;
-  };
-
-  const bool small = batch <= merge_max_batch();
-  // HIPBFV_PROGRAM_TRACE=1: drain the stream after every step and print where the time goes (diagnostics only)
-  const char* trace_env = std::getenv("HIPBFV_PROGRAM_TRACE");
-  const bool trace = trace_env && trace_env[0] == '1';
-  auto now_us = [] {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
-  };
-  static const char* step_names[] = {"sum", "plain_matrix", "mul_relin", "multiply", "relinearize", "rotate", "plain_op", "output"};
-  // ---- r06: the plaintext-matrix product on a side stream (examples/pir) ----
-  // The product of a LinComb step streams the database at 6+ TB/s and hardly uses the vector units; the merged multiply +
-  // relinearize that consumes its rows is bound by them.  When that is the very next step, the product runs on a SIDE stream in
-  // row chunks and the main stream takes each chunk's rows through the multiply as soon as its event has passed: chunk c + 1 of
-  // the product streams while chunk c is multiplied (measured with the batch primitives in r05: +2...4 %, same bits --
-  // tools/pir_overlap_probe.py).  Anything else that follows waits for every chunk first (`side_flush`).
-  // OPT-IN (HIPBFV_PIR_OVERLAP=1, read per run): measured inside this executor it LOSES -- examples/pir, 512 x 256 entries at
-  // n = 16384, interleaved on one box (profiles/r06_s11_ab_pir_overlap*.txt): serial 3.93 M entries/s, 2 chunks 3.84 M, 4 chunks
-  // 3.75 M, 8 chunks 3.48 M.  The probe's +2...4 % was against a CHUNKED serial schedule; the executor's serial schedule is one
-  // 512-row product and one 512-member multiply, and next to a concurrent multiply the product stream slows down by more (22.2 ->
-  // 24.6 ms) than the multiply hides.  Kept exercised by tests/test_gpu_program.py.
-  const bool side_enabled = [] {
-    const char* e = std::getenv("HIPBFV_PIR_OVERLAP");
-    return e && e[0] == '1';
-  }();
-  const bool member_tails = [] {  // HIPBFV_NO_MEMBER_TAILS=1: the sums around fused products as launches of their own (the cross-check arm)
-    const char* e = std::getenv("HIPBFV_NO_MEMBER_TAILS");
-    return !(e && e[0] == '1');
-  }();
-  const bool merge_products = [] {  // HIPBFV_NO_MERGED_PRODUCTS=1: merged product launches below merge_max_batch() only (r03 ... r06 s26)
-    const char* e = std::getenv("HIPBFV_NO_MERGED_PRODUCTS");
-    return !(e && e[0] == '1');
-  }() || small;
-  auto side_stream = [&]() -> hipStream_t {
-    thread_local hipStream_t streams[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipStream_t& ss = streams[dev & 15];
-    if (!ss && hipStreamCreateWithFlags(&ss, hipStreamNonBlocking) != hipSuccess) ss = nullptr;
-    return ss;
-  };
-  auto side_drop = [&]() {
-    for (hipEvent_t e : side.done) (void)hipEventDestroy(e);
-    side = SideProduct{};
-  };
-  // the main stream waits for every outstanding chunk (a consumer other than the pipelined multiply, or the end of the run)
-  auto side_flush = [&]() -> int {
-    if (!side.base) return kOk;
-    int rc2 = kOk;
-    for (hipEvent_t e : side.done)
-      if (hipStreamWaitEvent(s, e, 0) != hipSuccess) rc2 = kHipError;
-    if (!rc2 && !side.noted) rc2 = ev.note_result(side.base, 2, (u32)K, side.rows * batch, s);
-    side_drop();
-    return rc2;
-  };
+  PlanRun run(*this, P, ev, batch, inputs, num_inputs, keys, outputs, num_outputs_given, s, err);
+  if (int rc = run.setup()) return rc;
   for (size_t si = 0; si < P.steps.size(); si++) {
     const Plan::Step& st = P.steps[si];
-    const size_t members = st.node.size();
     int rc = kOk;
-    // the one consumer that takes the side product chunk by chunk: a merged multiply + relinearize right behind it (below)
-    bool side_consumer = side.base && st.kind == kStepMulRelin && small && members > 1 && members == side.rows && !st.square;
-    if (side_consumer) {  // member m's left (or right) operand is row m of the product, in place
-      bool as_a = true, as_b = true;
-      for (size_t m = 0; m < members; m++) {
-        as_a = as_a && sp[st.a[m]] == side.base + m * batch * 2 * poly;
-        as_b = as_b && sp[st.b[m]] == side.base + m * batch * 2 * poly;
-      }
-      side_consumer = as_a || as_b;
-    }
-    if (side.base && !side_consumer)
-      if ((rc = side_flush())) return cleanup(rc, "operation failed");
-    const double t_begin = trace ? now_us() : 0.0;
-    struct TraceEnd {
-      bool on;
-      double t0;
-      hipStream_t s;
-      const char* name;
-      size_t members;
-      decltype(now_us)& now;
-      ~TraceEnd() {
-        if (!on) return;
-        const double t1 = now();
-        (void)hipStreamSynchronize(s);
-        const double t2 = now();
-        fprintf(stderr, "[program] %-12s members=%zu host %.0f us, drained after %.0f us\n", name, members, t1 - t0, t2 - t0);
-      }
-    } trace_end{trace, t_begin, s, step_names[st.kind], members, now_us};
+    run.side_consumer = run.takes_side_product(st);
+    if (run.side.base && !run.side_consumer)
+      if ((rc = run.side_flush())) return run.fail(rc, "operation failed");
+    StepTrace trace_end{run.trace, s, kStepNames[st.kind], st.node.size()};
     switch (st.kind) {
-      case kStepNary: {
-        // A long sum (examples/pir: 256 products into one ciphertext) is one output per thread column: its terms are added
-        // one after the other.  Sums of more than kLongSum terms go in two levels -- partial sums of kSumChunk terms, which
-        // are many independent outputs, then the sum of the partials (modular addition is associative: same bits).
-        constexpr u32 kLongSum = 32, kSumChunk = 16;
-        std::vector<NaryOut> pre_outs, outs;
-        std::vector<NaryTerm> pre_terms, terms;
-        u32 max_size = 0, pre_max = 0;
-        const std::vector<int>& fv = folded_into[si];
-        for (size_t m = 0; m < members; m++) {
-          if (!fv.empty() && fv[m] >= 0) continue;  // its producer already added the other operand and wrote this slot
-          const int osl = st.out[m];
-          u64* o = alloc_member(osl);
-          if (!o) return cleanup(kOutOfMemory, "out of device memory");
-          const u32 count = st.first[m + 1] - st.first[m], osz = P.slot_size[osl];
-          NaryOut d;
-          d.out = o;
-          d.first = (u32)terms.size();
-          d.size = osz;
-          d.pad = 0;
-          max_size = std::max(max_size, osz);
-          if (count > kLongSum) {
-            const u32 chunks = (count + kSumChunk - 1) / kSumChunk;
-            u64* part = (u64*)pool.acquire((size_t)chunks * batch * osz * poly * sizeof(u64), s);
-            if (!part) return cleanup(kOutOfMemory, "out of device memory");
-            temps.push_back(part);
-            pre_max = std::max(pre_max, osz);
-            for (u32 c = 0; c < chunks; c++) {
-              NaryOut pd;
-              pd.out = part + (size_t)c * batch * osz * poly;
-              pd.first = (u32)pre_terms.size();
-              pd.count = std::min(kSumChunk, count - c * kSumChunk);
-              pd.size = osz;
-              pd.pad = 0;
-              for (u32 t = 0; t < pd.count; t++) {
-                const Term& tm = st.terms[st.first[m] + c * kSumChunk + t];
-                pre_terms.push_back(NaryTerm{sp[tm.slot], P.slot_size[tm.slot], tm.sign});
-              }
-              pre_outs.push_back(pd);
-              terms.push_back(NaryTerm{pd.out, osz, 1});
-            }
-            d.count = chunks;
-          } else {
-            d.count = count;
-            for (u32 t = st.first[m]; t < st.first[m + 1]; t++) terms.push_back(NaryTerm{sp[st.terms[t].slot], P.slot_size[st.terms[t].slot], st.terms[t].sign});
-          }
-          outs.push_back(d);
-        }
-        if (outs.empty()) break;
-        if (!pre_outs.empty()) {
-          const NaryOut* dpo = (const NaryOut*)stage_table(pre_outs.data(), pre_outs.size() * sizeof(NaryOut));
-          const NaryTerm* dpt = (const NaryTerm*)stage_table(pre_terms.data(), pre_terms.size() * sizeof(NaryTerm));
-          if (!dpo || !dpt) return cleanup(kOutOfMemory, "descriptor table allocation failed");
-          ev.profiler().begin(kKernEltwise, pre_outs.size() * batch * pre_max * K, s);
-          const hipError_t e = launch_nary_sum(ctx->dev(), (u32)n, (u32)K, dpo, dpt, (u32)pre_outs.size(), pre_max, (u32)batch, s);
-          ev.profiler().end(s);
-          if (e != hipSuccess) return cleanup(kHipError, "operation failed");
-        }
-        const NaryOut* douts = (const NaryOut*)stage_table(outs.data(), outs.size() * sizeof(NaryOut));
-        const NaryTerm* dterms = (const NaryTerm*)stage_table(terms.data(), terms.size() * sizeof(NaryTerm));
-        if (!douts || !dterms) return cleanup(kOutOfMemory, "descriptor table allocation failed");
-        ev.profiler().begin(kKernEltwise, outs.size() * batch * max_size * K, s);
-        const hipError_t e = launch_nary_sum(ctx->dev(), (u32)n, (u32)K, douts, dterms, (u32)outs.size(), max_size, (u32)batch, s);
-        ev.profiler().end(s);
-        if (e != hipSuccess) return cleanup(kHipError, "operation failed");
-        rc = ev.note_nary(douts, (u32)outs.size(), (u32)batch, s);
-        break;
-      }
+      case kStepNary: rc = run.run_sum(si, st); break;
       case kStepMulRelin:
       case kStepRelin:
-      case kStepGalois: {
-        const bool is_mul = st.kind == kStepMulRelin, is_rot = st.kind == kStepGalois;
-        if (!is_rot && !relin_key.present() && !(st.kind == kStepRelin && st.out_size == 2)) return cleanup(kNoKey, "operation failed");
-        u32 elt = 0;
-        KeySel gkey;
-        if (is_rot) {
-          if (!ctx->batching()) return cleanup(kUnsupported, "encryption parameters do not support batching");
-          elt = st.swap ? 2 * (u32)n - 1 : (st.rot_steps ? ev.galois_elt_from_step(st.rot_steps) : 0);
-          if (st.swap || st.rot_steps) {
-            if (!elt) return cleanup(kInvalidArg, "operation failed");
-            gkey = galois_key(elt);
-            if (st.swap && !gkey.present()) return cleanup(kNoKey, "Galois key for the column rotation is missing");
-          }
-        }
-        const u32 in_size = st.kind == kStepRelin ? st.out_size : 2;
-        const size_t in_words = batch * in_size * poly, out_words = batch * 2 * poly;
-        const bool direct_ks = is_mul || (st.kind == kStepRelin && in_size == 3) || (is_rot && gkey.present());
-        // r06: products with a linear fold (Plan::LinFold) or a caller's buffer to write take each member's destination, multiplier and
-        // signed addend from a table in their last kernel (kernels.hpp MemberTail): the sums around the products and the copies into the
-        // outputs cost no pass of their own (examples/chi_sq: 2 x^2, 2 y^2, 4 n0 n2 - n1^2, x y).  Members [m0, m1) in one launch.
-        auto has_lin = [&](size_t m) { return !st.lin.empty() && st.lin[m].mult != 0; };
-        auto tail_launch = [&](size_t m0, size_t m1) -> int {
-          const size_t cnt = m1 - m0;
-          std::vector<MemberHead> heads(cnt);  // the operands where they are (no gather into one array)
-          for (size_t m = m0; m < m1; m++) heads[m - m0] = MemberHead{sp[st.a[m]], sp[st.square ? st.a[m] : st.b[m]]};
-          std::vector<MemberTail> tab(cnt);
-          for (size_t m = m0; m < m1; m++) {
-            const Plan::LinFold* lf = has_lin(m) ? &st.lin[m] : nullptr;
-            const int target = lf ? P.steps[lf->nary_step].out[lf->nary_member] : st.out[m];
-            u64* o = alloc_member(target);  // the caller's buffer when the value is a program output
-            if (!o) return (int)kOutOfMemory;
-            if (lf) {
-              bind(st.out[m], block_of[target], o);  // (nothing reads the bare product: every use of it is inside the sum)
-              auto& v = folded_into[lf->nary_step];
-              if (v.empty()) v.assign(P.steps[lf->nary_step].node.size(), -1);
-              v[lf->nary_member] = st.out[m];
-            }
-            const bool has_other = lf && lf->other_slot >= 0;
-            tab[m - m0] = MemberTail{o, has_other ? sp[lf->other_slot] : nullptr, lf ? (u32)lf->mult : 1u, has_other ? lf->sign : 0};
-          }
-          const MemberTail* dtab = (const MemberTail*)stage_table(tab.data(), tab.size() * sizeof(MemberTail));
-          const MemberHead* dheads = (const MemberHead*)stage_table(heads.data(), heads.size() * sizeof(MemberHead));
-          if (!dtab || !dheads) return (int)kOutOfMemory;
-          KeySel sub = relin_key;  // (member-major item numbering: member m0's items start at m0 * batch)
-          sub.first = relin_key.first + m0 * batch;
-          int r = ev.multiply_relin(nullptr, nullptr, sub, nullptr, cnt * batch, s, nullptr, dtab, (u32)batch, dheads, st.square);
-          for (size_t m = 0; m < cnt && !r; m++) r = ev.note_result(tab[m].out, 2, (u32)K, batch, s);
-          return r;
-        };
-        const bool tails_on = is_mul && !side_consumer && member_tails;
-        // With both tables a merged launch costs nothing to set up (operands and results stay where they are), so the ready products
-        // of a round run as ONE launch sequence at every batch size, not only below merge_max_batch(): examples/chi_sq at one GPU's
-        // share of 128 sets runs 384 + 256 + 128 items instead of six launches of 128.
-        if (tails_on && members > 1 && members <= 64 && merge_products && ev.member_tail_ok(members * batch)) {
-          rc = tail_launch(0, members);
-          break;
-        }
-        if (small && members > 1 && direct_ks) {
-          // ONE launch sequence over members x batch ciphertexts
-          const u64 *A = nullptr, *B2 = nullptr;
-          if ((rc = as_array(st.a, in_words, &A))) return cleanup(rc, "operation failed");
-          if (is_mul && !st.square && (rc = as_array(st.b, in_words, &B2))) return cleanup(rc, "operation failed");
-          const int blk = new_block(members * out_words);
-          if (blk < 0) return cleanup(kOutOfMemory, "out of device memory");
-          u64* out = (u64*)blocks[blk].ptr;
-          for (size_t m = 0; m < members; m++) bind(st.out[m], blk, out + m * out_words);
-          const size_t count = members * batch;
-          if (side_consumer && is_mul) {
-            // rows of the side-stream product, chunk by chunk: the main stream waits for chunk c's event only, so the product's
-            // later chunks stream while this one is multiplied
-            size_t r0 = 0;
-            for (size_t c = 0; c < side.done.size() && !rc; c++) {
-              const size_t r1 = side.row_end[c];
-              if (hipStreamWaitEvent(s, side.done[c], 0) != hipSuccess) rc = kHipError;
-              KeySel sub = relin_key;
-              sub.first = relin_key.first + r0 * batch;
-              if (!rc) rc = ev.multiply_relin(A + r0 * batch * 2 * poly, B2 + r0 * batch * 2 * poly, sub, out + r0 * batch * 2 * poly, (r1 - r0) * batch, s);
-              r0 = r1;
-            }
-            if (!rc) rc = ev.note_result(side.base, 2, (u32)K, side.rows * batch, s);
-            side.noted = true;
-            side_drop();
-            break;
-          }
-          rc = is_mul ? ev.multiply_relin(A, st.square ? A : B2, relin_key, out, count, s)
-             : is_rot ? ev.apply_galois(A, elt, gkey, out, count, s)
-                      : ev.relinearize(A, relin_key, out, count, s);
-          break;
-        }
-        for (size_t m = 0; m < members && !rc; m++) {
-          if (tails_on && has_lin(m) && !(small && members > 1) && ev.member_tail_ok(batch)) {  // (a merged launch has no tables: whole or not at all)
-            rc = tail_launch(m, m + 1);
-            continue;
-          }
-          const u64* addend = direct_ks ? try_fold(st, m) : nullptr;
-          u64* out = addend ? alloc_for_fold(st, m) : alloc_member(st.out[m]);
-          if (!out) return cleanup(kOutOfMemory, "out of device memory");
-          const u64* a = sp[st.a[m]];
-          if (is_mul)
-            rc = ev.multiply_relin(a, sp[st.b[m]], relin_key, out, batch, s, addend);
-          else if (st.kind == kStepRelin && in_size == 2)
-            rc = hipMemcpyAsync(out, a, out_words * sizeof(u64), hipMemcpyDeviceToDevice, s) == hipSuccess ? (int)kOk : (int)kHipError;
-          else if (st.kind == kStepRelin)
-            rc = ev.relinearize(a, relin_key, out, batch, s, addend);
-          else if (gkey.present())
-            rc = ev.apply_galois(a, elt, gkey, out, batch, s, addend);
-          else
-            rc = rotate(a, st.rot_steps, out);
-          if (addend && !rc) mark_folded(st, m);
-        }
-        break;
-      }
-      case kStepMultiply: {
-        u64* out = alloc_member(st.out[0]);
-        if (!out) return cleanup(kOutOfMemory, "out of device memory");
-        rc = ev.multiply(sp[st.a[0]], P.slot_size[st.a[0]], sp[st.b[0]], P.slot_size[st.b[0]], out, batch, s);
-        break;
-      }
-      case kStepPlainOp: {
-        PlainVal pv;
-        if (const char* m = plain_of(st.plain[0], &pv)) return cleanup(kInvalidArg, m);
-        const u32 sz = P.slot_size[st.a[0]];
-        if (pv.kind == 2 && st.plain_op != kOpMultiplyPlaintext)
-          return cleanup(kInvalidArg, "a transform-domain plaintext argument can only be an operand of MultiplyPlaintext");
-        u64* out = alloc_member(st.out[0]);
-        if (!out) return cleanup(kOutOfMemory, "out of device memory");
-        if (st.plain_op == kOpAddPlaintext)
-          rc = ev.add_plain(sp[st.a[0]], sz, pv.ptr, pv.stride, out, batch, s);
-        else if (st.plain_op == kOpSubPlaintext)
-          rc = ev.sub_plain(sp[st.a[0]], sz, pv.ptr, pv.stride, out, batch, s);
-        else if (pv.kind == 1)
-          rc = ev.multiply_plain(sp[st.a[0]], sz, pv.ptr, pv.stride, out, batch, s);
-        else
-          rc = ev.multiply_plain_ntt(sp[st.a[0]], sz, pv.ptr, pv.stride, out, batch, s);
-        break;
-      }
-      case kStepLinComb: {
-        // out[row] = sum_j cts[j] (.) plain[row][j]: transform the ciphertexts once, accumulate in the transform domain, one inverse per row
-        const size_t cols = st.cts.size(), rows = members;
-        const size_t ct_words = batch * 2 * poly;
-        // The ciphertexts first: their copy and transforms need no table, so the device works on them while the host builds the
-        // plaintext table below (65 536 descriptors for a 256 x 256 database: ~0.15 ms during which the device used to idle).
-        const u64* staged = nullptr;
-        {
-          // always a copy: the transform runs in place.  Adjacent operands are copied with one memcpy.
-          bool adjacent = true;
-          for (size_t j = 1; j < cols && adjacent; j++) adjacent = sp[st.cts[j]] == sp[st.cts[0]] + j * ct_words;
-          u64* ctn = (u64*)pool.acquire(cols * ct_words * sizeof(u64), s);
-          if (!ctn) return cleanup(kOutOfMemory, "out of device memory");
-          temps.push_back(ctn);
-          if (adjacent) {
-            if (hipMemcpyAsync(ctn, sp[st.cts[0]], cols * ct_words * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess) return cleanup(kHipError, "copy failed");
-          } else {
-            std::vector<const u64*> ctab(cols);
-            for (size_t j = 0; j < cols; j++) ctab[j] = sp[st.cts[j]];
-            const u64* const* dctab = (const u64* const*)stage_table(ctab.data(), cols * sizeof(u64*));
-            if (!dctab) return cleanup(kOutOfMemory, "descriptor table allocation failed");
-            for (size_t off = 0; off < cols; off += 65535) {
-              const size_t c = std::min<size_t>(65535, cols - off);
-              if (launch_gather_items(dctab + off, ctn + off * ct_words, ct_words, c, s) != hipSuccess) return cleanup(kHipError, "operation failed");
-            }
-          }
-          if ((rc = ev.ct_to_ntt(ctn, 2, ctn, cols * batch, s))) return cleanup(rc, "operation failed");
-          staged = ctn;
-        }
-        // Then the plaintexts (host work, then one table upload).  Transform-domain arguments are used as they are; coefficient-form ones
-        // are lifted and transformed now (runs of adjacent plaintexts in one call), and an all-zero one raises the
-        // transparent-result failure SEAL's multiply_plain raises.
-        const size_t entries = rows * cols;
-        PlainNttRef* const tab = reinterpret_cast<PlainNttRef*>(stage_begin(entries * sizeof(PlainNttRef)));  // built in place in the pinned arena
-        size_t need_ntt = 0;
-        for (size_t e = 0; e < entries; e++) {
-          const Node& nd = nodes_[st.plain[e]];
-          if (nd.op == kOpInputPlaintext && nd.arg < num_inputs && inputs[nd.arg].kind == 2 && inputs[nd.arg].ptr) {  // the common case, kept tight
-            tab[e] = PlainNttRef{inputs[nd.arg].ptr, (u64)inputs[nd.arg].stride};
-            continue;
-          }
-          PlainVal v;
-          if (const char* m = plain_of(st.plain[e], &v)) return cleanup(kInvalidArg, m);
-          tab[e] = PlainNttRef{nullptr, 0};  // filled below
-          need_ntt += v.stride ? batch : 1;
-        }
-        if (need_ntt) {
-          u64* pscratch = (u64*)pool.acquire(need_ntt * poly * sizeof(u64), s);
-          if (!pscratch) return cleanup(kOutOfMemory, "out of device memory");
-          temps.push_back(pscratch);
-          size_t pos = 0;
-          for (size_t e = 0; e < entries;) {
-            if (tab[e].ptr) {
-              e++;
-              continue;
-            }
-            PlainVal v;
-            (void)plain_of(st.plain[e], &v);
-            if (v.stride) {  // per-item plaintexts u64[batch][N]
-              if ((rc = ev.plain_to_ntt(v.ptr, v.stride, pscratch + pos * poly, batch, s, 1))) return cleanup(rc, "operation failed");
-              tab[e] = PlainNttRef{pscratch + pos * poly, (u64)poly};
-              pos += batch;
-              e++;
-              continue;
-            }
-            size_t run = 1;  // shared plaintexts that sit next to each other in memory: one lift + transform launch for the run
-            while (e + run < entries && !tab[e + run].ptr) {
-              PlainVal w;
-              (void)plain_of(st.plain[e + run], &w);
-              if (w.stride || w.ptr != v.ptr + run * n) break;
-              run++;
-            }
-            if ((rc = ev.plain_to_ntt(v.ptr, n, pscratch + pos * poly, run, s, 2))) return cleanup(rc, "operation failed");
-            for (size_t r = 0; r < run; r++) tab[e + r] = PlainNttRef{pscratch + (pos + r) * poly, 0};
-            pos += run;
-            e += run;
-          }
-        }
-        const PlainNttRef* dtab = (const PlainNttRef*)stage_commit(reinterpret_cast<const unsigned char*>(tab), entries * sizeof(PlainNttRef));
-        if (!dtab) return cleanup(kOutOfMemory, "descriptor table allocation failed");
-        const int blk = new_block(rows * ct_words);
-        if (blk < 0) return cleanup(kOutOfMemory, "out of device memory");
-        u64* out = (u64*)blocks[blk].ptr;
-        for (size_t m = 0; m < rows; m++) bind(st.out[m], blk, out + m * ct_words);
-        {
-          // on the side stream, in row chunks, when the next step is the merged multiply + relinearize of these rows
-          bool pipelined = false;
-          if (side_enabled && small && rows >= 64 && si + 1 < P.steps.size()) {
-            const Plan::Step& nx = P.steps[si + 1];
-            bool consumes = nx.kind == kStepMulRelin && nx.node.size() == rows && !nx.square;
-            if (consumes) {  // member m of the multiply takes row m of this product, as its left or its right operand, rows in order
-              bool as_a = true, as_b = true;
-              for (size_t m = 0; m < rows; m++) as_a = as_a && nx.a[m] == st.out[m], as_b = as_b && nx.b[m] == st.out[m];
-              consumes = as_a || as_b;
-            }
-            hipStream_t ss = consumes ? side_stream() : nullptr;
-            if (ss) {
-              const size_t kChunks = [] { const char* e = std::getenv("HIPBFV_PIR_CHUNKS"); const long v = e ? atol(e) : 2; return (size_t)(v >= 1 && v <= 64 ? v : 2); }();
-              hipEvent_t ready = nullptr;
-              bool ok = hipEventCreateWithFlags(&ready, hipEventDisableTiming) == hipSuccess && hipEventRecord(ready, s) == hipSuccess &&
-                        hipStreamWaitEvent(ss, ready, 0) == hipSuccess;  // the staged ciphertexts and the table were enqueued on `s`
-              if (ready) (void)hipEventDestroy(ready);
-              if (ok) {
-                side.base = out;
-                side.rows = rows;
-                for (size_t c = 0; c < kChunks && ok; c++) {
-                  const size_t r0 = rows * c / kChunks, r1 = rows * (c + 1) / kChunks;
-                  if ((rc = ev.dot_plain_tab(staged, (u32)cols, dtab + r0 * cols, (u32)(r1 - r0), (u32)batch, out + r0 * ct_words, ss))) break;
-                  hipEvent_t e = nullptr;
-                  ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess && hipEventRecord(e, ss) == hipSuccess;
-                  if (e) side.done.push_back(e);
-                  side.row_end.push_back(r1);
-                }
-                if (rc || !ok) {  // launched chunks finish on the side stream; wait for them here and fail the run
-                  (void)hipStreamSynchronize(ss);
-                  return cleanup(rc ? rc : (int)kHipError, "operation failed");
-                }
-                pipelined = true;
-              }
-            }
-          }
-          if (pipelined) break;
-        }
-        if ((rc = ev.dot_plain_tab(staged, (u32)cols, dtab, (u32)rows, (u32)batch, out, s))) return cleanup(rc, "operation failed");
-        rc = ev.note_result(out, 2, (u32)K, rows * batch, s);
-        break;
-      }
-      case kStepOutput: {
-        if (direct_written[st.out_index]) break;
-        if (hipMemcpyAsync(outputs[st.out_index], sp[st.a[0]], batch * 2 * poly * sizeof(u64), hipMemcpyDeviceToDevice, s) != hipSuccess)
-          return cleanup(kHipError, "copy failed");
-        break;
-      }
-      default:
-        return cleanup(kInvalidArg, "unsupported operation");
+      case kStepGalois: rc = run.run_key_switch(si, st); break;
+      case kStepMultiply: rc = run.run_multiply(si, st); break;
+      case kStepPlainOp: rc = run.run_plain_op(si, st); break;
+      case kStepLinComb: rc = run.run_plain_matrix(si, st); break;
+      case kStepOutput: rc = run.run_output(si, st); break;
+      default: return run.fail(kInvalidArg, "unsupported operation");
     }
-    if (rc) return cleanup(rc, st.kind == kStepMulRelin ? "multiply+relinearize failed" : "operation failed");
-    for (int sl : st.release) unbind(sl);
+    if (rc) return run.fail(rc, st.kind == kStepMulRelin ? "multiply+relinearize failed" : "operation failed");
+    for (int sl : st.release) run.unbind(sl);
   }
-  if (int rc2 = side_flush()) return cleanup(rc2, "operation failed");
-  for (Block& b : blocks)
-    if (b.owned && b.refs > 0) pool.release(b.ptr, s);
-  for (void* t : temps) pool.release(t, s);
-  // the descriptor tables were copied from this thread's pinned arena: an event behind the copies guards its reuse (two runs from
-  // now: TableArenas) -- the run itself does not wait for the device
-  if (tables_used && !arena.mark(s)) return fail(kHipError, "stream synchronisation failed");
-  return kOk;
+  return run.finish();
 }
 
 }  // namespace hipbfv
