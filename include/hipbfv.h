@@ -445,6 +445,34 @@ long hipbfv_batch_multiply_sum_shared(void *evaluator, const uint64_t *a, void *
                                       uint64_t *out3, uint64_t groups, uint64_t terms, void *stream);
 long hipbfv_batch_multiply_sum_relin_shared(void *evaluator, const uint64_t *a, void *multiplicand, const uint32_t *b_index,
                                             uint64_t index_len, void *relin_keys, uint64_t *out2, uint64_t groups, uint64_t terms, void *stream);
+/* Products of TWO prepared operands: both operands recur -- the ciphertext matrix product C = A B (C[i][j] = sum_t A[i][t] * B[t][j]:
+ * every A[i][t] is used by n groups, every B[t][j] by m), a Gram matrix, all-pairs scoring of two ciphertext sets.  ma and mb are
+ * ordinary multiplicand objects (hipbfv_Multiplicand_Create; ma == mb is allowed): each distinct ciphertext was extended and
+ * forward-transformed once when its object was made, and these calls extend and transform nothing.
+ *  - a_index and b_index are HOST arrays of `index_len` entries each, read before the call returns: item i multiplies prepared
+ *    ciphertext a_index[i % index_len] of ma by prepared ciphertext b_index[i % index_len] of mb; in the sum forms i = g * terms + t.
+ *  - Bits: every output is, word for word, the counterpart call (hipbfv_batch_multiply, hipbfv_batch_multiply_relin,
+ *    hipbfv_batch_multiply_sum, hipbfv_batch_multiply_sum_relin) on the two gathered arrays; an item whose two operands are the same
+ *    prepared ciphertext has the words of the product of that ciphertext with itself.
+ *  - Path: the counterpart's for the same item count.  Where that is the split kernels (and both objects hold transformed rows)
+ *    there is no head launch at all: one middle kernel reads both operands' rows, forms the three products and runs the inverse
+ *    transforms; the tail, the summing tail and the fused relinearization are the counterpart's.  Elsewhere (N < 4096, N = 32768, a
+ *    few items) both operands of a chunk are gathered from the objects' copies and the counterpart's launches run.
+ *  - Refusals, all before anything is launched, copied or written: a NULL evaluator, ma, mb, a_index, b_index or output, or a handle
+ *    that is not a multiplicand, is HIPBFV_E_POINTER; index_len == 0, terms == 0 or an index >= its object's count is
+ *    HIPBFV_E_INVALIDARG (hipbfv_last_error names the first such item as "item <i>" and the operand as a_index or b_index); so is an
+ *    object made for another context; a missing relinearization key fails as in the counterpart.  The objects own the operands, so
+ *    an output cannot alias them.  count == 0 / groups == 0 returns HIPBFV_S_OK with no launch.
+ *  - Transparent results are recorded as in the counterparts: by item number, by GROUP number in the sum forms. */
+long hipbfv_batch_multiply_prepared(void *evaluator, void *ma, const uint32_t *a_index, void *mb, const uint32_t *b_index, uint64_t index_len,
+                                    uint64_t *out3, uint64_t count, void *stream);
+long hipbfv_batch_multiply_relin_prepared(void *evaluator, void *ma, const uint32_t *a_index, void *mb, const uint32_t *b_index,
+                                          uint64_t index_len, void *relin_keys, uint64_t *out2, uint64_t count, void *stream);
+long hipbfv_batch_multiply_sum_prepared(void *evaluator, void *ma, const uint32_t *a_index, void *mb, const uint32_t *b_index,
+                                        uint64_t index_len, uint64_t *out3, uint64_t groups, uint64_t terms, void *stream);
+long hipbfv_batch_multiply_sum_relin_prepared(void *evaluator, void *ma, const uint32_t *a_index, void *mb, const uint32_t *b_index,
+                                              uint64_t index_len, void *relin_keys, uint64_t *out2, uint64_t groups, uint64_t terms,
+                                              void *stream);
 long hipbfv_batch_apply_galois_keys(void *evaluator, const uint64_t *ct2, uint32_t galois_elt, void *const *galois_key_sets,
                                     uint64_t num_key_sets, const uint32_t *key_index, uint64_t *out2, uint64_t count,
                                     void *stream);

@@ -714,6 +714,58 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
                                  uint64_t* out2, uint64_t groups, uint64_t terms, void* stream = nullptr) const {
     check(hipbfv_batch_multiply_sum_relin_shared(h_, a, m.get_handle(), b_index.data(), b_index.size(), rk.get_handle(), out2, groups, terms, stream));
   }
+  // Products of two prepared operands (hipbfv.h): item i multiplies prepared ciphertext a_index[i % L] of ma by b_index[i % L] of mb,
+  // L = a_index.size() = b_index.size() (in the sum forms i = g * terms + t); ma may be mb.  No head and no forward transform on the
+  // split path; the words of the counterpart call on the two gathered arrays.
+  static void pair_index_ok(const std::vector<uint32_t>& a_index, const std::vector<uint32_t>& b_index) {
+    if (a_index.size() != b_index.size()) throw Error(Error::InvalidArgument, HIPBFV_E_INVALIDARG, "a_index and b_index differ in length");
+  }
+  void multiply_prepared(const Multiplicand& ma, const std::vector<uint32_t>& a_index, const Multiplicand& mb, const std::vector<uint32_t>& b_index,
+                         uint64_t* out3, uint64_t count, void* stream = nullptr) const {
+    pair_index_ok(a_index, b_index);
+    check(hipbfv_batch_multiply_prepared(h_, ma.get_handle(), a_index.data(), mb.get_handle(), b_index.data(), a_index.size(), out3, count, stream));
+  }
+  void multiply_relin_prepared(const Multiplicand& ma, const std::vector<uint32_t>& a_index, const Multiplicand& mb, const std::vector<uint32_t>& b_index,
+                               const RelinearizationKeys& rk, uint64_t* out2, uint64_t count, void* stream = nullptr) const {
+    pair_index_ok(a_index, b_index);
+    check(hipbfv_batch_multiply_relin_prepared(h_, ma.get_handle(), a_index.data(), mb.get_handle(), b_index.data(), a_index.size(), rk.get_handle(), out2,
+                                               count, stream));
+  }
+  void multiply_sum_prepared(const Multiplicand& ma, const std::vector<uint32_t>& a_index, const Multiplicand& mb, const std::vector<uint32_t>& b_index,
+                             uint64_t* out3, uint64_t groups, uint64_t terms, void* stream = nullptr) const {
+    pair_index_ok(a_index, b_index);
+    check(hipbfv_batch_multiply_sum_prepared(h_, ma.get_handle(), a_index.data(), mb.get_handle(), b_index.data(), a_index.size(), out3, groups, terms,
+                                             stream));
+  }
+  void multiply_sum_relin_prepared(const Multiplicand& ma, const std::vector<uint32_t>& a_index, const Multiplicand& mb,
+                                   const std::vector<uint32_t>& b_index, const RelinearizationKeys& rk, uint64_t* out2, uint64_t groups, uint64_t terms,
+                                   void* stream = nullptr) const {
+    pair_index_ok(a_index, b_index);
+    check(hipbfv_batch_multiply_sum_relin_prepared(h_, ma.get_handle(), a_index.data(), mb.get_handle(), b_index.data(), a_index.size(), rk.get_handle(),
+                                                   out2, groups, terms, stream));
+  }
+  // The index tables of C = A B over prepared operands, A row-major m x k and B row-major k x n: item (i * n + j) * k + t multiplies
+  // A[i][t] (prepared ciphertext i * k + t) by B[t][j] (prepared ciphertext t * n + j); groups = m * n, terms = k in the sum forms.
+  static void matrix_product_index(uint32_t m, uint32_t k, uint32_t n, std::vector<uint32_t>& a_index, std::vector<uint32_t>& b_index) {
+    a_index.clear();
+    b_index.clear();
+    for (uint32_t i = 0; i < m; i++)
+      for (uint32_t j = 0; j < n; j++)
+        for (uint32_t t = 0; t < k; t++) {
+          a_index.push_back(i * k + t);
+          b_index.push_back(t * n + j);
+        }
+  }
+  // C = A B: out = u64[m * n][3 or 2][K][N] row-major; rk != nullptr: one key switch per entry (out2), otherwise size-3 sums (out3)
+  void matrix_product(const Multiplicand& ma, const Multiplicand& mb, uint32_t m, uint32_t k, uint32_t n, const RelinearizationKeys* rk, uint64_t* out,
+                      void* stream = nullptr) const {
+    std::vector<uint32_t> a_index, b_index;
+    matrix_product_index(m, k, n, a_index, b_index);
+    if (rk)
+      multiply_sum_relin_prepared(ma, a_index, mb, b_index, *rk, out, (uint64_t)m * n, k, stream);
+    else
+      multiply_sum_prepared(ma, a_index, mb, b_index, out, (uint64_t)m * n, k, stream);
+  }
   // ... group g through keys[key_index[g]]; an entry of `keys` that no group names may be nullptr
   void multiply_sum_relin_keys(const uint64_t* a, const uint64_t* b, const std::vector<const RelinearizationKeys*>& keys,
                                const std::vector<uint32_t>& key_index, uint64_t* out2, uint64_t terms, void* stream = nullptr) const {

@@ -245,6 +245,67 @@ impl<'e> BatchEvaluator<'e> {
                                                             self.stream)
         })
     }
+    // ---- products of two prepared operands: no head, one middle kernel over both operands' rows (include/hipbfv.h) ----
+    // Item i multiplies prepared ciphertext `a_index[i % L]` of `ma` by `b_index[i % L]` of `mb`, L = a_index.len() = b_index.len();
+    // in the sum forms i = g * terms + t.  `ma` may be `mb`.
+    fn pair_index_ok(a_index: &[u32], b_index: &[u32]) -> Result<()> {
+        if a_index.len() != b_index.len() {
+            return Err(crate::Error::InvalidArgument(format!("{} a indices and {} b indices", a_index.len(), b_index.len())));
+        }
+        Ok(())
+    }
+    pub fn multiply_prepared(&self, ma: &Multiplicand, a_index: &[u32], mb: &Multiplicand, b_index: &[u32], out3: DeviceBatch) -> Result<()> {
+        Self::pair_index_ok(a_index, b_index)?;
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_prepared(self.h(), ma.h, a_index.as_ptr(), mb.h, b_index.as_ptr(), a_index.len() as u64, out3.ptr, out3.count, self.stream)
+        })
+    }
+    pub fn multiply_relin_prepared(&self, ma: &Multiplicand, a_index: &[u32], mb: &Multiplicand, b_index: &[u32], rk: &RelinearizationKeys,
+                                   out: DeviceBatch) -> Result<()> {
+        Self::pair_index_ok(a_index, b_index)?;
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_relin_prepared(self.h(), ma.h, a_index.as_ptr(), mb.h, b_index.as_ptr(), a_index.len() as u64, rk.get_handle(), out.ptr,
+                                                          out.count, self.stream)
+        })
+    }
+    pub fn multiply_sum_prepared(&self, ma: &Multiplicand, a_index: &[u32], mb: &Multiplicand, b_index: &[u32], terms: u64, out3: DeviceBatch) -> Result<()> {
+        Self::pair_index_ok(a_index, b_index)?;
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_sum_prepared(self.h(), ma.h, a_index.as_ptr(), mb.h, b_index.as_ptr(), a_index.len() as u64, out3.ptr, out3.count, terms,
+                                                        self.stream)
+        })
+    }
+    pub fn multiply_sum_relin_prepared(&self, ma: &Multiplicand, a_index: &[u32], mb: &Multiplicand, b_index: &[u32], terms: u64, rk: &RelinearizationKeys,
+                                       out: DeviceBatch) -> Result<()> {
+        Self::pair_index_ok(a_index, b_index)?;
+        check(unsafe {
+            bindgen::hipbfv_batch_multiply_sum_relin_prepared(self.h(), ma.h, a_index.as_ptr(), mb.h, b_index.as_ptr(), a_index.len() as u64, rk.get_handle(),
+                                                              out.ptr, out.count, terms, self.stream)
+        })
+    }
+    /// The index tables of C = A B over prepared operands, A row-major m x k and B row-major k x n: item (i * n + j) * k + t multiplies
+    /// A[i][t] (prepared ciphertext i * k + t) by B[t][j] (prepared ciphertext t * n + j); groups = m * n, terms = k.
+    pub fn matrix_product_index(m: u32, k: u32, n: u32) -> (Vec<u32>, Vec<u32>) {
+        let mut a_index = Vec::with_capacity((m * n * k) as usize);
+        let mut b_index = Vec::with_capacity((m * n * k) as usize);
+        for i in 0..m {
+            for j in 0..n {
+                for t in 0..k {
+                    a_index.push(i * k + t);
+                    b_index.push(t * n + j);
+                }
+            }
+        }
+        (a_index, b_index)
+    }
+    /// C = A B, `out` = m * n ciphertexts row-major: size 2 with one key switch per entry when `rk` is given, size-3 sums otherwise.
+    pub fn matrix_product(&self, ma: &Multiplicand, mb: &Multiplicand, m: u32, k: u32, n: u32, rk: Option<&RelinearizationKeys>, out: DeviceBatch) -> Result<()> {
+        let (a_index, b_index) = Self::matrix_product_index(m, k, n);
+        match rk {
+            Some(rk) => self.multiply_sum_relin_prepared(ma, &a_index, mb, &b_index, k as u64, rk, out),
+            None => self.multiply_sum_prepared(ma, &a_index, mb, &b_index, k as u64, out),
+        }
+    }
     pub fn rotate_rows_keys(&self, a: DeviceBatch, steps: i32, keys: &[&GaloisKeys], key_index: &[u32], out: DeviceBatch) -> Result<()> {
         same_count(&a, &out)?;
         Self::key_index_ok(key_index, keys.len(), a.count)?;

@@ -238,6 +238,10 @@ _SIGNATURES = {
     "hipbfv_batch_multiply_relin_shared": [vp, vp, vp, C.POINTER(C.c_uint32), u64, vp, vp, u64, vp],
     "hipbfv_batch_multiply_sum_shared": [vp, vp, vp, C.POINTER(C.c_uint32), u64, vp, u64, u64, vp],
     "hipbfv_batch_multiply_sum_relin_shared": [vp, vp, vp, C.POINTER(C.c_uint32), u64, vp, vp, u64, u64, vp],
+    "hipbfv_batch_multiply_prepared": [vp, vp, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint32), u64, vp, u64, vp],
+    "hipbfv_batch_multiply_relin_prepared": [vp, vp, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint32), u64, vp, vp, u64, vp],
+    "hipbfv_batch_multiply_sum_prepared": [vp, vp, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint32), u64, vp, u64, u64, vp],
+    "hipbfv_batch_multiply_sum_relin_prepared": [vp, vp, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint32), u64, vp, vp, u64, u64, vp],
     "hipbfv_profile_enable": [vp, C.c_bool],
     "hipbfv_profile_reset": [vp],
     "hipbfv_profile_kernel_count": [C.POINTER(C.c_uint32)],

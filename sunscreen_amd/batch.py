@@ -296,6 +296,56 @@ class BatchEvaluator:
                                                                   _stream()))
         return out
 
+    # ---- products of two prepared operands: no head, one middle kernel over both operands' rows (include/hipbfv.h) ----
+    @classmethod
+    def _pair_index(cls, a_index, b_index):
+        ap, na, ka = cls._b_index(a_index)
+        bp, nb, kb = cls._b_index(b_index)
+        if na != nb:
+            raise ValueError(f"a_index has {na} entries, b_index {nb}")
+        return ap, bp, na, (ka, kb)
+
+    def _new_prepared(self, count: int, size: int) -> torch.Tensor:
+        # (the operands live inside the objects: the output goes to the current device)
+        return torch.empty((count, size, self.K, self.n), dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))
+
+    def multiply_prepared(self, ma: "Multiplicand", a_index, mb: "Multiplicand", b_index, count: int | None = None,
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[i] = ma[a_index[i % L]] * mb[b_index[i % L]] as size-3 ciphertexts, L = len(a_index) = len(b_index); count defaults to L.
+        The words of multiply() on the two gathered arrays."""
+        ap, bp, n, _keep = self._pair_index(a_index, b_index)
+        count = n if count is None else count
+        out = out if out is not None else self._new_prepared(count, 3)
+        _check(_lib.load().hipbfv_batch_multiply_prepared(self._h, ma.get_handle(), ap, mb.get_handle(), bp, n, _ptr(out), count, _stream()))
+        return out
+
+    def multiply_relin_prepared(self, ma: "Multiplicand", a_index, mb: "Multiplicand", b_index, rk: RelinearizationKeys, count: int | None = None,
+                                out: torch.Tensor | None = None) -> torch.Tensor:
+        """multiply_relin() with both operands taken from prepared objects, [count, 2, K, N]."""
+        ap, bp, n, _keep = self._pair_index(a_index, b_index)
+        count = n if count is None else count
+        out = out if out is not None else self._new_prepared(count, 2)
+        _check(_lib.load().hipbfv_batch_multiply_relin_prepared(self._h, ma.get_handle(), ap, mb.get_handle(), bp, n, rk.get_handle(), _ptr(out), count,
+                                                                _stream()))
+        return out
+
+    def multiply_sum_prepared(self, ma: "Multiplicand", a_index, mb: "Multiplicand", b_index, groups: int, terms: int,
+                              out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[g] = sum_t ma[a_index[(g * terms + t) % L]] * mb[b_index[(g * terms + t) % L]], [groups, 3, K, N]."""
+        ap, bp, n, _keep = self._pair_index(a_index, b_index)
+        out = out if out is not None else self._new_prepared(groups, 3)
+        _check(_lib.load().hipbfv_batch_multiply_sum_prepared(self._h, ma.get_handle(), ap, mb.get_handle(), bp, n, _ptr(out), groups, terms, _stream()))
+        return out
+
+    def multiply_sum_relin_prepared(self, ma: "Multiplicand", a_index, mb: "Multiplicand", b_index, rk: RelinearizationKeys, groups: int, terms: int,
+                                    out: torch.Tensor | None = None) -> torch.Tensor:
+        """relinearize(multiply_sum_prepared(...)), [groups, 2, K, N]: one key switch per group."""
+        ap, bp, n, _keep = self._pair_index(a_index, b_index)
+        out = out if out is not None else self._new_prepared(groups, 2)
+        _check(_lib.load().hipbfv_batch_multiply_sum_relin_prepared(self._h, ma.get_handle(), ap, mb.get_handle(), bp, n, rk.get_handle(), _ptr(out),
+                                                                    groups, terms, _stream()))
+        return out
+
     def apply_galois_keys(self, ct: torch.Tensor, galois_elt: int, key_sets: Sequence[GaloisKeys], key_index, out: torch.Tensor | None = None) -> torch.Tensor:
         self._shape_ok(ct, 2)
         out = out if out is not None else self._new(ct.shape[0], 2, ct)

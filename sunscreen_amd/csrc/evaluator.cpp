@@ -334,26 +334,33 @@ int Evaluator::ntt(u64* data, size_t polys, u32 nprimes, bool inverse, hipStream
   return kOk;
 }
 
-int Evaluator::multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, size_t count, hipStream_t s, bool watch, const SharedSel* sh) {
+int Evaluator::multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, size_t count, hipStream_t s, bool watch, const SharedSel* sh,
+                        const PairSel* pr) {
   const DevCtx& h = ctx_->host();
   if (sa < 2 || sb < 2 || sa + sb > 16) return kInvalidArg;
-  if (sh && (sa != 2 || sb != 2)) return kInvalidArg;
+  if ((sh || pr) && (sa != 2 || sb != 2)) return kInvalidArg;
+  if (sh && pr) return kInvalidArg;
   if (h.logn > 15) return kUnsupported;
   const u32 n = h.n, K = h.K, S = h.S, R = K + S, sd = sa + sb - 1;
   // the per-coefficient kernels are instantiated for KMAX data primes and KMAX + 2 auxiliary primes
   const u32 kneed = std::max(K, S > 2 ? S - 2 : 0u);
   const bool split = split_mul_ && sa == 2 && sb == 2 && (kneed <= 4 || (kneed <= 8 && h.aux_f64)) && h.logn >= 12 && h.logn <= 14 &&
-                     !few_for_split_mul(count) && (!sh || sh->m->rows);
+                     !few_for_split_mul(count) && (!sh || sh->m->rows) && (!pr || pr->rows());
   // (the split kernels put the items on grid z; only the whole-polynomial launches count residue polynomials on one grid axis.
   // r06: the 3 x 54-bit multiply of 4096 items ran as 1820 + 1820 + 456 under the shared limit)
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, split ? 65535 : 65535 / (R * (sa + sb))));
-  const size_t ext_words = (size_t)(sa + sb) * R * n, d_words = (size_t)sd * R * n;
+  // (two prepared operands on the split path: no head, so no ext region -- D alone)
+  const size_t ext_words = pr && split ? 0 : (size_t)(sa + sb) * R * n, d_words = (size_t)sd * R * n;
   const size_t cc = std::min(chunk, count);  // a handle-level call (count = 1) reserves one op's scratch, not a chunk's
   // prepared multiplicands on the whole-polynomial path: the chunk's second operands are gathered behind D
-  const size_t gather_words = sh && !split ? (size_t)2 * K * n : 0;
+  // (two prepared operands: both are, the first operands in front of the second)
+  const size_t gather_words = split ? 0 : sh ? (size_t)2 * K * n : pr ? (size_t)4 * K * n : 0;
   SharedLease sl;
   if (sh)
     if (int rc = stage_shared(*sh, count, split, s, sl)) return rc;
+  PairLease pl;
+  if (pr)
+    if (int rc = stage_pair(*pr, count, split, s, pl)) return rc;
   ScratchGuard sg(pool_, cc * (ext_words + d_words + gather_words) * sizeof(u64), s);
   if (!sg.p) return kOutOfMemory;
   u64* ext = (u64*)sg.p;
@@ -364,7 +371,7 @@ int Evaluator::multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, si
   for (u32 j = 0; j < S; j++) mods.push_back(h.KK + j);
   const NttPlan plan = make_plan(1, mods);
   // x * x (Evaluator_Square, a program node with one operand twice): the split kernels extend and transform x once
-  const bool square = split && !sh && a == b;
+  const bool square = split && !sh && !pr && a == b;
   for (size_t off = 0; off < count; off += chunk) {
     const size_t c = std::min(chunk, count - off);
     if (split && sh) {
@@ -374,16 +381,27 @@ int Evaluator::multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, si
       HB_LAUNCH(kKernMulTail, c * 3, launch_mul_tail(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out + off * 3 * K * n, c, s));
       continue;
     }
+    if (split && pr) {
+      // no head: the middle kernel reads both operands' prepared rows, the tail unchanged
+      HB_LAUNCH(kKernMulMid, c, launch_mul_mid_pair(ctx_->dev(), h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, pr->ma->rows, pr->mb->rows, pl.idx + off, D, c, s));
+      HB_LAUNCH(kKernMulTail, c * 3, launch_mul_tail(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out + off * 3 * K * n, c, s));
+      continue;
+    }
     if (sh) HB_CHECK(launch_gather_items(sl.ptrs + off, bstage, gather_words, c, s));
-    const u64* bc = sh ? bstage : b + off * sb * K * n;
+    if (pr) {
+      HB_CHECK(launch_gather_items(pl.ptrs_a + off, bstage, gather_words / 2, c, s));
+      HB_CHECK(launch_gather_items(pl.ptrs_b + off, bstage + cc * (gather_words / 2), gather_words / 2, c, s));
+    }
+    const u64* ac = pr ? bstage : a + off * sa * K * n;
+    const u64* bc = sh ? bstage : pr ? bstage + cc * (gather_words / 2) : b + off * sb * K * n;
     if (split) {
       // head / middle / tail split transforms (kernels_split.hip): 3 launches instead of 5, 40 % less HBM traffic
-      HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + off * 2 * K * n, bc, ext, c, s, square ? 2u : 4u));
+      HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, ac, bc, ext, c, s, square ? 2u : 4u));
       HB_LAUNCH(kKernMulMid, c, launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square));
       HB_LAUNCH(kKernMulTail, c * 3, launch_mul_tail(ctx_->dev(), h.tw_inv, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul : (h.aux_mixed ? 1 : 0), h.conv_grid != 0, kneed, D, out + off * 3 * K * n, c, s));
       continue;
     }
-    HB_LAUNCH(kKernBehzExtend, c * (sa + sb), launch_behz_extend(ctx_->dev(), n, kneed, a + off * sa * K * n, sa, bc, sb, c, ext, s));
+    HB_LAUNCH(kKernBehzExtend, c * (sa + sb), launch_behz_extend(ctx_->dev(), n, kneed, ac, sa, bc, sb, c, ext, s));
     HB_LAUNCH(kKernNttFwd, c * (sa + sb) * R, launch_ntt(ctx_->dev(), h.tw_fwd, h.logn, ext, c * (sa + sb) * R, plan, false, 0, s));
     HB_LAUNCH(kKernTensor, c, launch_tensor(ctx_->dev(), n, R, ext, sa, sb, D, c, s));
     HB_LAUNCH(kKernNttInv, c * sd * R, launch_ntt(ctx_->dev(), h.tw_inv, h.logn, D, c * sd * R, plan, true, 1, s));
@@ -530,15 +548,15 @@ int Evaluator::relinearize(const u64* ct3, const KeySel& rk, u64* out2, size_t c
 
 // out3[g] = sum_t a[g][t] * b[g][t] (evaluator.hpp).  The path is multiply()'s choice for groups * terms items.
 int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch, const MulOp* wt,
-                            const SharedSel* sh) {
+                            const SharedSel* sh, const PairSel* pr) {
   const DevCtx& h = ctx_->host();
-  if (!terms) return kInvalidArg;
+  if (!terms || (sh && pr)) return kInvalidArg;
   if (h.logn > 15) return kUnsupported;
   if (!groups) return kOk;
   const u32 n = h.n, K = h.K, S = h.S, R = K + S;
   const u32 kneed = std::max(K, S > 2 ? S - 2 : 0u);
   const bool split = split_mul_ && (kneed <= 4 || (kneed <= 8 && h.aux_f64)) && h.logn >= 12 && h.logn <= 14 && !few_for_split_mul(groups * terms) &&
-                     (!sh || sh->m->rows);
+                     (!sh || sh->m->rows) && (!pr || pr->rows());
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, split ? 65535 : 65535 / (R * 4)));
   const size_t in_words = (size_t)2 * K * n, out_words = (size_t)3 * K * n;
   const size_t cc = std::min(chunk, groups * terms);
@@ -551,7 +569,8 @@ int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups
     const int rc = plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) -> int {
       const size_t first = st.group0 * terms + st.term0;
       const SharedSel sub = sh ? sh->at(first) : SharedSel();
-      if (int r = multiply(a + first * in_words, 2, sh ? nullptr : b + first * in_words, 2, stage, st.groups * st.terms, s, false, sh ? &sub : nullptr)) return r;
+      const PairSel psub = pr ? pr->at(first) : PairSel();
+      if (int r = multiply(pr ? nullptr : a + first * in_words, 2, sh || pr ? nullptr : b + first * in_words, 2, stage, st.groups * st.terms, s, false, sh ? &sub : nullptr, pr ? &psub : nullptr)) return r;
       for (size_t g = 0; g < st.groups; g++) {
         u64* o = out3 + (st.group0 + g) * out_words;
         const u64* t0 = stage + g * st.terms * out_words;
@@ -576,18 +595,23 @@ int Evaluator::multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups
     if (rc) return rc;
     return watch ? note_result(out3, 3, K, groups, s) : (int)kOk;
   }
-  const size_t ext_words = (size_t)4 * R * n, d_words = (size_t)3 * R * n;
+  const size_t ext_words = pr ? 0 : (size_t)4 * R * n, d_words = (size_t)3 * R * n;  // (two prepared operands: no head, no ext region)
   ScratchGuard sg(pool_, cc * (ext_words + d_words) * sizeof(u64), s);
   if (!sg.p) return kOutOfMemory;
   u64* ext = (u64*)sg.p;
   u64* D = ext + cc * ext_words;
-  const bool square = !sh && a == b;  // sums of squares: the head extends and the middle kernel transforms x once
+  const bool square = !sh && !pr && a == b;  // sums of squares: the head extends and the middle kernel transforms x once
   SharedLease sl;  // prepared multiplicands: one index table for the whole call, a launch sequence reads it from its first item
   if (sh)
     if (int rc = stage_shared(*sh, groups * terms, true, s, sl)) return rc;
+  PairLease pl;
+  if (pr)
+    if (int rc = stage_pair(*pr, groups * terms, true, s, pl)) return rc;
   const int rc = plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) -> int {
     const size_t first = st.group0 * terms + st.term0, c = st.groups * st.terms;
-    if (sh) {
+    if (pr) {
+      HB_LAUNCH(kKernMulMid, c, launch_mul_mid_pair(ctx_->dev(), h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, pr->ma->rows, pr->mb->rows, pl.idx + first, D, c, s));
+    } else if (sh) {
       HB_LAUNCH(kKernMulHead, c * 2, launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, h.aux_f64 != 0, h.aux_f64 ? (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0) : (h.aux_mixed ? 1 : 0), kneed, a + first * in_words, a + first * in_words, ext, c, s, 2u));
       HB_LAUNCH(kKernMulMid, c, launch_mul_mid_shared(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, sh->m->rows, sl.idx + first, D, c, s));
     } else {
@@ -612,7 +636,7 @@ int Evaluator::multiply_sum_weighted(const u64* a, const u64* b, const int32_t* 
 
 // one key switch per group: the size-3 sums go through a pooled buffer, chunk_ops() groups at a time
 int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s, const int32_t* weights,
-                                  const SharedSel* sh) {
+                                  const SharedSel* sh, const PairSel* pr) {
   const DevCtx& h = ctx_->host();
   if (h.KK < 2 || !rk.present()) return kNoKey;
   if (!terms) return kInvalidArg;
@@ -629,7 +653,8 @@ int Evaluator::multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, 
     const size_t c = std::min(block, groups - g0);
     const size_t off = g0 * terms * 2 * K * n;  // (b == a stays b + off == a + off: the squaring form)
     const SharedSel sub = sh ? sh->at(g0 * terms) : SharedSel();
-    if (int rc = multiply_sum(a + off, sh ? nullptr : b + off, sum3, c, terms, s, false, wl.wt, sh ? &sub : nullptr)) return rc;
+    const PairSel psub = pr ? pr->at(g0 * terms) : PairSel();
+    if (int rc = multiply_sum(pr ? nullptr : a + off, sh || pr ? nullptr : b + off, sum3, c, terms, s, false, wl.wt, sh ? &sub : nullptr, pr ? &psub : nullptr)) return rc;
     KeySel sel = rk;
     sel.first = rk.first + g0;
     if (int rc = relinearize(sum3, sel, out2 + g0 * 2 * K * n, c, s, nullptr, false)) return rc;
@@ -645,10 +670,11 @@ bool Evaluator::member_tail_ok(size_t count) const {
 }
 
 int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t count, hipStream_t s, const u64* addend, const MemberTail* members,
-                              u32 per, const MemberHead* heads, bool heads_square, const SharedSel* sh) {
+                              u32 per, const MemberHead* heads, bool heads_square, const SharedSel* sh, const PairSel* pr) {
   const DevCtx& h = ctx_->host();
   if (h.KK < 2 || !rk.present()) return kNoKey;
-  if (sh && (members || heads)) return kInvalidArg;
+  if ((sh || pr) && (members || heads)) return kInvalidArg;
+  if (sh && pr) return kInvalidArg;
   if (members && (!member_tail_ok(count) || !per || addend)) return kInvalidArg;
   if (heads && !members) return kInvalidArg;
   const u32 n = h.n, K = h.K, KK = h.KK, S = h.S, R = K + S;
@@ -661,22 +687,28 @@ int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64*
   // 3 x 54-bit set): mulrelin_head_mixed / mulrelin_tail_mixed, 8-byte rows, one or two middle launches per policy
   const bool fused_m = !fused_d && fuse_mulrelin_ && fuse_head_ && split_mul_ && split_ks_ && !h.aux_f64 && h.aux_mixed && h.ks_split_ok && kneed <= 4 &&
                        h.logn >= 12 && h.logn <= 14 && !lane_split((int)h.logn) && !few_for_fused(count);
-  const bool fused = (fused_d || fused_m) && (!sh || sh->m->rows);
+  const bool fused = (fused_d || fused_m) && (!sh || sh->m->rows) && (!pr || pr->rows());
   // x * x: the head extends and the middle kernel transforms x once.  Prepared multiplicands (sh) take the same two-polynomial head on
   // `a` (b = a below) and launch_mul_mid_shared in place of launch_mul_mid.
-  const bool square = fused && (sh || (heads ? heads_square : a == b));
+  // Two prepared operands (pr): no head at all, launch_mul_mid_pair.
+  const bool square = fused && !pr && (sh || (heads ? heads_square : a == b));
   if (sh) b = a;
   SharedLease sl;
   if (sh && fused)
     if (int rc = stage_shared(*sh, count, true, s, sl)) return rc;
+  PairLease pl;
+  if (pr && fused)
+    if (int rc = stage_pair(*pr, count, true, s, pl)) return rc;
   // the middle launch of a chunk of c items from item off
   const auto mul_mid = [&](const u64* ext, u64* D, size_t off, size_t c) -> hipError_t {
+    if (pr)
+      return launch_mul_mid_pair(ctx_->dev(), h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, pr->ma->rows, pr->mb->rows, pl.idx + off, D, c, s);
     if (sh)
       return launch_mul_mid_shared(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, sh->m->rows, sl.idx + off, D, c, s);
     return launch_mul_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, ctx_->dev()->mid_res_dp, h.mid_ndp, ctx_->dev()->mid_res_d, h.mid_nd, ctx_->dev()->mid_res_i, h.mid_ni, ext, D, c, s, square);
   };
   if (fused) {
-    const size_t ext_words = (size_t)4 * R * n, d_words = (size_t)3 * R * n, t_words = (size_t)KK * K * n, acc_words = (size_t)2 * KK * n, c2_words = (size_t)K * n;
+    const size_t ext_words = pr ? 0 : (size_t)4 * R * n, d_words = (size_t)3 * R * n, t_words = (size_t)KK * K * n, acc_words = (size_t)2 * KK * n, c2_words = (size_t)K * n;
     const size_t per_op = ext_words + d_words + t_words + acc_words + c2_words;
     // every kernel of this path puts the ops on grid z and its residue / block count on grid x: no 65535 limit but z's, which
     // the 4096-op cap of chunk_ops_ is far below (the limits of the whole-polynomial launches made N = 16384 run 910 + 114)
@@ -694,14 +726,14 @@ int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64*
     for (size_t off = 0; off < count; off += chunk) {
       const size_t c = std::min(chunk, count - off);
       if (fused_m) {
-        HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, false, 1, kneed, a + off * c2, b + off * c2, ext, c, s, square ? 2u : 4u));
+        if (!pr) HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, false, 1, kneed, a + off * c2, b + off * c2, ext, c, s, square ? 2u : 4u));
         HB_LAUNCH(kKernMulMid, c, mul_mid(ext, D, off, c));
         HB_LAUNCH(kKernKsHead, c, launch_mulrelin_head_mixed(ctx_->dev(), h.tw_inv, h.tw_fwd, h.logn, D, T, c, s));
         HB_LAUNCH(kKernKsMid, c, launch_ks_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, h, T, rk.key, ACC, c, s, kl.at(off)));
         HB_LAUNCH(kKernKsTail, c, launch_mulrelin_tail_mixed(ctx_->dev(), h.tw_inv, h.logn, D, ACC, addend ? addend + off * c2 : nullptr, out2 + off * c2, c, s));
         continue;
       }
-      HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, true, (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0), kneed, a + off * c2, b + off * c2, ext, c, s, square ? 2u : 4u, heads, (u32)off, per));
+      if (!pr) HB_LAUNCH(kKernMulHead, c * (square ? 2 : 4), launch_mul_head(ctx_->dev(), h.tw_fwd, h.logn, true, (int)h.pack_mul | (h.conv_grid == 1 ? 4 : 0), kneed, a + off * c2, b + off * c2, ext, c, s, square ? 2u : 4u, heads, (u32)off, per));
       HB_LAUNCH(kKernMulMid, c, mul_mid(ext, D, off, c));
       if (fuse_head_) {
         HB_LAUNCH(kKernKsHead, c, launch_mulrelin_head(ctx_->dev(), h.tw_inv, h.tw_fwd, h.logn, (int)h.pack_mul, h.conv_grid != 0, (int)h.pack_ks, kneed, D, T, c, s));
@@ -721,7 +753,8 @@ int Evaluator::multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64*
   for (size_t off = 0; off < count; off += chunk) {
     const size_t c = std::min(chunk, count - off);
     const SharedSel shc = sh ? sh->at(off) : SharedSel();
-    int rc = multiply(a + off * c2, 2, b + off * c2, 2, (u64*)sg.p, c, s, false, sh ? &shc : nullptr);
+    const PairSel prc = pr ? pr->at(off) : PairSel();
+    int rc = multiply(pr ? nullptr : a + off * c2, 2, pr ? nullptr : b + off * c2, 2, (u64*)sg.p, c, s, false, sh ? &shc : nullptr, pr ? &prc : nullptr);
     if (rc) return rc;
     KeySel sub = rk;  // the chunk's items are items first + off ... of the selection
     sub.first = rk.first + off;
@@ -863,6 +896,96 @@ int Evaluator::multiply_sum_relin_shared(const u64* a, const SharedSel& sh, cons
   if (!groups) return kOk;
   HB_CHECK(hipStreamWaitEvent(s, sh.m->ready, 0));
   return multiply_sum_relin(a, nullptr, rk, out2, groups, terms, s, nullptr, &sh);
+}
+
+// ---- products of two prepared operands
+
+int Evaluator::check_pair(const PairSel& sel, size_t items, size_t* bad, bool* bad_b) const {
+  if (!sel.ma || !sel.mb || !sel.a_index || !sel.b_index || !sel.period || sel.ma->ctx != ctx_ || sel.mb->ctx != ctx_) return kInvalidArg;
+  for (size_t i = 0; i < std::min(items, sel.period); i++) {
+    const size_t j = (sel.first + i) % sel.period;
+    const bool a_bad = sel.a_index[j] >= sel.ma->count;
+    if (a_bad || sel.b_index[j] >= sel.mb->count) {
+      if (bad) *bad = i;
+      if (bad_b) *bad_b = !a_bad;
+      return kInvalidArg;
+    }
+  }
+  return kOk;
+}
+
+Evaluator::PairLease::~PairLease() {
+  if (!ev) return;
+  if (host) ev->pinned_.release(host, s);
+  if (dev) ev->pool_.release(dev, s);
+}
+
+int Evaluator::stage_pair(const PairSel& sel, size_t items, bool rows, hipStream_t s, PairLease& lease) {
+  if (!sel.ma || !sel.mb || !sel.a_index || !sel.b_index || !sel.period || !items) return kInvalidArg;
+  const size_t bytes = items * (rows ? sizeof(uint2) : 2 * sizeof(u64*));
+  lease.ev = this;
+  lease.s = s;
+  lease.host = pinned_.acquire(bytes);
+  lease.dev = pool_.acquire(std::max<size_t>(bytes, (size_t)1 << 20), s);  // (one size class for the small tables, as stage_keymap's)
+  if (!lease.host || !lease.dev) return kOutOfMemory;
+  const size_t ct_words = (size_t)2 * ctx_->host().K * ctx_->host().n;
+  for (size_t i = 0; i < items; i++) {
+    const size_t j = (sel.first + i) % sel.period;
+    const u32 ka = sel.a_index[j], kb = sel.b_index[j];
+    if (ka >= sel.ma->count || kb >= sel.mb->count) return kInvalidArg;
+    if (rows) {
+      static_cast<uint2*>(lease.host)[i] = make_uint2(ka, kb);
+    } else {
+      static_cast<const u64**>(lease.host)[i] = sel.ma->ct + (size_t)ka * ct_words;
+      static_cast<const u64**>(lease.host)[items + i] = sel.mb->ct + (size_t)kb * ct_words;
+    }
+  }
+  HB_CHECK(hipMemcpyAsync(lease.dev, lease.host, bytes, hipMemcpyHostToDevice, s));
+  if (rows) {
+    lease.idx = static_cast<const uint2*>(lease.dev);
+  } else {
+    lease.ptrs_a = static_cast<const u64* const*>(lease.dev);
+    lease.ptrs_b = lease.ptrs_a + items;
+  }
+  return kOk;
+}
+
+// the call's stream waits for both objects (one wait where they are one object)
+static hipError_t wait_pair(const PairSel& pr, hipStream_t s) {
+  if (hipError_t e = hipStreamWaitEvent(s, pr.ma->ready, 0)) return e;
+  return pr.mb != pr.ma ? hipStreamWaitEvent(s, pr.mb->ready, 0) : hipSuccess;
+}
+
+int Evaluator::multiply_prepared(const PairSel& pr, u64* out3, size_t count, hipStream_t s) {
+  if (int rc = check_pair(pr, count, nullptr, nullptr)) return rc;
+  if (!count) return kOk;
+  HB_CHECK(wait_pair(pr, s));
+  return multiply(nullptr, 2, nullptr, 2, out3, count, s, true, nullptr, &pr);
+}
+
+int Evaluator::multiply_relin_prepared(const PairSel& pr, const KeySel& rk, u64* out2, size_t count, hipStream_t s) {
+  if (ctx_->host().KK < 2 || !rk.present()) return kNoKey;
+  if (int rc = check_pair(pr, count, nullptr, nullptr)) return rc;
+  if (!count) return kOk;
+  HB_CHECK(wait_pair(pr, s));
+  return multiply_relin(nullptr, nullptr, rk, out2, count, s, nullptr, nullptr, 0, nullptr, false, nullptr, &pr);
+}
+
+int Evaluator::multiply_sum_prepared(const PairSel& pr, u64* out3, size_t groups, size_t terms, hipStream_t s) {
+  if (!terms) return kInvalidArg;
+  if (int rc = check_pair(pr, groups * terms, nullptr, nullptr)) return rc;
+  if (!groups) return kOk;
+  HB_CHECK(wait_pair(pr, s));
+  return multiply_sum(nullptr, nullptr, out3, groups, terms, s, true, nullptr, nullptr, &pr);
+}
+
+int Evaluator::multiply_sum_relin_prepared(const PairSel& pr, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s) {
+  if (ctx_->host().KK < 2 || !rk.present()) return kNoKey;
+  if (!terms) return kInvalidArg;
+  if (int rc = check_pair(pr, groups * terms, nullptr, nullptr)) return rc;
+  if (!groups) return kOk;
+  HB_CHECK(wait_pair(pr, s));
+  return multiply_sum_relin(nullptr, nullptr, rk, out2, groups, terms, s, nullptr, nullptr, &pr);
 }
 
 // g^{-1} mod 2n (Newton iteration, g odd)

@@ -165,6 +165,23 @@ struct SharedSel {
   }
 };
 
+// Which two prepared ciphertexts each item of a *_prepared call multiplies: item i is ma->ct[a_index[(first + i) % period]] times
+// mb->ct[b_index[(first + i) % period]] (HOST arrays, every entry below its object's count -- the callers check; ma may be mb).
+struct PairSel {
+  const Multiplicand* ma = nullptr;
+  const Multiplicand* mb = nullptr;
+  const u32* a_index = nullptr;
+  const u32* b_index = nullptr;
+  size_t period = 0;
+  size_t first = 0;
+  bool rows() const { return ma->rows && mb->rows; }
+  PairSel at(size_t off) const {
+    PairSel r = *this;
+    r.first += off;
+    return r;
+  }
+};
+
 // The invariant-noise outputs of Evaluator::decrypt (device memory, one entry per item): budget = SEAL's invariant_noise_budget,
 // noise (optional) = the fork's invariant_noise as a double, worst (optional) = u64[count][K] limbs of max_x |[t * phase(x)]_q|.
 struct NoiseOut {
@@ -287,7 +304,11 @@ class Evaluator {
   // sh (here, in multiply_relin, multiply_sum and multiply_sum_relin): the second operands are prepared ciphertexts (SharedSel above), b is
   // unused.  The path is the one the call takes without it; where that is the split kernels, the head extends `a` alone and
   // launch_mul_mid_shared reads the prepared rows, elsewhere the chunk's multiplicands are gathered from sh->m->ct.  The same words.
-  int multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, size_t count, hipStream_t s, bool watch = true, const SharedSel* sh = nullptr);
+  // pr (the same four): BOTH operands are prepared ciphertexts (PairSel above), a and b are unused.  On the split path there is no head:
+  // launch_mul_mid_pair reads both operands' rows and the tail runs unchanged; elsewhere both operands of a chunk are gathered from the
+  // objects' canonical copies and the existing launches run.  The same words.  sh and pr exclude each other.
+  int multiply(const u64* a, u32 sa, const u64* b, u32 sb, u64* out, size_t count, hipStream_t s, bool watch = true, const SharedSel* sh = nullptr,
+               const PairSel* pr = nullptr);
   // addend (optional, the three key-switching operations): ciphertexts u64[count][2][K][N] added to the results inside the last kernel
   // rk / key: one key for the whole batch (a device pointer converts) or a per-item selection (KeySel above)
   int relinearize(const u64* ct3, const KeySel& rk, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr, bool watch = true);
@@ -298,7 +319,7 @@ class Evaluator {
   // member multiplies a ciphertext by itself
   int multiply_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr,
                      const MemberTail* members = nullptr, u32 per = 0, const MemberHead* heads = nullptr, bool heads_square = false,
-                     const SharedSel* sh = nullptr);
+                     const SharedSel* sh = nullptr, const PairSel* pr = nullptr);
   bool member_tail_ok(size_t count) const;
   // Sums of products with lazy relinearization: a, b = u64[groups][terms][2][K][N] (b == a: sums of squares),
   // out3[g] = sum_t a[g][t] * b[g][t] as size-3 ciphertexts -- word for word the sum of multiply()'s results (the order of a modular
@@ -310,13 +331,13 @@ class Evaluator {
   // just before they are added (mul_tail_sum_weighted_kernel; scaled_accumulate_kernel on the folded path).  A slice that starts at
   // term0 reads the table from row term0.
   int multiply_sum(const u64* a, const u64* b, u64* out3, size_t groups, size_t terms, hipStream_t s, bool watch = true, const MulOp* wt = nullptr,
-                   const SharedSel* sh = nullptr);
+                   const SharedSel* sh = nullptr, const PairSel* pr = nullptr);
   // weights: a HOST array of `terms` entries, read before the call returns and staged once (stage_weights).  All weights 1: the call above.
   int multiply_sum_weighted(const u64* a, const u64* b, const int32_t* weights, u64* out3, size_t groups, size_t terms, hipStream_t s);
   // out2[g] = relinearize(sum_t a[g][t] * b[g][t]): one key switch per GROUP; rk selects per group.  weights (optional): as above,
   // staged once for the whole call, not once per block of groups
   int multiply_sum_relin(const u64* a, const u64* b, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s,
-                         const int32_t* weights = nullptr, const SharedSel* sh = nullptr);
+                         const int32_t* weights = nullptr, const SharedSel* sh = nullptr, const PairSel* pr = nullptr);
   // Prepared multiplicands: ct2 = u64[count][2][K][N] is copied and, where the parameter set has a split multiply, extended and
   // transformed once (mul_head on two polynomials, mul_prep_mid).  Asynchronous on s; *out is owned by the caller (delete).
   int prepare_multiplicand(const u64* ct2, size_t count, hipStream_t s, Multiplicand** out);
@@ -329,6 +350,15 @@ class Evaluator {
   int multiply_relin_shared(const u64* a, const SharedSel& sh, const KeySel& rk, u64* out2, size_t count, hipStream_t s);
   int multiply_sum_shared(const u64* a, const SharedSel& sh, u64* out3, size_t groups, size_t terms, hipStream_t s);
   int multiply_sum_relin_shared(const u64* a, const SharedSel& sh, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s);
+  // kInvalidArg unless both objects belong to this context and every index is below its object's count (*bad: the first item that is
+  // not, *bad_b: whether it is the second operand's index); nothing is launched
+  int check_pair(const PairSel& sel, size_t items, size_t* bad, bool* bad_b) const;
+  // the four products of two prepared operands (include/hipbfv.h, hipbfv_batch_multiply_prepared ...): the stream waits for both
+  // objects' events, then the counterpart's launch sequence runs with pr
+  int multiply_prepared(const PairSel& pr, u64* out3, size_t count, hipStream_t s);
+  int multiply_relin_prepared(const PairSel& pr, const KeySel& rk, u64* out2, size_t count, hipStream_t s);
+  int multiply_sum_prepared(const PairSel& pr, u64* out3, size_t groups, size_t terms, hipStream_t s);
+  int multiply_sum_relin_prepared(const PairSel& pr, const KeySel& rk, u64* out2, size_t groups, size_t terms, hipStream_t s);
   // out2 = (sigma_g(c0), 0) + switch_key(sigma_g(c1), key)
   int apply_galois(const u64* ct2, u32 galois_elt, const KeySel& key, u64* out2, size_t count, hipStream_t s, const u64* addend = nullptr);
   // every item by its OWN Galois element in one key-switch pass (mixed-step rotation batches): elts / keys are HOST arrays of `count`
@@ -448,6 +478,19 @@ class Evaluator {
     ~SharedLease();
   };
   int stage_shared(const SharedSel& sel, size_t items, bool rows, hipStream_t s, SharedLease& lease);
+  // ... of one call over two prepared operands: rows -- uint2[items], item i's {a, b} indices (launch_mul_mid_pair reads idx + first item
+  // of the launch); otherwise two pointer tables of `items` entries each, item i's canonical ciphertexts (launch_gather_items)
+  struct PairLease {
+    Evaluator* ev = nullptr;
+    hipStream_t s = nullptr;
+    void* dev = nullptr;
+    void* host = nullptr;
+    const uint2* idx = nullptr;
+    const u64* const* ptrs_a = nullptr;
+    const u64* const* ptrs_b = nullptr;
+    ~PairLease();
+  };
+  int stage_pair(const PairSel& sel, size_t items, bool rows, hipStream_t s, PairLease& lease);
   bool split_mul_params() const;  // the parameter set has a split multiply at all (multiply()'s conditions but the item count)
   PinnedPool pinned_;
   Context* ctx_;

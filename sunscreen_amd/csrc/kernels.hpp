@@ -86,6 +86,10 @@ hipError_t launch_mul_prep_mid(const DevCtx* ctx, const MulOp* twf, u32 logn, co
                                const unsigned char* res_i, u32 ni, const u64* ext, u64* rows, size_t ops, hipStream_t s);
 hipError_t launch_mul_mid_shared(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d,
                                  u32 nd, const unsigned char* res_i, u32 ni, const u64* ext, const u64* rows, const u32* bidx, u64* D, size_t ops, hipStream_t s);
+// Products of two prepared operands: launch_mul_mid with item i's FIRST operand read from rows_a[pidx[i].x] and its second from
+// rows_b[pidx[i].y] (pidx: a DEVICE table of `ops` index pairs; rows_a may be rows_b).  No head, no forward transform, no ext.
+hipError_t launch_mul_mid_pair(const DevCtx* ctx, const MulOp* twi, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d, u32 nd,
+                               const unsigned char* res_i, u32 ni, const u64* rows_a, const u64* rows_b, const uint2* pidx, u64* D, size_t ops, hipStream_t s);
 hipError_t launch_mul_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, bool aux_f64, int pack, bool conv_grid, u32 kneed, const u64* D, u64* out,
                            size_t ops, hipStream_t s, u32 poly0 = 0, u32 npolys = 3);
 // the summing form (Evaluator::multiply_sum): D = [groups][terms][3][R][N]; out3[g] = the sum over group g's terms of what launch_mul_tail

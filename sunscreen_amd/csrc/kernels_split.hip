@@ -2248,6 +2248,137 @@ __global__ __launch_bounds__((MulSharedGeom<L, POLICY_D>::TPB), (MulSharedGeom<L
     run(ArithI(dm), twf, ext_r, out, smem, std::false_type{});
 }
 
+// ---- products of two prepared operands (the *_prepared calls): both operands are rows that mul_prep_mid_kernel wrote, so the middle
+// kernel runs no forward transform and the product has no head.  The rows hold what mul_mid_shared_body has in registers in front of
+// the tensor product (the same forward transform, the same MulSharedGeom), the products are formed by the same calls in the same
+// order, and the inverse transforms, the store-reduce and the packing of D are that body's: the same words in D.
+// ah / bh: this thread's first word of a^0's / b^0's row block; a^1's / b^1's is row_stride words further
+template <class A, int L, bool PACK, int EPT>
+__device__ __forceinline__ void mul_mid_pair_body(const DevMod& dm, const typename A::Tw* twi, const typename A::V* ah, const typename A::V* bh,
+                                                  size_t row_stride, typename A::V* D_r, size_t dpoly_stride, typename A::V* smem, u32 tid, u32 blk) {
+  using Sh = SplitShape<L, EPT>;
+  using V = typename A::V;
+  const A ar(dm);
+  const bool store_reduce = (dm.split_inv_mask & kPlanStoreReduce) != 0;
+  constexpr int RI = split_inv_radix(L, Sh::NPI - 1), LOWI = split_inv_low(L, Sh::NPI - 1);
+  using Out = BlkPass<A, L, LOWI, RI, EPT>;
+  auto store_poly = [&](int i, V(&dv)[EPT], u32 t) {
+    V* dst = D_r + (size_t)i * dpoly_stride;
+    if constexpr (PACK && std::is_same<A, ArithD>::value) {
+      if (store_reduce) reduce_all<A, EPT>(ar, dv);
+    }
+#pragma unroll
+    for (int g = 0; g < Out::G; g++)
+#pragma unroll
+      for (int k = 0; k < (1 << RI); k++) {
+        if constexpr (PACK && std::is_same<A, ArithD>::value)
+          nat_store<true, NtSites<L>::mul_mid_st>(dst, Sh::N, Out::elem(t, blk, g, k), dv[g * (1 << RI) + k]);
+        else
+          nt_st<NtSites<L>::mul_mid_st>(dst + Out::elem(t, blk, g, k), dv[g * (1 << RI) + k]);
+      }
+  };
+  const V* ah_p = ah;
+  const V* bh_p = bh;
+  auto load_row = [&](const V* base, int p, V(&dst)[EPT]) {
+#pragma unroll
+    for (int e = 0; e < EPT; e++) dst[e] = base[(size_t)p * row_stride + (size_t)e * Sh::TPB];
+  };
+  // (an opaque re-base of the row pointers: the loads after it are not scheduled above it)
+  auto pin = [&]() {
+    u32 zero = 0;
+    asm volatile("" : "+s"(zero) : : "memory");
+    ah_p = ah + zero;
+    bh_p = bh + zero;
+  };
+  if constexpr (EPT > kBlkEPT) {
+    // mul_mid_shared_body's sequence: d0 = a^0 b^0 leaves before d1 = a^1 b^0 + a^0 b^1 and d2 = a^1 b^1 are formed.  Nothing is held
+    // across an inverse transform: every row is requested just before its use (a^0, b^0 twice: L2 has them)
+    pin();
+    {
+      V d0[1][EPT];
+      {
+        V x[EPT], y[EPT];
+        load_row(ah_p, 0, x);
+        load_row(bh_p, 0, y);
+#pragma unroll
+        for (int e = 0; e < EPT; e++) d0[0][e] = ar.mul_var(x[e], y[e]);
+      }
+      mid_inverse_multi<A, L, 1, EPT, MID_TW_PIPE(L)>(ar, d0, smem, tid, blk, opaque_uniform(twi), dm.split_inv_mask);
+      store_poly(0, d0[0], tid);
+    }
+    pin();
+    u32 tid_st = tid;  // (the store offsets are worked out again for d1, d2, as in mul_mid_shared_body)
+    asm volatile("" : "+v"(tid_st));
+    V d12[2][EPT];
+    {
+      V x[EPT], y[EPT];
+      load_row(ah_p, 0, x);
+      load_row(bh_p, 1, y);
+#pragma unroll
+      for (int e = 0; e < EPT; e++) d12[0][e] = ar.mul_var(x[e], y[e]);  // a0 b1
+      load_row(ah_p, 1, x);
+#pragma unroll
+      for (int e = 0; e < EPT; e++) d12[1][e] = ar.mul_var(x[e], y[e]);  // a1 b1
+      load_row(bh_p, 0, y);
+#pragma unroll
+      for (int e = 0; e < EPT; e++) d12[0][e] = ar.mul_add(x[e], y[e], d12[0][e]);  // + a1 b0
+    }
+    __syncthreads();  // d0's last inverse pass may still be reading the exchange buffer
+    mid_inverse_multi<A, L, 2, EPT, MID_TW_PIPE(L)>(ar, d12, smem, tid, blk, opaque_uniform(twi), dm.split_inv_mask);
+    store_poly(1, d12[0], tid_st);
+    store_poly(2, d12[1], tid_st);
+  } else {
+    V d[3][EPT];
+    pin();
+    {
+      V a0[EPT], a1[EPT], b0[EPT], b1[EPT];
+      load_row(ah_p, 0, a0);
+      load_row(ah_p, 1, a1);
+      load_row(bh_p, 0, b0);
+      load_row(bh_p, 1, b1);
+#pragma unroll
+      for (int e = 0; e < EPT; e++) {
+        d[0][e] = ar.mul_var(a0[e], b0[e]);
+        d[1][e] = ar.mul_add(a0[e], b1[e], ar.mul_var(a1[e], b0[e]));
+        d[2][e] = ar.mul_var(a1[e], b1[e]);
+      }
+    }
+    mid_inverse_multi<A, L, 3, EPT, MID_TW_PIPE(L)>(ar, d, smem, tid, blk, twi, dm.split_inv_mask);
+#pragma unroll
+    for (int i = 0; i < 3; i++) store_poly(i, d[i], tid);
+  }
+}
+
+// grid as mul_mid_kernel's; pidx[op] = {index into rows_a, index into rows_b}, each below its object's number of prepared ciphertexts
+// (checked on the host before anything is launched), wave-uniform; rows_a may be rows_b
+template <int L, bool POLICY_D, bool PACK>
+__global__ __launch_bounds__((MulSharedGeom<L, POLICY_D>::TPB), (MulSharedGeom<L, POLICY_D>::WAVES)) void mul_mid_pair_kernel(
+    const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base, const u64* rows_a, const u64* rows_b, const uint2* __restrict__ pidx,
+    u64* __restrict__ D, const unsigned char* __restrict__ residues, u32 nres, u32 ops) {
+  using Geo = MulSharedGeom<L, POLICY_D>;
+  using Sh = SplitShape<L, Geo::EPT>;
+  __shared__ u64 smem[Geo::REGIONS * Sh::BLOCK];
+  const u32 tid = threadIdx.x;
+  const u32 K = ctx->K, S = ctx->S, KK = ctx->KK, R = K + S;
+  u32 blk, r, op;
+  if (!mul_mid_coords<L, Geo::EPT>(blockIdx.x, residues, nres, ops, blk, r, op)) return;
+  const u32 m = r < K ? r : KK + (r - K);
+  const DevMod& dm = ctx->mod[m];
+  u64* D_r = D + ((size_t)op * 3 * R + r) * Sh::N;
+  const size_t ps = (size_t)R * Sh::N;
+  const uint2 ix = pidx[op];
+  const size_t in_row = (size_t)blk * Sh::BLOCK + tid;
+  const u64* ah = rows_a + ((size_t)ix.x * 2 * R + r) * Sh::N + in_row;
+  const u64* bh = rows_b + ((size_t)ix.y * 2 * R + r) * Sh::N + in_row;
+  const MulOp* twi = twi_base + (size_t)m * Sh::N;
+  if constexpr (POLICY_D)
+    mul_mid_pair_body<ArithD, L, PACK, Geo::EPT>(dm, reinterpret_cast<const double*>(twi), reinterpret_cast<const double*>(ah),
+                                                 reinterpret_cast<const double*>(bh), ps, reinterpret_cast<double*>(D_r), ps,
+                                                 reinterpret_cast<double*>(smem), tid, blk);
+  else
+    mul_mid_pair_body<ArithI, L, false, kBlkEPT>(dm, twi, ah, bh, ps, D_r, ps, smem, tid, blk);
+}
+
 // the tail's inverse stages + BEHZ scaling on the 4 coefficients thread t owns (EdgeGeom): canonical residues out
 // src: the residue row (not offset by t)
 template <class A, int L>
@@ -3581,6 +3712,24 @@ hipError_t launch_mul_prep_mid(const DevCtx* ctx, const MulOp* twf, u32 logn, co
                                const unsigned char* res_i, u32 ni, const u64* ext, u64* rows, size_t ops, hipStream_t s) {
   if (!rows) return hipErrorInvalidValue;
   SPLIT_DISPATCH(mul_mid_shared_t, ctx, twf, (const MulOp*)nullptr, res_dp, ndp, res_d, nd, res_i, ni, ext, rows, (const u32*)nullptr, (u64*)nullptr, ops, s)
+}
+
+template <int L>
+static hipError_t mul_mid_pair_t(const DevCtx* ctx, const MulOp* twi, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d, u32 nd,
+                                 const unsigned char* res_i, u32 ni, const u64* rows_a, const u64* rows_b, const uint2* pidx, u64* D, size_t ops, hipStream_t s) {
+  using Sh = SplitShape<L>;
+  if (((reinterpret_cast<uintptr_t>(res_dp) | reinterpret_cast<uintptr_t>(res_d) | reinterpret_cast<uintptr_t>(res_i)) & 3u) != 0) return hipErrorInvalidValue;
+  const size_t ops_g = MUL_MID_SLICE(L) ? (ops + 7) / 8 * 8 : ops;
+  constexpr unsigned TD = MulSharedGeom<L, true>::TPB, TI = MulSharedGeom<L, false>::TPB;
+  if (ndp) mul_mid_pair_kernel<L, true, true><<<dim3((unsigned)(ops_g * ndp * Sh::NBLK)), TD, 0, s>>>(ctx, twi, rows_a, rows_b, pidx, D, res_dp, ndp, (u32)ops);
+  if (nd) mul_mid_pair_kernel<L, true, false><<<dim3((unsigned)(ops_g * nd * Sh::NBLK)), TD, 0, s>>>(ctx, twi, rows_a, rows_b, pidx, D, res_d, nd, (u32)ops);
+  if (ni) mul_mid_pair_kernel<L, false, false><<<dim3((unsigned)(ops_g * ni * Sh::NBLK)), TI, 0, s>>>(ctx, twi, rows_a, rows_b, pidx, D, res_i, ni, (u32)ops);
+  return hipGetLastError();
+}
+hipError_t launch_mul_mid_pair(const DevCtx* ctx, const MulOp* twi, u32 logn, const unsigned char* res_dp, u32 ndp, const unsigned char* res_d, u32 nd,
+                               const unsigned char* res_i, u32 ni, const u64* rows_a, const u64* rows_b, const uint2* pidx, u64* D, size_t ops, hipStream_t s) {
+  if (!twi || !rows_a || !rows_b || !pidx) return hipErrorInvalidValue;
+  SPLIT_DISPATCH(mul_mid_pair_t, ctx, twi, res_dp, ndp, res_d, nd, res_i, ni, rows_a, rows_b, pidx, D, ops, s)
 }
 
 template <int L>

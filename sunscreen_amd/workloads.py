@@ -130,3 +130,27 @@ def pir_lookup_sharded(ev, col_query, row_query_local, db_ntt_local, relin_keys,
     from . import dist as D
 
     return D.reduce_ciphertexts(pir_lookup(ev, col_query, row_query_local, db_ntt_local, relin_keys), ev.add, root)
+
+
+def matrix_product_index(m: int, k: int, n: int):
+    """The index tables of C = A B over prepared operands, A row-major m x k and B row-major k x n: item (i * n + j) * k + t multiplies
+    A[i][t] = prepared ciphertext i * k + t of A by B[t][j] = prepared ciphertext t * n + j of B.  Returns (a_index, b_index), two lists
+    of m * n * k integers: groups = m * n, terms = k in the sum forms."""
+    if m <= 0 or k <= 0 or n <= 0:
+        raise ValueError("matrix_product_index needs m, k, n >= 1")
+    a_index = [i * k + t for i in range(m) for j in range(n) for t in range(k)]
+    b_index = [t * n + j for i in range(m) for j in range(n) for t in range(k)]
+    return a_index, b_index
+
+
+def matrix_product(ev, ma, mb, m: int, k: int, n: int, relin_keys=None):
+    """The ciphertext matrix product C[i][j] = sum_t A[i][t] * B[t][j] in one call: ma = ev.prepare of A's m * k ciphertexts (row-major),
+    mb = ev.prepare of B's k * n.  Each distinct ciphertext was extended and transformed once when its object was made; the product
+    runs no head and no forward transform (BatchEvaluator.multiply_sum_prepared).  Returns int64[m * n, 3, K, N], row-major, or
+    int64[m * n, 2, K, N] with one key switch per entry when relin_keys is given.  The words of multiply, add and relinearize."""
+    if ma.count != m * k or mb.count != k * n:
+        raise ValueError(f"A holds {ma.count} ciphertexts for {m} x {k}, B {mb.count} for {k} x {n}")
+    a_index, b_index = matrix_product_index(m, k, n)
+    if relin_keys is None:
+        return ev.multiply_sum_prepared(ma, a_index, mb, b_index, m * n, k)
+    return ev.multiply_sum_relin_prepared(ma, a_index, mb, b_index, relin_keys, m * n, k)
