@@ -341,6 +341,42 @@ long hipbfv_batch_apply_galois_items(void *evaluator, const uint64_t *ct2, const
                                      uint64_t *out2, uint64_t count, void *stream);
 long hipbfv_batch_rotate_rows_items(void *evaluator, const uint64_t *ct2, const int32_t *steps, void *galois_keys,
                                     uint64_t *out2, uint64_t count, void *stream);
+/* Sums of rotations: out2[g] = sum_t rotate_rows(source of item g * terms + t, steps[t]) -- the giant-step sum of a baby-step /
+ * giant-step matrix-vector product, a moving-window or prefix sum over slots, a convolution with a few taps, a replicated slot --
+ * with every term finished and added inside the key switch's last kernel: a term's rows are never written and no add pass runs.
+ *  - Layouts: ct2 device u64[sources][2][K][N]; out2 device u64[groups][2][K][N]; steps / galois_elts HOST arrays of `terms`
+ *    entries, shared by every group (as `weights` in hipbfv_batch_multiply_sum_weighted); src_index a HOST array of index_len
+ *    entries; all host arrays are read before the call returns.  Item i = g * terms + t reads source src_index[i % index_len];
+ *    src_index == NULL means source i, and then sources must equal groups * terms.  (NULL: a sum of distinct ciphertexts;
+ *    src_index[i] = i / terms with index_len = groups * terms: one ciphertext per group by many steps; {0, ..., terms - 1}: one set
+ *    of ciphertexts shared by all groups.)  Nothing is replicated in memory.
+ *  - Bits: out2[g] is, word for word, the sum (hipbfv_batch_add, in any order) of hipbfv_batch_rotate_rows(source, steps[t]) over the
+ *    group's terms -- of hipbfv_batch_apply_galois for the Galois form.  Every distinct step decides as SEAL's rotate_internal does:
+ *    step 0 (element 1) contributes the source itself, a step whose element's key is held rotates through it, any other step
+ *    walks its NAF chain.  With terms == 1 the result equals hipbfv_batch_rotate_rows_items (hipbfv_batch_apply_galois_items).  The
+ *    same (source, step) listed twice contributes twice.  Neither one decomposition shared by many steps nor one mod-down shared by
+ *    a group's terms would give these bits: every term runs its own key switch up to its own mod-down.
+ *  - Refusals, all before anything is launched, copied or written: a NULL evaluator, ct2, out2, steps (galois_elts) or key object
+ *    is HIPBFV_E_POINTER; HIPBFV_E_INVALIDARG: terms == 0; src_index != NULL with index_len == 0; an index >= sources; src_index
+ *    == NULL with sources != groups * terms; |step| >= N/2, or an even or too large element; a missing direct key or chain key; ANY
+ *    overlap of the out2 range with the ct2 range (there is no in-place form: a group's sum would be written while other groups
+ *    still read their sources); more than 2^32 - 1 groups or terms.  groups == 0 returns HIPBFV_S_OK, nothing launched.  Parameters
+ *    without batching give the row form HIPBFV_COR_E_INVALIDOPERATION.  hipbfv_last_error names the first offender: "term <t>: ..."
+ *    for a step, an element or a key, "item <i>: ..." for an index.
+ *  - Launches: where the key switch takes the split kernels for groups * terms items (N = 4096 ... 16384), a chunk is a whole
+ *    number of groups and runs ONE head / middle / summing-tail sequence for all its direct-key and identity terms; a group with
+ *    more terms than a chunk holds is summed in slices (hipbfv_debug_rotate_sum_plan).  Chain terms are rotated beforehand by the
+ *    chain of hipbfv_batch_rotate_rows into a staging buffer -- each distinct (source, step) once -- and enter the sum as identity
+ *    terms.  Elsewhere (N < 4096, N = 32768, a few items, HIPBFV_NO_FUSED_GALOIS=1) the terms are rotated into a staging buffer and
+ *    folded by the element-wise add: the same bits.  Asynchronous on `stream`.
+ *  - Transparent results: the sums are recorded under GROUP numbers (hipbfv_batch_status); a transparent term inside a sum that is
+ *    not transparent is NOT detected. */
+long hipbfv_batch_rotate_rows_sum(void *evaluator, const uint64_t *ct2, uint64_t sources, const uint32_t *src_index,
+                                  uint64_t index_len, const int32_t *steps, void *galois_keys, uint64_t *out2, uint64_t groups,
+                                  uint64_t terms, void *stream);
+long hipbfv_batch_apply_galois_sum(void *evaluator, const uint64_t *ct2, uint64_t sources, const uint32_t *src_index,
+                                   uint64_t index_len, const uint32_t *galois_elts, void *galois_keys, uint64_t *out2,
+                                   uint64_t groups, uint64_t terms, void *stream);
 /* Per-key batches (multi-tenant serving).  The reference hands the keys over with every call
  * (sunscreen_runtime/src/run.rs:100-105: `relin_keys: &Option<&RelinearizationKeys>`, `galois_keys: &Option<&GaloisKeys>`;
  * runtime.rs:310-327), so a server that batches the calls of many clients holds one key set per client.  These are the
@@ -776,6 +812,15 @@ long hipbfv_debug_rotate_items_keys_plan(uint64_t n, const int32_t *steps, const
  * earlier slice of the same group wrote.  *count = the number of sequences (E_INVALIDARG when it exceeds capacity). */
 long hipbfv_debug_multiply_sum_plan(uint64_t groups, uint64_t terms, uint64_t chunk, uint64_t *steps5, uint64_t capacity,
                                     uint64_t *count);
+/* Host only: what hipbfv_batch_rotate_rows_sum does with `steps` (terms entries) at degree n over a key set that holds exactly the
+ * keys of the elements present_elts, for `groups` groups under a chunk of `chunk` items.  kind[t]: 0 the term is the source itself,
+ * 1 it rotates through its own key inside the summing sequence (elt[t] = its Galois element), 2 it walks a NAF chain of rounds[t]
+ * hops beforehand and enters the sum as an identity term (rounds[t] = 0 for the other kinds).  steps5 / capacity / *count: the launch
+ * sequences as rows of {first group, groups, first term, terms, accumulate}, exactly as hipbfv_debug_multiply_sum_plan reports them.
+ * Fails as the call would (terms == 0, a refused step or a missing key: "term <t>: ..."), and on chunk == 0. */
+long hipbfv_debug_rotate_sum_plan(uint64_t n, const int32_t *steps, uint64_t terms, const uint32_t *present_elts, uint64_t num_present,
+                                  uint64_t groups, uint64_t chunk, int32_t *kind, uint32_t *elt, uint32_t *rounds, uint64_t *steps5,
+                                  uint64_t capacity, uint64_t *count);
 /* Host only, no device access: the product launches of hipbfv_batch_dot_plain_ntt_queries, 6 words per step
  * {first_query, queries, first_row, rows, QT, RT}: one launch multiplies those queries against those rows, QT queries and RT rows
  * per thread; QT == 1 names today's single-query kernel.  One query is one such step; otherwise the queries go in order, as many per

@@ -665,6 +665,19 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
   void rotate_rows_items(const uint64_t* ct, const std::vector<int32_t>& steps, const GaloisKeys& gk, uint64_t* out, void* stream = nullptr) const {
     check(hipbfv_batch_rotate_rows_items(h_, ct, steps.data(), gk.get_handle(), out, steps.size(), stream));
   }
+  // Sums of rotations on device buffers (hipbfv.h): out[g] = sum_t rotate_rows(source of item g * terms + t, steps[t]), ct =
+  // u64[sources][2][K][N], out = u64[groups][2][K][N], terms = steps.size().  Item i reads source src_index[i % src_index.size()]; an empty
+  // src_index means source i (sources == groups * terms).  No in-place form.  Not part of the reference crate's surface.
+  void rotate_rows_sum(const uint64_t* ct, uint64_t sources, const std::vector<uint32_t>& src_index, const std::vector<int32_t>& steps, const GaloisKeys& gk,
+                       uint64_t* out, uint64_t groups, void* stream = nullptr) const {
+    check(hipbfv_batch_rotate_rows_sum(h_, ct, sources, src_index.empty() ? nullptr : src_index.data(), src_index.size(), steps.data(), gk.get_handle(), out, groups,
+                                       steps.size(), stream));
+  }
+  void apply_galois_sum(const uint64_t* ct, uint64_t sources, const std::vector<uint32_t>& src_index, const std::vector<uint32_t>& galois_elts,
+                        const GaloisKeys& gk, uint64_t* out, uint64_t groups, void* stream = nullptr) const {
+    check(hipbfv_batch_apply_galois_sum(h_, ct, sources, src_index.empty() ? nullptr : src_index.data(), src_index.size(), galois_elts.data(), gk.get_handle(), out,
+                                        groups, galois_elts.size(), stream));
+  }
   // ... with one key set per client: item i by its own element / step through keys[key_index[i]].  An entry of `keys` that no rotating
   // item names may be nullptr.
   void apply_galois_items_keys(const uint64_t* ct, const std::vector<uint32_t>& galois_elts, const std::vector<const GaloisKeys*>& keys,

@@ -121,6 +121,34 @@ impl<'e> BatchEvaluator<'e> {
         Self::per_item_ok(steps.len(), a.count, "steps")?;
         check(unsafe { bindgen::hipbfv_batch_rotate_rows_items(self.h(), a.ptr, steps.as_ptr(), gk.get_handle(), out.ptr, a.count, self.stream) })
     }
+    // ---- sums of rotations: out[g] = sum_t rotate_rows(source of item g * terms + t, steps[t]) (include/hipbfv.h) ----
+    // `a` holds the sources, `out` one ciphertext per group, terms = steps.len().  Item i reads source `src_index[i % src_index.len()]`;
+    // `None` means source i (a.count == out.count * terms).  No in-place form.
+    fn sum_sources_ok(a: &DeviceBatch, out: &DeviceBatch, terms: usize, src_index: Option<&[u32]>) -> Result<()> {
+        let ok = terms > 0
+            && match src_index {
+                None => a.count == out.count * terms as u64,
+                Some(idx) => !idx.is_empty() && idx.iter().all(|&i| (i as u64) < a.count),
+            };
+        if !ok {
+            return Err(crate::Error::InvalidArgument(format!("{} sources for {} groups of {} terms", a.count, out.count, terms)));
+        }
+        Ok(())
+    }
+    pub fn rotate_rows_sum(&self, a: DeviceBatch, src_index: Option<&[u32]>, steps: &[i32], gk: &GaloisKeys, out: DeviceBatch) -> Result<()> {
+        Self::sum_sources_ok(&a, &out, steps.len(), src_index)?;
+        let (ip, n) = src_index.map_or((std::ptr::null(), 0u64), |idx| (idx.as_ptr(), idx.len() as u64));
+        check(unsafe {
+            bindgen::hipbfv_batch_rotate_rows_sum(self.h(), a.ptr, a.count, ip, n, steps.as_ptr(), gk.get_handle(), out.ptr, out.count, steps.len() as u64, self.stream)
+        })
+    }
+    pub fn apply_galois_sum(&self, a: DeviceBatch, src_index: Option<&[u32]>, galois_elts: &[u32], gk: &GaloisKeys, out: DeviceBatch) -> Result<()> {
+        Self::sum_sources_ok(&a, &out, galois_elts.len(), src_index)?;
+        let (ip, n) = src_index.map_or((std::ptr::null(), 0u64), |idx| (idx.as_ptr(), idx.len() as u64));
+        check(unsafe {
+            bindgen::hipbfv_batch_apply_galois_sum(self.h(), a.ptr, a.count, ip, n, galois_elts.as_ptr(), gk.get_handle(), out.ptr, out.count, galois_elts.len() as u64, self.stream)
+        })
+    }
     // ---- per-key batches ----
     // The reference hands the keys over with every call (`sunscreen_runtime/src/run.rs:100-105`: `relin_keys:
     // &Option<&RelinearizationKeys>`, `galois_keys: &Option<&GaloisKeys>`; `runtime.rs:310-327`): a server that batches the

@@ -119,6 +119,8 @@ _SIGNATURES = {
     "hipbfv_batch_rotate_rows": [vp, vp, C.c_int, vp, vp, u64, vp],
     "hipbfv_batch_apply_galois_items": [vp, vp, C.POINTER(C.c_uint32), vp, vp, u64, vp],
     "hipbfv_batch_rotate_rows_items": [vp, vp, C.POINTER(C.c_int32), vp, vp, u64, vp],
+    "hipbfv_batch_rotate_rows_sum": [vp, vp, u64, C.POINTER(C.c_uint32), u64, C.POINTER(C.c_int32), vp, vp, u64, u64, vp],
+    "hipbfv_batch_apply_galois_sum": [vp, vp, u64, C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32), vp, vp, u64, u64, vp],
     "hipbfv_batch_rotate_columns": [vp, vp, vp, vp, u64, vp],
     "hipbfv_batch_relinearize_keys": [vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64, vp],
     "hipbfv_batch_multiply_relin_keys": [vp, vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64, vp],
@@ -226,6 +228,8 @@ _SIGNATURES = {
     "hipbfv_batch_multiply_sum_relin": [vp, vp, vp, vp, vp, u64, u64, vp],
     "hipbfv_batch_multiply_sum_relin_keys": [vp, vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64, u64, vp],
     "hipbfv_debug_multiply_sum_plan": [u64, u64, u64, u64p, u64, u64p],
+    "hipbfv_debug_rotate_sum_plan": [u64, C.POINTER(C.c_int32), u64, C.POINTER(C.c_uint32), u64, u64, u64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32), u64p, u64, u64p],
     "hipbfv_batch_multiply_sum_weighted": [vp, vp, vp, C.POINTER(C.c_int32), vp, u64, u64, vp],
     "hipbfv_batch_multiply_sum_weighted_relin": [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, u64, u64, vp],
     "hipbfv_batch_multiply_sum_weighted_relin_keys": [vp, vp, vp, C.POINTER(C.c_int32), vpp, u64, C.POINTER(C.c_uint32), vp, u64, u64, vp],

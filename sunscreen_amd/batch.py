@@ -155,6 +155,51 @@ class BatchEvaluator:
                                                           ct.shape[0], _stream()))
         return out
 
+    # ---- sums of rotations: every term finished and added inside the key switch's last kernel (include/hipbfv.h) ----
+    def _rotation_sum_args(self, ct: torch.Tensor, terms: int, groups, src_index, out):
+        self._shape_ok(ct, 2)
+        assert terms > 0, "a sum of rotations needs at least one term per group"
+        if src_index is None:
+            assert ct.shape[0] % terms == 0, (ct.shape[0], terms)
+            groups = ct.shape[0] // terms if groups is None else groups
+            assert groups * terms == ct.shape[0], (groups, terms, ct.shape[0])
+            idx, ip, n = None, None, 0
+        else:
+            idx = np.ascontiguousarray(np.asarray(src_index, dtype=np.uint32))
+            assert idx.ndim == 1 and idx.size > 0, idx.shape
+            assert int(idx.max()) < ct.shape[0], (int(idx.max()), ct.shape[0])
+            if groups is None:
+                assert idx.size % terms == 0, (idx.size, terms)
+                groups = idx.size // terms
+            ip, n = idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size
+        if out is None:
+            out = self._new(groups, 2, ct)
+        self._shape_ok(out, 2)
+        assert out.shape[0] == groups, (out.shape[0], groups)
+        return groups, ip, n, out, idx
+
+    def rotate_rows_sum(self, ct: torch.Tensor, steps, gk: GaloisKeys, groups: int | None = None, src_index=None,
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[g] = sum over t of rotate_rows(ct[source of item g * len(steps) + t], steps[t]): the bits of rotate_rows + add.  Item i
+        reads source src_index[i % len(src_index)]; without src_index it reads ct[i] (groups * len(steps) ciphertexts).  groups defaults
+        to the items / terms."""
+        st = np.ascontiguousarray(np.asarray(steps, dtype=np.int32))
+        assert st.ndim == 1, st.shape
+        groups, ip, n, out, _keep = self._rotation_sum_args(ct, st.size, groups, src_index, out)
+        _check(_lib.load().hipbfv_batch_rotate_rows_sum(self._h, _ptr(ct), ct.shape[0], ip, n, st.ctypes.data_as(C.POINTER(C.c_int32)), gk.get_handle(),
+                                                        _ptr(out), groups, st.size, _stream()))
+        return out
+
+    def apply_galois_sum(self, ct: torch.Tensor, galois_elts, gk: GaloisKeys, groups: int | None = None, src_index=None,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+        """rotate_rows_sum with term t given by its Galois element (odd, below 2 N; 1: the source itself)."""
+        elts = np.ascontiguousarray(np.asarray(galois_elts, dtype=np.uint32))
+        assert elts.ndim == 1, elts.shape
+        groups, ip, n, out, _keep = self._rotation_sum_args(ct, elts.size, groups, src_index, out)
+        _check(_lib.load().hipbfv_batch_apply_galois_sum(self._h, _ptr(ct), ct.shape[0], ip, n, elts.ctypes.data_as(C.POINTER(C.c_uint32)), gk.get_handle(),
+                                                         _ptr(out), groups, elts.size, _stream()))
+        return out
+
     # ---- per-key batches (multi-tenant: the reference passes the keys per call, sunscreen_runtime/src/run.rs:100-105) ----
     @staticmethod
     def _key_sets(key_sets, key_index, count: int):
@@ -618,6 +663,25 @@ def rotate_items_keys_plan(n: int, steps, key_index, present_sets) -> tuple[list
                                                            offsets.ctypes.data_as(C.POINTER(C.c_uint64)), kind, entry, rounds_of, C.byref(entries),
                                                            C.byref(rounds)))
     return list(kind[: st.size]), list(entry[: st.size]), list(rounds_of[: st.size]), entries.value, rounds.value
+
+
+def rotate_sum_plan(n: int, steps, present_elts, groups: int, chunk: int):
+    """The library's plan for rotate_rows_sum (host only) at degree n over a key set that holds exactly the keys of present_elts: per
+    term its kind (0 the source itself, 1 through its own key inside the summing sequence, 2 a NAF chain beforehand), its Galois
+    element and its chain's rounds; then the launch sequences as multiply_sum_plan reports them."""
+    st = np.ascontiguousarray(np.asarray(steps, dtype=np.int32))
+    pe = np.ascontiguousarray(np.asarray(present_elts, dtype=np.uint32))
+    kind = (C.c_int32 * max(1, st.size))()
+    elt = (C.c_uint32 * max(1, st.size))()
+    rounds = (C.c_uint32 * max(1, st.size))()
+    L = _lib.load()
+    args = (n, st.ctypes.data_as(C.POINTER(C.c_int32)), st.size, pe.ctypes.data_as(C.POINTER(C.c_uint32)), pe.size, groups, chunk, kind, elt, rounds)
+    cnt = C.c_uint64()
+    L.hipbfv_debug_rotate_sum_plan(*args, None, 0, C.byref(cnt))  # (the count; the call below raises what this one refused)
+    buf = (C.c_uint64 * (5 * max(1, cnt.value)))()
+    _check(L.hipbfv_debug_rotate_sum_plan(*args, buf, cnt.value, C.byref(cnt)))
+    seq = [(buf[5 * i], buf[5 * i + 1], buf[5 * i + 2], buf[5 * i + 3], bool(buf[5 * i + 4])) for i in range(cnt.value)]
+    return list(kind[: st.size]), list(elt[: st.size]), list(rounds[: st.size]), seq
 
 
 def multiply_sum_plan(groups: int, terms: int, chunk: int) -> list[tuple[int, int, int, int, bool]]:

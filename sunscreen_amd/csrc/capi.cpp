@@ -2158,6 +2158,136 @@ long hipbfv_debug_rotate_items_plan(uint64_t n, const int32_t* steps, uint64_t c
   return HIPBFV_S_OK;
 HIPBFV_END
 
+// ---- sums of rotations: out2[g] = sum_t rotate(source of item g * terms + t, steps[t]) (include/hipbfv.h) ----
+// What hipbfv_batch_rotate_rows_sum / hipbfv_batch_apply_galois_sum do with every TERM, decided once per term as
+// hipbfv_batch_rotate_rows decides for a whole batch (plan_row_rotation): step 0 / element 1 is the source itself; a step whose
+// element's key is held rotates through it inside the summing launch sequence (Evaluator::rotate_sum); any other step walks its NAF
+// chain beforehand, into a stage, and enters the sum as an identity term.  Host only (hipbfv_debug_rotate_sum_plan shows it).
+static long term_error(uint64_t term, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "term %llu: %s", (unsigned long long)term, what);
+  return fail(HIPBFV_E_INVALIDARG, msg);
+}
+// steps (the row form) or elts (the Galois form, which has no chains); has(element): the key set holds that element's key
+static long plan_rotate_sum(u32 n, const int32_t* steps, const uint32_t* elts, uint64_t terms, const std::function<bool(u32)>& has,
+                            std::vector<RowRotation>* plan) {
+  if (!terms) return fail(HIPBFV_E_INVALIDARG, "a sum of rotations needs at least one term per group");
+  plan->assign(terms, RowRotation());
+  for (uint64_t t = 0; t < terms; t++) {
+    RowRotation& r = (*plan)[t];
+    if (steps) {
+      const uint64_t same = std::find(steps, steps + t, steps[t]) - steps;  // (one decision per distinct step)
+      r = same < t ? (*plan)[same] : plan_row_rotation(n, steps[t], has);
+      if (r.kind == RowRotation::kTooLarge) return term_error(t, "step count too large");
+    } else {
+      if (!(elts[t] & 1) || elts[t] >= 2 * n) return term_error(t, "the Galois element must be odd and below 2 N");
+      if (elts[t] == 1) continue;
+      r.elt = elts[t];
+      if (has(r.elt))
+        r.kind = RowRotation::kDirect, r.hop[r.hops++] = r.elt;
+      else
+        r.kind = RowRotation::kNoKey;
+    }
+    if (r.kind == RowRotation::kNoKey) return term_error(t, "required key-switching key is not present");
+  }
+  return HIPBFV_S_OK;
+}
+
+static long batch_rotate_sum(EvalObj* e, const u64* ct2, uint64_t sources, const uint32_t* src_index, uint64_t index_len, const int32_t* steps,
+                             const uint32_t* elts, void* keys, u64* out2, uint64_t groups, uint64_t terms, hipStream_t s) {
+  if (!ct2 || !out2 || !(steps || elts) || !as<KeysObj>(keys, kMagicKeys)) return HIPBFV_E_POINTER;
+  if (steps && !e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
+  if (!terms) return fail(HIPBFV_E_INVALIDARG, "a sum of rotations needs at least one term per group");
+  if (groups > 0xFFFFFFFFull || terms > 0xFFFFFFFFull) return fail(HIPBFV_E_INVALIDARG, "too many groups or terms");
+  if (src_index && !index_len) return fail(HIPBFV_E_INVALIDARG, "a source index table needs at least one entry");
+  const uint64_t count = groups * terms;
+  if (!src_index && sources != count) return fail(HIPBFV_E_INVALIDARG, "without a source index table there is one source per item: sources must equal groups * terms");
+  for (uint64_t i = 0; src_index && i < index_len; i++)
+    if (src_index[i] >= sources) return item_error(i, "the source index is not below `sources`");
+  std::vector<RowRotation> plan;
+  if (long hr = plan_rotate_sum(e->ctx->n(), steps, elts, terms, [&](u32 elt) { return key_or_null(keys, e, (elt - 1) >> 1) != nullptr; }, &plan)) return hr;
+  const size_t w = e->ctx->ct_words(2);
+  ALIAS_OR_RETURN(cts(out2, w, groups), {cts(ct2, w, sources)}, false);
+  if (!groups) return HIPBFV_S_OK;
+  const auto source_of = [&](uint64_t i) { return src_index ? (uint64_t)src_index[i % index_len] : i; };
+  // chain terms: every distinct (source, term's step) once, gathered per term into a stage and rotated by the chain of
+  // hipbfv_batch_rotate_rows; slot_of[t]: source -> the stage slot of its rotation
+  std::vector<std::map<uint64_t, size_t>> slot_of(terms);
+  size_t slots = 0, largest = 0;
+  for (uint64_t t = 0; t < terms; t++) {
+    if (plan[t].kind != RowRotation::kChain) continue;
+    const uint64_t same = steps ? std::find(steps, steps + t, steps[t]) - steps : t;  // (a step listed twice shares its rotations)
+    if (same < t) continue;
+    for (uint64_t i = 0; i < count; i++)
+      if (steps[i % terms] == steps[t]) slot_of[t].emplace(source_of(i), 0);
+    for (auto& kv : slot_of[t]) kv.second = slots++;
+    largest = std::max(largest, slot_of[t].size());
+  }
+  ScratchGuard sg(e->ev->scratch(), (slots + largest) * w * sizeof(u64), s);
+  if (slots && !sg.p) return from_status(kOutOfMemory);
+  u64* rotated = (u64*)sg.p;
+  u64* in_stage = rotated + slots * w;
+  u32* const watch = Evaluator::watch_status();
+  {
+    WatchScope quiet(nullptr);  // (the stage's item numbers mean nothing to the caller: the sums are noted once, under group numbers)
+    for (uint64_t t = 0; t < terms; t++) {
+      if (slot_of[t].empty()) continue;
+      std::vector<uint64_t> items;
+      for (const auto& kv : slot_of[t]) items.push_back(kv.first);
+      if (copy_items(in_stage, ct2, nullptr, w, w, items, s) != hipSuccess) return from_status(kHipError);
+      if (long hr = batch_rotate_planned(e, plan[t], in_stage, keys, rotated + slot_of[t].begin()->second * w, items.size(), s)) return hr;
+    }
+  }
+  std::vector<Evaluator::RotSumItem> item(count);
+  std::vector<const u64*> key(terms, nullptr);
+  for (uint64_t t = 0; t < terms; t++)
+    if (plan[t].kind == RowRotation::kDirect) key[t] = key_or_null(keys, e, (plan[t].elt - 1) >> 1);
+  for (uint64_t i = 0; i < count; i++) {
+    const uint64_t t = i % terms;
+    if (plan[t].kind == RowRotation::kChain) {
+      const uint64_t first = std::find(steps, steps + t, steps[t]) - steps;
+      item[i] = Evaluator::RotSumItem{rotated + slot_of[first].at(source_of(i)) * w, 1u, nullptr};
+    } else {
+      item[i] = Evaluator::RotSumItem{ct2 + source_of(i) * w, plan[t].kind == RowRotation::kDirect ? plan[t].elt : 1u, key[t]};
+    }
+  }
+  WatchScope noted(watch);
+  return from_status(e->ev->rotate_sum(item.data(), out2, groups, terms, s));
+}
+
+long hipbfv_batch_rotate_rows_sum(void* h, const uint64_t* ct2, uint64_t sources, const uint32_t* src_index, uint64_t index_len, const int32_t* steps,
+                                  void* keys, uint64_t* out2, uint64_t groups, uint64_t terms, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!steps) return HIPBFV_E_POINTER;
+  return batch_rotate_sum(e, (const u64*)ct2, sources, src_index, index_len, steps, nullptr, keys, (u64*)out2, groups, terms, (hipStream_t)stream);
+HIPBFV_END
+
+long hipbfv_batch_apply_galois_sum(void* h, const uint64_t* ct2, uint64_t sources, const uint32_t* src_index, uint64_t index_len, const uint32_t* elts,
+                                   void* keys, uint64_t* out2, uint64_t groups, uint64_t terms, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!elts) return HIPBFV_E_POINTER;
+  return batch_rotate_sum(e, (const u64*)ct2, sources, src_index, index_len, nullptr, elts, keys, (u64*)out2, groups, terms, (hipStream_t)stream);
+HIPBFV_END
+
+// The plan of hipbfv_batch_rotate_rows_sum (include/hipbfv.h).  Host only.
+long hipbfv_debug_rotate_sum_plan(uint64_t n, const int32_t* steps, uint64_t terms, const uint32_t* present_elts, uint64_t num_present, uint64_t groups,
+                                  uint64_t chunk, int32_t* kind, uint32_t* elt, uint32_t* rounds, uint64_t* steps5, uint64_t capacity, uint64_t* count) HIPBFV_BEGIN
+  if ((!steps || !kind || !elt || !rounds) && terms) return HIPBFV_E_POINTER;
+  if ((!present_elts && num_present) || !count || (!steps5 && capacity)) return HIPBFV_E_POINTER;
+  if (n < 4 || n > (1u << 20) || (n & (n - 1))) return fail(HIPBFV_E_INVALIDARG, "the degree must be a power of two");
+  if (!chunk) return fail(HIPBFV_E_INVALIDARG, "terms and chunk must not be zero");
+  std::vector<RowRotation> plan;
+  if (long hr = plan_rotate_sum((u32)n, steps, nullptr, terms, [&](u32 g) { return std::find(present_elts, present_elts + num_present, g) != present_elts + num_present; },
+                                &plan))
+    return hr;
+  for (uint64_t t = 0; t < terms; t++) {
+    kind[t] = plan[t].kind;
+    elt[t] = plan[t].elt;
+    rounds[t] = plan[t].kind == RowRotation::kChain ? plan[t].hops : 0;
+  }
+  return hipbfv_debug_multiply_sum_plan(groups, terms, chunk, steps5, capacity, count);
+HIPBFV_END
+
 // ---- mixed-step rotation batches with one key set per client (include/hipbfv.h) ----
 // What hipbfv_batch_rotate_rows_items_keys / hipbfv_batch_apply_galois_items_keys do with every item, decided once per distinct
 // (key set, step) pair as hipbfv_batch_rotate_rows decides for a whole batch over that set: step 0 / element 1 copies (the set is

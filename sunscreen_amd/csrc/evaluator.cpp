@@ -153,7 +153,7 @@ NttPlan make_plan(u32 div, const std::vector<u32>& mods) {
 const char* kernel_name(int id) {
   static const char* names[kKernCount] = {"ntt_fwd",   "ntt_inv",    "behz_extend", "tensor",  "behz_floor_sk", "ks_decompose",
                                           "ks_mac",    "ks_moddown", "galois",      "eltwise", "plain",
-                                          "ks_head",    "ks_mid",      "ks_tail", "mul_head",      "mul_mid",
+                                          "ks_head",    "ks_mid",      "ks_tail", "ks_tail_sum", "mul_head",      "mul_mid",
                                           "mul_prep",  "mul_tail",   "mul_tail_sum"};
   return id >= 0 && id < kKernCount ? names[id] : "?";
 }
@@ -1136,6 +1136,141 @@ int Evaluator::apply_galois_items(const u64* ct2, const u32* elts, const u64* co
     }
   }
   return watch ? note_result(out2, 2, K, count, s) : (int)kOk;
+}
+
+Evaluator::RotSumLease::~RotSumLease() {
+  if (!ev) return;
+  if (host) ev->pinned_.release(host, s);
+  if (dev) ev->pool_.release(dev, s);
+}
+
+// out2[g] = sum_t apply_galois(items[g * terms + t]) (evaluator.hpp)
+int Evaluator::rotate_sum(const RotSumItem* items, u64* out2, size_t groups, size_t terms, hipStream_t s) {
+  const DevCtx& h = ctx_->host();
+  const u32 n = h.n, K = h.K, KK = h.KK;
+  if (!terms || !items) return kInvalidArg;
+  if (!groups) return kOk;
+  const size_t count = groups * terms;
+  // distinct elements > 1 in order of first appearance; kidx[i]: item i's entry, kKeyNone for an identity term
+  std::vector<u32> delt, kidx(count, kKeyNone);
+  std::vector<const u64*> dkey;
+  for (size_t i = 0; i < count; i++) {
+    const u32 e = items[i].elt;
+    if (!items[i].src || !(e & 1) || e >= 2 * n) return kInvalidArg;
+    if (e == 1) continue;
+    if (KK < 2 || !items[i].key) return kNoKey;
+    const size_t d = std::find(delt.begin(), delt.end(), e) - delt.begin();
+    if (d == delt.size()) delt.push_back(e), dkey.push_back(items[i].key);
+    kidx[i] = (u32)d;
+  }
+  if (h.logn > 15) return kUnsupported;
+  const size_t w = (size_t)2 * K * n;
+  const bool split = fuse_galois_ && h.logn >= 12 && h.logn <= 14 && ks_split_for(count);
+  // (the split kernels have the items on grid z; the whole-polynomial transforms of the other path have KK * K rows per item there)
+  const size_t chunk = std::max<size_t>(1, std::min<size_t>(chunk_ops_, split ? 65535 : 65535 / ((size_t)KK * K)));
+  size_t cc = 0;  // the items of the largest launch sequence
+  (void)plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) {
+    cc = std::max(cc, st.groups * st.terms);
+    return 0;
+  });
+  if (split) {
+    RotSumLease rl;
+    const size_t tab_bytes = ((size_t)dkey.size() * sizeof(u64*) + 15) & ~(size_t)15;
+    const size_t order_bytes = (count * sizeof(uint2) + 15) & ~(size_t)15;
+    const size_t bytes = tab_bytes + order_bytes + count * sizeof(RotTerm);
+    rl.ev = this;
+    rl.s = s;
+    rl.host = pinned_.acquire(bytes);
+    rl.dev = pool_.acquire(std::max<size_t>(bytes, (size_t)1 << 20), s);  // (one size class for the small tables, as stage_keymap's)
+    if (!rl.host || !rl.dev) return kOutOfMemory;
+    unsigned char* hb = static_cast<unsigned char*>(rl.host);
+    const u64** tab = reinterpret_cast<const u64**>(hb);
+    for (size_t k = 0; k < dkey.size(); k++) tab[k] = dkey[k];
+    uint2* order = reinterpret_cast<uint2*>(hb + tab_bytes);
+    RotTerm* rt = reinterpret_cast<RotTerm*>(hb + tab_bytes + order_bytes);
+    for (size_t i = 0; i < count; i++) rt[i] = RotTerm{items[i].src, kidx[i] == kKeyNone ? kGinvSkip : galois_inverse(items[i].elt, n), 0u};
+    const u32 nkeys = (u32)dkey.size();
+    std::vector<u32> start(nkeys + 2);
+    (void)plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) {
+      // counting sort of the sequence's items by key index, the identity terms last (stage_keymap)
+      const size_t first = st.group0 * terms + st.term0, c = st.groups * st.terms;
+      std::fill(start.begin(), start.end(), 0u);
+      for (size_t i = 0; i < c; i++) start[std::min(kidx[first + i], nkeys) + 1]++;
+      for (u32 k = 0; k <= nkeys; k++) start[k + 1] += start[k];
+      for (size_t i = 0; i < c; i++) {
+        const u32 k = kidx[first + i];
+        if (k < nkeys)
+          order[first + start[k]++] = make_uint2((u32)i, k);
+        else
+          order[first + start[nkeys]++] = make_uint2(0xFFFFFFFFu, 0u);
+      }
+      return 0;
+    });
+    HB_CHECK(hipMemcpyAsync(rl.dev, rl.host, bytes, hipMemcpyHostToDevice, s));
+    unsigned char* db = static_cast<unsigned char*>(rl.dev);
+    rl.km.keys = reinterpret_cast<const u64* const*>(db);
+    rl.km.order = reinterpret_cast<const uint2*>(db + tab_bytes);
+    rl.terms = reinterpret_cast<const RotTerm*>(db + tab_bytes + order_bytes);
+    ScratchGuard sg(pool_, cc * ks_scratch_words() * sizeof(u64), s);
+    if (!sg.p) return kOutOfMemory;
+    const bool mixed = h.ks_ni != 0;
+    const int rc = plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) -> int {
+      const size_t first = st.group0 * terms + st.term0, c = st.groups * st.terms;
+      u64* T = (u64*)sg.p;
+      u64* ACC = T + c * (size_t)KK * K * n;
+      if (std::any_of(kidx.begin() + first, kidx.begin() + first + c, [](u32 k) { return k != kKeyNone; })) {
+        HB_LAUNCH(kKernKsHead, c, launch_ks_head_src(ctx_->dev(), h.tw_fwd, h.logn, (int)h.pack_ks, mixed, K, rl.terms + first, T, c, s));
+        HB_LAUNCH(kKernKsMid, c, launch_ks_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, h, T, nullptr, ACC, c, s, KeyMap{rl.km.keys, rl.km.order + first}));
+      }
+      HB_LAUNCH(kKernKsTailSum, c, launch_ks_tail_sum(ctx_->dev(), h.tw_inv, h.logn, (int)h.pack_ks, mixed, K, ACC, rl.terms + first, out2 + st.group0 * w, st.groups, st.terms, st.accumulate, s));
+      return kOk;
+    });
+    if (rc) return rc;
+    return note_result(out2, 2, K, groups, s);
+  }
+  // elsewhere: a sequence's sources gathered into a stage, rotated by the existing calls, folded by the element-wise add: the same words
+  struct Pinned {
+    PinnedPool& pool;
+    hipStream_t s;
+    void* p;
+    ~Pinned() {
+      if (p) pool.release(p, s);
+    }
+  } tabs{pinned_, s, pinned_.acquire(count * sizeof(u64*))};
+  if (!tabs.p) return kOutOfMemory;
+  const u64** src = static_cast<const u64**>(tabs.p);
+  std::vector<u32> elts(count);
+  std::vector<const u64*> keys(count);
+  for (size_t i = 0; i < count; i++) src[i] = items[i].src, elts[i] = items[i].elt, keys[i] = items[i].key;
+  ScratchGuard sg(pool_, 2 * cc * w * sizeof(u64), s);
+  if (!sg.p) return kOutOfMemory;
+  u64* in_stage = (u64*)sg.p;
+  u64* stage = in_stage + cc * w;
+  const size_t polys = (size_t)2 * K;
+  {
+    WatchScope quiet(nullptr);  // the stage's item numbers mean nothing to the caller: the sums are noted once, below
+    const int rc = plan_multiply_sum(groups, terms, chunk, [&](const MulSumStep& st) -> int {
+      const size_t first = st.group0 * terms + st.term0, c = st.groups * st.terms;
+      HB_CHECK(launch_gather_items(src + first, in_stage, w, c, s));
+      if (int r = apply_galois_items(in_stage, elts.data() + first, keys.data() + first, stage, c, s, false)) return r;
+      for (size_t g = 0; g < st.groups; g++) {
+        u64* o = out2 + (st.group0 + g) * w;
+        const u64* t0 = stage + g * st.terms * w;
+        size_t t = 0;
+        if (!st.accumulate) {
+          if (st.terms == 1)
+            HB_CHECK(hipMemcpyAsync(o, t0, w * sizeof(u64), hipMemcpyDeviceToDevice, s));
+          else
+            HB_LAUNCH(kKernEltwise, polys, launch_eltwise(ctx_->dev(), n, t0, t0 + w, o, polys, 0, s));
+          t = st.terms == 1 ? 1 : 2;
+        }
+        for (; t < st.terms; t++) HB_LAUNCH(kKernEltwise, polys, launch_eltwise(ctx_->dev(), n, o, t0 + t * w, o, polys, 0, s));
+      }
+      return kOk;
+    });
+    if (rc) return rc;
+  }
+  return note_result(out2, 2, K, groups, s);
 }
 
 static int eltwise_chunks(Profiler& prof_, const DevCtx* dev, u32 n, u32 K, const u64* a, const u64* b, u64* out, size_t residue_polys, int mode,

@@ -63,6 +63,7 @@ enum KernelId : int {
   kKernKsHead,
   kKernKsMid,
   kKernKsTail,
+  kKernKsTailSum,  // the summing tail of rotate_sum; kinds are read by name, so it sits beside its twin
   kKernMulHead,
   kKernMulMid,
   kKernMulPrep,  // the forward half alone (prepared multiplicands); kinds are read by name, so it sits beside its twin
@@ -377,6 +378,20 @@ class Evaluator {
   // scattered to out2 from the stage they finished in.  Host arrays; the results are not noted (the caller does).
   int apply_galois_rounds(const u64* ct2, u64* out2, const u64* items, size_t nitems, u32 rounds, const u32* elts, const u64* const* keys,
                           const u32* key_ids, hipStream_t s);
+  // Sums of rotations: out2[g] (u64[groups][2][K][N]) = the sum over t < terms of apply_galois(items[g * terms + t].src, .elt), word for
+  // word what apply_galois + add give in any order.  items: a HOST array of groups * terms entries -- src: the term's source ciphertext
+  // (device, u64[2][K][N]; many items may name one), elt: its Galois element (1: the source itself enters the sum), key: the device key
+  // of elt (not read for element 1).  No source may overlap out2.  Everything is validated before the first launch.
+  // Where the split kernels run (ks_split_for(groups * terms), fused automorphisms, N = 4096 ... 16384) every launch sequence of
+  // plan_multiply_sum over chunk_ops() is ONE ks_head_src -> ks_mid -> ks_tail_sum: a term is finished and added inside the last kernel
+  // and never written.  Elsewhere a sequence's terms are gathered, rotated by apply_galois_items into a stage and folded by the
+  // element-wise add.  The sums are noted under GROUP numbers; a transparent term inside a sum that is not transparent is not seen.
+  struct RotSumItem {
+    const u64* src;
+    u32 elt;
+    const u64* key;
+  };
+  int rotate_sum(const RotSumItem* items, u64* out2, size_t groups, size_t terms, hipStream_t s);
   int mod_switch_next(const u64* ct, u32 size, u64* out, size_t count, hipStream_t s);  // out has K-1 residues per polynomial
   int add(const u64* a, const u64* b, u64* out, u32 size, size_t count, hipStream_t s);
   int sub(const u64* a, const u64* b, u64* out, u32 size, size_t count, hipStream_t s);
@@ -465,6 +480,17 @@ class Evaluator {
     ~WeightLease();
   };
   int stage_weights(const int32_t* weights, size_t terms, hipStream_t s, WeightLease& lease);
+  // the device tables of one rotate_sum call on the split path, staged as stage_keymap's: the key table, every launch sequence's items
+  // sorted by key (numbered from 0 within the sequence, at order + the sequence's first item) and the RotTerm entry of every item
+  struct RotSumLease {
+    Evaluator* ev = nullptr;
+    hipStream_t s = nullptr;
+    void* dev = nullptr;
+    void* host = nullptr;
+    KeyMap km;
+    const RotTerm* terms = nullptr;
+    ~RotSumLease();
+  };
   // the device table of one call over prepared multiplicands, staged as stage_keymap's: rows -- u32[items], item i's index (the split
   // path: launch_mul_mid_shared reads idx + first item of the launch); otherwise a pointer table, item i's canonical ciphertext
   // (launch_gather_items)

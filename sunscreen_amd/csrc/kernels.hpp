@@ -62,11 +62,27 @@ hipError_t launch_ntt_split(const DevCtx* ctx, const MulOp* tw, u32 logn, u64* d
 constexpr u32 kGinvSkip = 0xFFFFFFFFu;
 hipError_t launch_ks_head(const DevCtx* ctx, const MulOp* twf, u32 logn, int pack, bool mixed, u32 K, const u64* target, size_t tstride, u64* T, size_t ops, hipStream_t s,
                           u32 ginv = 0, const u32* ginv_tab = nullptr);
+// One term of a sum of rotations (Evaluator::rotate_sum), a DEVICE table entry per item of a launch: the source ciphertext
+// (u64[2][K][N], anywhere on the device: many items may name one) and g^-1 of the term's Galois element.  ginv == kGinvSkip: an
+// identity term -- no key switch, the summing tail adds the source's words as they are.
+struct RotTerm {
+  const u64* src;
+  u32 ginv;
+  u32 reserved;
+};
+// launch_ks_head with item i's target read from terms[i].src through terms[i].ginv (N = 4096 ... 16384); identity terms are left out
+hipError_t launch_ks_head_src(const DevCtx* ctx, const MulOp* twf, u32 logn, int pack, bool mixed, u32 K, const RotTerm* terms, u64* T, size_t ops, hipStream_t s);
 // h: the host copy of *ctx (its residue lists' counts: ks_nd 8-byte FP64 rows, ks_ndp packed FP64 rows, ks_ni integer rows)
 hipError_t launch_ks_mid(const DevCtx* ctx, const MulOp* twf, const MulOp* twi, u32 logn, const DevCtx& h, const u64* T, const u64* key, u64* ACC, size_t ops,
                          hipStream_t s, KeyMap km = KeyMap{});
 hipError_t launch_ks_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, int pack, bool mixed, const u64* ACC, const u64* base, size_t bstride, u32 base_mask, const u64* extra, u64* out2,
                           size_t ops, hipStream_t s, u32 ginv = 0, const u32* ginv_tab = nullptr);
+// The summing tail of a sum of rotations: ACC = the accumulators of groups * terms items (item g * terms + t), terms = their table;
+// out2[g] (u64[groups][2][K][N], canonical) = the sum over group g's terms of what launch_ks_tail writes for a rotation of terms[.].src
+// -- its own mod-down, its own sigma_g(c0) -- and, for an identity term, of the source's words.  accumulate: added onto the rows
+// already in out2.  groups <= 65535 (grid z); no source may overlap out2.
+hipError_t launch_ks_tail_sum(const DevCtx* ctx, const MulOp* twi, u32 logn, int pack, bool mixed, u32 K, const u64* ACC, const RotTerm* terms, u64* out2, size_t groups,
+                              size_t nterms, bool accumulate, hipStream_t s);
 // split BEHZ multiply (2 x 2 -> 3), K <= 4
 // Per-member operands of a MERGED multiply launch (graph executor): item i of the launch is item (first + i) % per of member
 // (first + i) / per, whose two factors are read where they are (u64[per][2][K][N] each; b == a for a squaring launch) -- no gather

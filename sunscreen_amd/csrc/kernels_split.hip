@@ -1003,6 +1003,88 @@ __global__ __launch_bounds__(kHeadThreads) void ks_head_kernel(const DevCtx* __r
   }
 }
 
+// ks_head_kernel's body for ks_head_src_kernel below: one workgroup's share of one item's head -- digit row J at `src`, read through
+// sigma_g, the rows T[I][J] of the item behind `rout`.  A copy and not a shared function: with the body moved out of ks_head_kernel
+// the compiler allocated that kernel's registers differently (same instructions, other fingerprints).
+template <int L, int PACK, bool MIXED>
+__device__ __forceinline__ void ks_head_item(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twf_base, const u64* __restrict__ src, const BufRsrc rout,
+                                             u32 ginv, u32 t, u32 J) {
+  using G = EdgeGeom<L>;
+  constexpr int NC = G::HEAD_NC;
+  constexpr u32 N = 1u << L;
+  const u32 K = ctx->K, KK = ctx->KK;
+  const u64 qJ = ctx->mod[J].q;
+  u64 x[NC];
+  if (ginv) {
+    // a rotation's key switch: the target is sigma_g(c1), read THROUGH the automorphism (SEAL apply_galois, seal_fhe/src/
+    // bfv_evaluator.rs:177-247) instead of from a rotated copy: coefficient j of sigma_g(p) is +- p[j * g^-1 mod 2N] (minus when the
+    // index passes N).  An 8-byte gather per value; every line is used in full by the workgroups of this row (L2 absorbs it).
+#pragma unroll
+    for (int k = 0; k < NC; k++) x[k] = galois_gather<L>(buf_rsrc(src), 0u, EdgeSplitIdx<L>::head_in_lane(t, k) + EdgeSplitIdx<L>::head_uni(k), ginv, qJ);
+  } else {
+#pragma unroll
+    for (int k = 0; k < NC; k++) x[k] = ld_head_in<L>(buf_row(buf_rsrc(src), 0), t, k);
+  }
+  for (u32 I = 0; I < KK; I++) {
+    const DevMod& dm = ctx->mod[I];
+    if constexpr (MIXED) {
+      if (!residue_is_f64(dm)) {
+        const ArithI ai(dm);
+        const bool shrink = qJ > dm.q;
+        u64 w[NC];
+#pragma unroll
+        for (int k = 0; k < NC; k++) w[k] = shrink ? reduce64(x[k], dm) : x[k];
+        head_fwd_owned<ArithI, L>(ai, w, twf_base + (size_t)I * N, t);
+#pragma unroll
+        for (int k = 0; k < NC; k++) st_head_out<L>(buf_row(rout, ((size_t)I * K + J) * N), t, k, w[k]);
+        continue;
+      }
+    }
+    const ArithD ar(dm);
+    const double* tw = reinterpret_cast<const double*>(twf_base + (size_t)I * N);
+    const bool need_reduce = qJ > dm.q;
+    double v[NC];
+#pragma unroll
+    for (int k = 0; k < NC; k++) {
+      if constexpr (MIXED) {
+        // the digit may come from an integer-policy prime (up to 61 bits): from_u64 is exact below 2^52 only, so bring it
+        // under q_I with integer arithmetic first
+        v[k] = ar.from_u64(need_reduce ? reduce64(x[k], dm) : x[k]);
+      } else {
+        const double d = ar.from_u64(x[k]);
+        v[k] = need_reduce ? ar.reduce(d) : d;
+      }
+    }
+    head_fwd_owned<ArithD, L>(ar, v, tw, t);
+    ks_head_store<L, PACK>(ctx, dm, ar, buf_row(rout, ((size_t)I * K + J) * N), I, t, v);
+  }
+}
+
+// The head of a sum of rotations (Evaluator::rotate_sum): item `op` of the launch reads its digit rows from ITS OWN source ciphertext,
+// terms[op].src (kernels.hpp RotTerm), through its own g^-1 -- many items may name one source, nothing is replicated.  An identity
+// term (ginv == kGinvSkip) has no key switch: its workgroups leave at once.  A sibling of the TAB instantiations of ks_head_kernel, on
+// their grid and in their XCD row order; those keep their names and their instructions.
+template <int L, int PACK, bool MIXED>
+__global__ __launch_bounds__(kHeadThreads) void ks_head_src_kernel(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twf_base,
+                                                                   const RotTerm* __restrict__ terms, double* __restrict__ T) {
+  constexpr u32 N = 1u << L;
+  u32 bx = blockIdx.x, J = blockIdx.y, op = blockIdx.z;
+  if (KS_XCD_ROWS) {
+    const u32 TB = gridDim.x, R = gridDim.y * gridDim.z;
+    if ((R & 7u) == 0u) {
+      const u32 d = blockIdx.x + TB * (blockIdx.y + gridDim.y * blockIdx.z), q = d >> 3, row = (q / TB) * 8u + (d & 7u);
+      bx = q % TB, J = row % gridDim.y, op = row / gridDim.y;
+    }
+  }
+  const RotTerm term = terms[op];
+  if (term.ginv == kGinvSkip) return;
+  const u32 t = bx * kHeadThreads + threadIdx.x;
+  const u32 K = ctx->K, KK = ctx->KK;
+  const u64* src = term.src + (size_t)(K + J) * N;  // c1 of the source: the key switch's target
+  const BufRsrc rout = buf_rsrc(T + (size_t)op * KK * K * N);
+  ks_head_item<L, PACK, MIXED>(ctx, twf_base, src, rout, term.ginv, t, J);
+}
+
 // Per-item keys (kernels.hpp KeyMap; multi-tenant batches).  The launch's items arrive sorted by key in km.order; each XCD takes a
 // CONTIGUOUS run of that order (position w = xcd * per + slot % per) instead of every eighth item, so the key rows of one client
 // are fetched into one XCD's L2 (two at a run boundary) and not into all eight.  Wave-uniform: two scalar loads per workgroup.
@@ -3009,6 +3091,218 @@ __global__ __launch_bounds__(kHeadThreads, (kTailSumThroughOut<KMAX> ? 2 : 1)) v
 }
 
 // -------------------------------------------------------------------------------------------------
+// key switch, summing tail (Evaluator::rotate_sum: out[g] = sum_t rotate(source of term t, element of term t)).
+// grid: (N/4/256, 2 polynomials, groups); ACC = [groups][terms][2][KK][N], terms = RotTerm[groups][terms] (kernels.hpp).
+// Per thread a loop over the group's terms.  Each term is FINISHED as ks_tail_kernel finishes an item -- the special-prime row first,
+// then rows 0 ... K - 1 with the inverse tail stages and its OWN mod-down (the floor of a sum is not the sum of the floors: the terms
+// cannot share one), sigma_g(c0) gathered from the term's SOURCE through the term's g^-1 -- and the finished canonical residues are
+// added with add_mod, which is exact in any order.  An identity term (ginv == kGinvSkip: step 0, or a term rotated beforehand into
+// a stage) has no accumulator rows and contributes its source's words alone.  A term's rows are never written.
+// A sibling of ks_tail_kernel and no template parameter of it: its instantiations keep their names and their instructions.
+// Sizing as mul_tail_sum_kernel's: K <= 4 sums in registers and stores every word once; the 8-prime form sums THROUGH the output rows
+// (kTailSumThroughOut: K * 4 more live words beside the tail's own would cost the second wave per SIMD), the first term onto zeros --
+// the descriptor without records.  The XCD row order of the gathering tail applies, with groups in place of items.
+// -------------------------------------------------------------------------------------------------
+// rows 0 ... K - 1 of one term: unrolled where the sums are registers (their index must be a constant), a loop otherwise
+template <int KMAX, class Row>
+__device__ __forceinline__ void ks_tail_sum_rows(u32 K, Row&& row) {
+  if constexpr (kTailSumThroughOut<KMAX>) {
+#pragma unroll 1
+    for (u32 J = 0; J < K; J++) row(J);
+  } else {
+#pragma unroll
+    for (int J = 0; J < KMAX; J++)
+      if ((u32)J < K) row(J);
+  }
+}
+
+// one term: sink(J, q_J, r) receives the four finished canonical residues of row J (coefficients EdgeGeom::tail_out(t, k))
+template <int L, bool PACK, bool MIXED, int KMAX, class Sink>
+__device__ __forceinline__ void ks_tail_sum_term(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base, const double* __restrict__ acc,
+                                                 const RotTerm term, u32 c, u32 t, Sink&& sink) {
+  constexpr u32 N = 1u << L;
+  const u32 K = ctx->K, KK = ctx->KK;
+  if (term.ginv == kGinvSkip) {  // (wave-uniform)
+    const BufRsrc rs = buf_rsrc(term.src + (size_t)c * K * N);
+    ks_tail_sum_rows<KMAX>(K, [&](auto J) {
+      u64 r[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) r[k] = ld_tail_out<L>(buf_row(rs, (size_t)J * N), t, k);
+      sink((u32)J, ctx->mod[J].q, r);
+    });
+    return;
+  }
+  const u32 ginv = term.ginv;
+  const BufRsrc racc = buf_rsrc(acc);
+  const BufRsrc rbase = buf_rsrc_opt(term.src, c == 0);  // the base is (sigma_g(c0), 0): polynomial 1 has none
+  if constexpr (!MIXED) {
+    const DevMod& sp = ctx->mod[KK - 1];
+    double v[4], tld[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = nat_unpack<PACK>(nat_fetch_tail<L, PACK, NtSites<L>::tail_ld>(buf_row(racc, (size_t)(KK - 1) * N), t, k));
+    tail_special_d<L>(ctx, sp, v, reinterpret_cast<const double*>(twi_base + (size_t)(KK - 1) * N), t, tld);
+    const u64 qsp = sp.q;
+    NatRaw<PACK> cur[4];  // row J + 1 is requested before row J is finished (ks_tail_kernel)
+#pragma unroll
+    for (int k = 0; k < 4; k++) cur[k] = nat_fetch_tail<L, PACK, NtSites<L>::tail_ld>(buf_row(racc, 0), t, k);
+    ks_tail_sum_rows<KMAX>(K, [&](auto J) {
+      const u32 Jn = (u32)J + 1 < K ? (u32)J + 1 : (u32)J;
+      NatRaw<PACK> nxt[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) nxt[k] = nat_fetch_tail<L, PACK, NtSites<L>::tail_ld>(buf_row(racc, (size_t)Jn * N), t, k);
+      const DevMod& mj = ctx->mod[J];
+      const ArithD ar(mj);
+      u64 bw[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        bw[k] = galois_gather<L>(rbase, (u32)((size_t)J * N * 8u), EdgeSplitIdx<L>::tail_out_lane(t, k) + EdgeSplitIdx<L>::tail_uni(k), ginv, mj.q);
+      double w[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) w[k] = nat_unpack<PACK>(cur[k]);
+      tail_inv_scale_fold_d<L, false>(ar, w, reinterpret_cast<const double*>(twi_base + (size_t)J * N), ctx->tail_fold_key[J], mj.split_inv_mask, t);
+      const MulOpD iw = ctx->inv_qsp_mod_q_d[J];
+      const double hf = ctx->qsp_half_mod_q_d[J];
+      const bool p_above_q = qsp > mj.q;
+      u64 r[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) r[k] = ArithD::to_bits(mod_down_d(ar.q, ar.qinv, iw.w, iw.wq, hf, p_above_q, w[k], tld[k], ArithD::from_u64(bw[k])));
+      sink((u32)J, mj.q, r);
+#pragma unroll
+      for (int k = 0; k < 4; k++) cur[k] = nxt[k];
+    });
+    return;
+  }
+  // MIXED (8-byte rows of either policy): the special prime's residue as a canonical u64
+  u64 tl[4];
+  {
+    const DevMod& sp = ctx->mod[KK - 1];
+    if (!residue_is_f64(sp)) {
+      const ArithI ai(sp);
+      u64 w[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) w[k] = ld_tail_in<L>(buf_row(racc, (size_t)(KK - 1) * N), t, k);
+      tail_inv_owned<ArithI, L>(ai, w, twi_base + (size_t)(KK - 1) * N, 0u, t);
+#pragma unroll
+      for (int k = 0; k < 4; k++) tl[k] = add_mod(ai.scale_canonical(w[k], sp.ninv), ctx->qsp_half, sp.q);
+    } else {
+      const ArithD ar(sp);
+      double v[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = nat_unpack<PACK>(nat_fetch_tail<L, PACK, NtSites<L>::tail_ld>(buf_row(racc, (size_t)(KK - 1) * N), t, k));
+      tail_inv_owned<ArithD, L>(ar, v, reinterpret_cast<const double*>(twi_base + (size_t)(KK - 1) * N), sp.split_inv_mask, t);
+#pragma unroll
+      for (int k = 0; k < 4; k++) tl[k] = add_mod(ar.scale_canonical(v[k], sp.ninv_d), ctx->qsp_half, sp.q);
+    }
+  }
+  const u64 qsp = ctx->mod[KK - 1].q;
+  u64 cur[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) cur[k] = ld_tail_in<L>(buf_row(racc, 0), t, k);
+  ks_tail_sum_rows<KMAX>(K, [&](auto J) {
+    const u32 Jn = (u32)J + 1 < K ? (u32)J + 1 : (u32)J;
+    u64 nxt[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) nxt[k] = ld_tail_in<L>(buf_row(racc, (size_t)Jn * N), t, k);
+    const DevMod& mj = ctx->mod[J];
+    u64 bw[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      bw[k] = galois_gather<L>(rbase, (u32)((size_t)J * N * 8u), EdgeSplitIdx<L>::tail_out_lane(t, k) + EdgeSplitIdx<L>::tail_uni(k), ginv, mj.q);
+    u64 av[4];
+    if (!residue_is_f64(mj)) {
+      const ArithI ai(mj);
+      u64 w[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) w[k] = cur[k];
+      tail_inv_owned<ArithI, L>(ai, w, twi_base + (size_t)J * N, 0u, t);
+#pragma unroll
+      for (int k = 0; k < 4; k++) av[k] = ai.scale_canonical(w[k], mj.ninv);
+    } else {
+      const ArithD ar(mj);
+      double v[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = __longlong_as_double((long long)cur[k]);
+      tail_inv_owned<ArithD, L>(ar, v, reinterpret_cast<const double*>(twi_base + (size_t)J * N), mj.split_inv_mask, t);
+#pragma unroll
+      for (int k = 0; k < 4; k++) av[k] = ar.scale_canonical(v[k], mj.ninv_d);
+    }
+    u64 r[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      u64 tk = qsp > mj.q ? reduce64(tl[k], mj) : tl[k];
+      tk = sub_mod(tk, ctx->qsp_half_mod_q[J], mj.q);
+      u64 d = sub_mod(av[k], tk, mj.q);
+      d = mul_shoup(d, ctx->inv_qsp_mod_q[J], mj.q);
+      r[k] = add_mod(bw[k], d, mj.q);
+    }
+    sink((u32)J, mj.q, r);
+#pragma unroll
+    for (int k = 0; k < 4; k++) cur[k] = nxt[k];
+  });
+}
+
+template <int L, bool PACK, bool MIXED, int KMAX>
+__global__ __launch_bounds__(kHeadThreads) void ks_tail_sum_kernel(const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base,
+                                                                   const double* __restrict__ ACC, const RotTerm* __restrict__ terms,
+                                                                   u64* __restrict__ out, u32 nterms, u32 accumulate) {
+  constexpr u32 N = 1u << L;
+  u32 bx = blockIdx.x, c = blockIdx.y, group = blockIdx.z;
+  if (KS_XCD_ROWS) {  // the workgroups of one (polynomial, group) on one XCD (ks_head_kernel): they gather sigma_g(c0) all over a row
+    const u32 TB = gridDim.x, R = gridDim.y * gridDim.z;
+    if ((R & 7u) == 0u) {
+      const u32 d = blockIdx.x + TB * (blockIdx.y + gridDim.y * blockIdx.z), q = d >> 3, row = (q / TB) * 8u + (d & 7u);
+      bx = q % TB, c = row % gridDim.y, group = row / gridDim.y;
+    }
+  }
+  const u32 t = bx * kHeadThreads + threadIdx.x;
+  const u32 K = ctx->K, KK = ctx->KK;
+  u64* o = out + ((size_t)group * 2 + c) * K * N;
+  const BufRsrc ro = buf_rsrc(o);
+  const RotTerm* tab = terms + (size_t)group * nterms;
+  const size_t term_words = (size_t)2 * KK * N;
+  const double* acc = ACC + ((size_t)group * nterms * 2 + c) * KK * N;
+  if constexpr (kTailSumThroughOut<KMAX>) {
+#pragma unroll 1
+    for (u32 term = 0; term < nterms; term++, acc += term_words) {
+      const BufRsrc rin = buf_rsrc_opt(o, (accumulate | term) != 0);
+      ks_tail_sum_term<L, PACK, MIXED, KMAX>(ctx, twi_base, acc, tab[term], c, t, [&](u32 J, u64 q, const u64(&r)[4]) {
+        u64 w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = ld_tail_out<L>(buf_row(rin, (size_t)J * N), t, k);
+#pragma unroll
+        for (int k = 0; k < 4; k++) st_tail_out<L>(buf_row(ro, (size_t)J * N), t, k, add_mod(w[k], r[k], q));
+      });
+    }
+    return;
+  } else {
+    u64 sum[4][KMAX];
+    {
+      // without `accumulate` the descriptor has no records: the loads return 0 and touch no memory (buf_rsrc_opt)
+      const BufRsrc rin = buf_rsrc_opt(o, accumulate != 0);
+#pragma unroll
+      for (int i = 0; i < KMAX; i++) {
+        const BufRow row = buf_row(rin, (size_t)((u32)i < K ? (u32)i : K - 1) * N);
+#pragma unroll
+        for (int k = 0; k < 4; k++) sum[k][i] = ld_tail_out<L>(row, t, k);
+      }
+    }
+#pragma unroll 1
+    for (u32 term = 0; term < nterms; term++, acc += term_words) {
+      ks_tail_sum_term<L, PACK, MIXED, KMAX>(ctx, twi_base, acc, tab[term], c, t, [&](u32 J, u64 q, const u64(&r)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) sum[k][J] = add_mod(sum[k][J], r[k], q);
+      });
+    }
+#pragma unroll
+    for (int i = 0; i < KMAX; i++)
+      if ((u32)i < K) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) st_tail_out<L>(buf_row(ro, (size_t)i * N), t, k, sum[k][i]);
+      }
+  }
+}
+
+// -------------------------------------------------------------------------------------------------
 // multiply + relinearize, last kernel: ks_tail whose base ciphertext (c0, c1 of the product) is computed in place from the
 // multiply's intermediates D instead of being read back: c0 and c1 never travel through HBM (1 MB of the 12 MB a mul+relin
 // moves at N = 8192).  Thread t of polynomial c owns the same coefficients {t + k*N/4} in both halves.  All-FP64 contexts
@@ -3613,6 +3907,55 @@ hipError_t launch_ks_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, int pac
     KS_DISPATCH(ks_tail_tab_t, ctx, twi, pack_ks, mixed, ACC, base, bstride, base_mask, extra, out2, ops, s, ginv_tab)
   }
   KS_DISPATCH(ks_tail_t, ctx, twi, pack_ks, mixed, ACC, base, bstride, base_mask, extra, out2, ops, s, ginv)
+}
+
+// sums of rotations (Evaluator::rotate_sum): the head over per-item sources and the summing tail, N = 4096 ... 16384
+template <int L>
+static hipError_t ks_head_src_t(const DevCtx* ctx, const MulOp* twf, int pack, bool mixed, u32 K, const RotTerm* terms, u64* T, size_t ops, hipStream_t s) {
+  if constexpr (L == 15) return hipErrorInvalidValue;
+  else {
+    const dim3 grid(EdgeGeom<L>::HEAD_THREADS / kHeadThreads, K, (unsigned)ops);
+    if (mixed)
+      ks_head_src_kernel<L, 0, true><<<grid, kHeadThreads, 0, s>>>(ctx, twf, terms, reinterpret_cast<double*>(T));
+    else if (pack == 2) {
+      if constexpr (L >= 13) ks_head_src_kernel<L, 2, false><<<grid, kHeadThreads, 0, s>>>(ctx, twf, terms, reinterpret_cast<double*>(T));
+      else return hipErrorInvalidValue;  // (context.cpp: beside pack_mul == 2 only)
+    } else if (pack)
+      ks_head_src_kernel<L, 1, false><<<grid, kHeadThreads, 0, s>>>(ctx, twf, terms, reinterpret_cast<double*>(T));
+    else
+      ks_head_src_kernel<L, 0, false><<<grid, kHeadThreads, 0, s>>>(ctx, twf, terms, reinterpret_cast<double*>(T));
+    return hipGetLastError();
+  }
+}
+hipError_t launch_ks_head_src(const DevCtx* ctx, const MulOp* twf, u32 logn, int pack, bool mixed, u32 K, const RotTerm* terms, u64* T, size_t ops, hipStream_t s) {
+  if (!terms || !ops || ops > 65535) return hipErrorInvalidValue;
+  KS_DISPATCH(ks_head_src_t, ctx, twf, pack, mixed, K, terms, T, ops, s)
+}
+
+template <int L, int KMAX>
+static hipError_t ks_tail_sum_k(const DevCtx* ctx, const MulOp* twi, int pack_ks, bool mixed, const u64* ACC, const RotTerm* terms, u64* out2, size_t groups,
+                                size_t nterms, bool accumulate, hipStream_t s) {
+  const dim3 grid((1u << L) / 4 / kHeadThreads, 2, (unsigned)groups);
+  const double* acc = reinterpret_cast<const double*>(ACC);
+  if (mixed)
+    ks_tail_sum_kernel<L, false, true, KMAX><<<grid, kHeadThreads, 0, s>>>(ctx, twi, acc, terms, out2, (u32)nterms, accumulate ? 1u : 0u);
+  else if (pack_ks == 1)  // (2 = per key prime: the rows of T only, the accumulator rows are doubles)
+    ks_tail_sum_kernel<L, true, false, KMAX><<<grid, kHeadThreads, 0, s>>>(ctx, twi, acc, terms, out2, (u32)nterms, accumulate ? 1u : 0u);
+  else
+    ks_tail_sum_kernel<L, false, false, KMAX><<<grid, kHeadThreads, 0, s>>>(ctx, twi, acc, terms, out2, (u32)nterms, accumulate ? 1u : 0u);
+  return hipGetLastError();
+}
+template <int L>
+static hipError_t ks_tail_sum_t(const DevCtx* ctx, const MulOp* twi, int pack_ks, bool mixed, u32 K, const u64* ACC, const RotTerm* terms, u64* out2, size_t groups,
+                                size_t nterms, bool accumulate, hipStream_t s) {
+  if constexpr (L == 15) return hipErrorInvalidValue;
+  else if (K <= 4) return ks_tail_sum_k<L, 4>(ctx, twi, pack_ks, mixed, ACC, terms, out2, groups, nterms, accumulate, s);
+  else return ks_tail_sum_k<L, 8>(ctx, twi, pack_ks, mixed, ACC, terms, out2, groups, nterms, accumulate, s);
+}
+hipError_t launch_ks_tail_sum(const DevCtx* ctx, const MulOp* twi, u32 logn, int pack_ks, bool mixed, u32 K, const u64* ACC, const RotTerm* terms, u64* out2,
+                              size_t groups, size_t nterms, bool accumulate, hipStream_t s) {
+  if (!terms || !groups || groups > 65535 || !nterms || nterms > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  KS_DISPATCH(ks_tail_sum_t, ctx, twi, pack_ks, mixed, K, ACC, terms, out2, groups, nterms, accumulate, s)
 }
 
 template <int L>

@@ -154,3 +154,14 @@ def matrix_product(ev, ma, mb, m: int, k: int, n: int, relin_keys=None):
     if relin_keys is None:
         return ev.multiply_sum_prepared(ma, a_index, mb, b_index, m * n, k)
     return ev.multiply_sum_relin_prepared(ma, a_index, mb, b_index, relin_keys, m * n, k)
+
+
+def window_sum(ev, x, w: int, galois_keys):
+    """The moving-window sum out[g] = sum over t < w of rotate_rows(x[g], t), one ciphertext per group, in one call: every term is
+    finished and added inside the key switch's last kernel (BatchEvaluator.rotate_rows_sum with src_index[i] = i // w); x is not
+    replicated.  galois_keys holds the keys of the steps 1 ... w - 1, or the power-of-two keys of their NAF chains.  Returns
+    int64[groups, 2, K, N]: the words of rotate_rows and add."""
+    if w <= 0:
+        raise ValueError("window_sum needs a window of at least one slot")
+    groups = x.shape[0]
+    return ev.rotate_rows_sum(x, list(range(w)), galois_keys, groups=groups, src_index=[i // w for i in range(groups * w)])
