@@ -377,6 +377,30 @@ long hipbfv_batch_rotate_rows_sum(void *evaluator, const uint64_t *ct2, uint64_t
 long hipbfv_batch_apply_galois_sum(void *evaluator, const uint64_t *ct2, uint64_t sources, const uint32_t *src_index,
                                    uint64_t index_len, const uint32_t *galois_elts, void *galois_keys, uint64_t *out2,
                                    uint64_t groups, uint64_t terms, void *stream);
+/* Weighted sums of rotations: out2[g] = sum_t w_t (.) rotate_rows(source of item g * terms + t, steps[t]) -- a convolution or FIR
+ * filter with taps (1, -2, 1), a finite difference x - rotate(x, 1), a weighted moving window, the signed giant-step sum of a baby-step
+ * / giant-step product -- with the weight applied to every finished term inside the key switch's last kernel, just before it is added.
+ * (.) is hipbfv_batch_multiply_sum_weighted's: every word of residue row i of the finished term is multiplied by (w_t mod q_i), taken
+ * canonically in [0, q_i), mod q_i -- the words of |w| hipbfv_batch_add calls of the rotated ciphertext, after hipbfv_batch_negate
+ * when w < 0.  No transform pair, no plaintext; a weight multiplies its term's noise by |w|.
+ *  - weights: a HOST array of `terms` int32_t, shared by every group as `steps` is, read before the call returns.  Any int32_t is a
+ *    weight, 0, -1, INT32_MIN and INT32_MAX included.  A zero weight is a weight like any other: its term is planned, validated,
+ *    refused and launched as any other term.
+ *  - Everything hipbfv_batch_rotate_rows_sum (hipbfv_batch_apply_galois_sum) promises carries over: layouts, src_index, every refusal
+ *    before anything is launched, copied or written, no in-place form, chunks and slices, transparent results under GROUP numbers.
+ *    In addition a NULL `weights` is HIPBFV_E_POINTER.
+ *  - A table of all ones is not staged and runs the unweighted launches: the same words and the same profiler counts.  All weights
+ *    0, or (+1, -1) on the same (source, step), give a transparent sum, reported under its group number.  The same (source, step)
+ *    listed twice with weights w1 and w2 contributes (w1 + w2).
+ *  - Launches: the unweighted call's, with the weighted sibling of the summing tail (same profiler kind, same units); chain terms
+ *    stay deduplicated per distinct (source, step) and are weighted where they enter the sum.  Off the split path the staged terms
+ *    are folded by one scaled accumulate per term and group (out = (out or 0) + w * x): the same bits. */
+long hipbfv_batch_rotate_rows_sum_weighted(void *evaluator, const uint64_t *ct2, uint64_t sources, const uint32_t *src_index,
+                                           uint64_t index_len, const int32_t *steps, const int32_t *weights, void *galois_keys,
+                                           uint64_t *out2, uint64_t groups, uint64_t terms, void *stream);
+long hipbfv_batch_apply_galois_sum_weighted(void *evaluator, const uint64_t *ct2, uint64_t sources, const uint32_t *src_index,
+                                            uint64_t index_len, const uint32_t *galois_elts, const int32_t *weights,
+                                            void *galois_keys, uint64_t *out2, uint64_t groups, uint64_t terms, void *stream);
 /* Per-key batches (multi-tenant serving).  The reference hands the keys over with every call
  * (sunscreen_runtime/src/run.rs:100-105: `relin_keys: &Option<&RelinearizationKeys>`, `galois_keys: &Option<&GaloisKeys>`;
  * runtime.rs:310-327), so a server that batches the calls of many clients holds one key set per client.  These are the

@@ -678,6 +678,20 @@ class BFVEvaluator : public detail::Handle<Evaluator_Destroy, detail::no_copy> {
     check(hipbfv_batch_apply_galois_sum(h_, ct, sources, src_index.empty() ? nullptr : src_index.data(), src_index.size(), galois_elts.data(), gk.get_handle(), out,
                                         groups, galois_elts.size(), stream));
   }
+  // Weighted sums of rotations (hipbfv.h): out[g] = sum_t weights[t] (.) rotate_rows(...), one int32_t per term shared by every group
+  // (weights.size() == steps.size()), applied to every finished term inside the key switch's last kernel.
+  void rotate_rows_sum_weighted(const uint64_t* ct, uint64_t sources, const std::vector<uint32_t>& src_index, const std::vector<int32_t>& steps,
+                                const std::vector<int32_t>& weights, const GaloisKeys& gk, uint64_t* out, uint64_t groups, void* stream = nullptr) const {
+    if (weights.size() != steps.size()) throw std::invalid_argument("one weight per term");
+    check(hipbfv_batch_rotate_rows_sum_weighted(h_, ct, sources, src_index.empty() ? nullptr : src_index.data(), src_index.size(), steps.data(), weights.data(),
+                                                gk.get_handle(), out, groups, steps.size(), stream));
+  }
+  void apply_galois_sum_weighted(const uint64_t* ct, uint64_t sources, const std::vector<uint32_t>& src_index, const std::vector<uint32_t>& galois_elts,
+                                 const std::vector<int32_t>& weights, const GaloisKeys& gk, uint64_t* out, uint64_t groups, void* stream = nullptr) const {
+    if (weights.size() != galois_elts.size()) throw std::invalid_argument("one weight per term");
+    check(hipbfv_batch_apply_galois_sum_weighted(h_, ct, sources, src_index.empty() ? nullptr : src_index.data(), src_index.size(), galois_elts.data(),
+                                                 weights.data(), gk.get_handle(), out, groups, galois_elts.size(), stream));
+  }
   // ... with one key set per client: item i by its own element / step through keys[key_index[i]].  An entry of `keys` that no rotating
   // item names may be nullptr.
   void apply_galois_items_keys(const uint64_t* ct, const std::vector<uint32_t>& galois_elts, const std::vector<const GaloisKeys*>& keys,

@@ -149,6 +149,31 @@ impl<'e> BatchEvaluator<'e> {
             bindgen::hipbfv_batch_apply_galois_sum(self.h(), a.ptr, a.count, ip, n, galois_elts.as_ptr(), gk.get_handle(), out.ptr, out.count, galois_elts.len() as u64, self.stream)
         })
     }
+    // ---- weighted sums of rotations: out[g] = sum_t weights[t] (.) rotate_rows(source of item g * terms + t, steps[t]) ----
+    // The two calls above with one weight per term, shared by every group (any i32): every word of residue row i of the finished term
+    // times (weights[t] mod q_i), applied inside the key switch's last kernel just before the term is added (include/hipbfv.h).
+    fn weights_ok(weights: &[i32], terms: usize) -> Result<()> {
+        if weights.len() != terms {
+            return Err(crate::Error::InvalidArgument(format!("{} weights for {} terms", weights.len(), terms)));
+        }
+        Ok(())
+    }
+    pub fn rotate_rows_sum_weighted(&self, a: DeviceBatch, src_index: Option<&[u32]>, steps: &[i32], weights: &[i32], gk: &GaloisKeys, out: DeviceBatch) -> Result<()> {
+        Self::sum_sources_ok(&a, &out, steps.len(), src_index)?;
+        Self::weights_ok(weights, steps.len())?;
+        let (ip, n) = src_index.map_or((std::ptr::null(), 0u64), |idx| (idx.as_ptr(), idx.len() as u64));
+        check(unsafe {
+            bindgen::hipbfv_batch_rotate_rows_sum_weighted(self.h(), a.ptr, a.count, ip, n, steps.as_ptr(), weights.as_ptr(), gk.get_handle(), out.ptr, out.count, steps.len() as u64, self.stream)
+        })
+    }
+    pub fn apply_galois_sum_weighted(&self, a: DeviceBatch, src_index: Option<&[u32]>, galois_elts: &[u32], weights: &[i32], gk: &GaloisKeys, out: DeviceBatch) -> Result<()> {
+        Self::sum_sources_ok(&a, &out, galois_elts.len(), src_index)?;
+        Self::weights_ok(weights, galois_elts.len())?;
+        let (ip, n) = src_index.map_or((std::ptr::null(), 0u64), |idx| (idx.as_ptr(), idx.len() as u64));
+        check(unsafe {
+            bindgen::hipbfv_batch_apply_galois_sum_weighted(self.h(), a.ptr, a.count, ip, n, galois_elts.as_ptr(), weights.as_ptr(), gk.get_handle(), out.ptr, out.count, galois_elts.len() as u64, self.stream)
+        })
+    }
     // ---- per-key batches ----
     // The reference hands the keys over with every call (`sunscreen_runtime/src/run.rs:100-105`: `relin_keys:
     // &Option<&RelinearizationKeys>`, `galois_keys: &Option<&GaloisKeys>`; `runtime.rs:310-327`): a server that batches the

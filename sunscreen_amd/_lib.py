@@ -121,6 +121,8 @@ _SIGNATURES = {
     "hipbfv_batch_rotate_rows_items": [vp, vp, C.POINTER(C.c_int32), vp, vp, u64, vp],
     "hipbfv_batch_rotate_rows_sum": [vp, vp, u64, C.POINTER(C.c_uint32), u64, C.POINTER(C.c_int32), vp, vp, u64, u64, vp],
     "hipbfv_batch_apply_galois_sum": [vp, vp, u64, C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32), vp, vp, u64, u64, vp],
+    "hipbfv_batch_rotate_rows_sum_weighted": [vp, vp, u64, C.POINTER(C.c_uint32), u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, u64, u64, vp],
+    "hipbfv_batch_apply_galois_sum_weighted": [vp, vp, u64, C.POINTER(C.c_uint32), u64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp, vp, u64, u64, vp],
     "hipbfv_batch_rotate_columns": [vp, vp, vp, vp, u64, vp],
     "hipbfv_batch_relinearize_keys": [vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64, vp],
     "hipbfv_batch_multiply_relin_keys": [vp, vp, vp, vpp, u64, C.POINTER(C.c_uint32), vp, u64, vp],

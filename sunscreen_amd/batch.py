@@ -200,6 +200,40 @@ class BatchEvaluator:
                                                          _ptr(out), groups, elts.size, _stream()))
         return out
 
+    # ---- weighted sums of rotations: the weight applied to every finished term just before it is added (include/hipbfv.h) ----
+    @staticmethod
+    def _rotation_weights(weights, terms: int):
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.int64))
+        assert w.shape == (terms,), (w.shape, terms)
+        assert w.size == 0 or (int(w.min()) >= -(1 << 31) and int(w.max()) < (1 << 31)), "a weight is an int32"
+        return np.ascontiguousarray(w.astype(np.int32))
+
+    def rotate_rows_sum_weighted(self, ct: torch.Tensor, steps, weights, gk: GaloisKeys, groups: int | None = None, src_index=None,
+                                 out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[g] = sum over t of weights[t] (.) rotate_rows(ct[source of item g * len(steps) + t], steps[t]): every word of residue row i
+        of the rotated term times (weights[t] mod q_i) -- the bits of |w| add calls, after negate when w < 0.  weights: len(steps) integers
+        in the int32 range, shared by every group.  Sources, groups and src_index as rotate_rows_sum."""
+        st = np.ascontiguousarray(np.asarray(steps, dtype=np.int32))
+        assert st.ndim == 1, st.shape
+        wt = self._rotation_weights(weights, st.size)
+        groups, ip, n, out, _keep = self._rotation_sum_args(ct, st.size, groups, src_index, out)
+        _check(_lib.load().hipbfv_batch_rotate_rows_sum_weighted(self._h, _ptr(ct), ct.shape[0], ip, n, st.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                 wt.ctypes.data_as(C.POINTER(C.c_int32)), gk.get_handle(), _ptr(out), groups, st.size,
+                                                                 _stream()))
+        return out
+
+    def apply_galois_sum_weighted(self, ct: torch.Tensor, galois_elts, weights, gk: GaloisKeys, groups: int | None = None, src_index=None,
+                                  out: torch.Tensor | None = None) -> torch.Tensor:
+        """rotate_rows_sum_weighted with term t given by its Galois element (odd, below 2 N; 1: the source itself)."""
+        elts = np.ascontiguousarray(np.asarray(galois_elts, dtype=np.uint32))
+        assert elts.ndim == 1, elts.shape
+        wt = self._rotation_weights(weights, elts.size)
+        groups, ip, n, out, _keep = self._rotation_sum_args(ct, elts.size, groups, src_index, out)
+        _check(_lib.load().hipbfv_batch_apply_galois_sum_weighted(self._h, _ptr(ct), ct.shape[0], ip, n, elts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                  wt.ctypes.data_as(C.POINTER(C.c_int32)), gk.get_handle(), _ptr(out), groups, elts.size,
+                                                                  _stream()))
+        return out
+
     # ---- per-key batches (multi-tenant: the reference passes the keys per call, sunscreen_runtime/src/run.rs:100-105) ----
     @staticmethod
     def _key_sets(key_sets, key_index, count: int):

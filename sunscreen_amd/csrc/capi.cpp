@@ -2194,7 +2194,7 @@ static long plan_rotate_sum(u32 n, const int32_t* steps, const uint32_t* elts, u
 }
 
 static long batch_rotate_sum(EvalObj* e, const u64* ct2, uint64_t sources, const uint32_t* src_index, uint64_t index_len, const int32_t* steps,
-                             const uint32_t* elts, void* keys, u64* out2, uint64_t groups, uint64_t terms, hipStream_t s) {
+                             const uint32_t* elts, void* keys, u64* out2, uint64_t groups, uint64_t terms, hipStream_t s, const int32_t* weights = nullptr) {
   if (!ct2 || !out2 || !(steps || elts) || !as<KeysObj>(keys, kMagicKeys)) return HIPBFV_E_POINTER;
   if (steps && !e->ctx->batching()) return fail(HIPBFV_COR_E_INVALIDOPERATION, "encryption parameters do not support batching");
   if (!terms) return fail(HIPBFV_E_INVALIDARG, "a sum of rotations needs at least one term per group");
@@ -2252,7 +2252,7 @@ static long batch_rotate_sum(EvalObj* e, const u64* ct2, uint64_t sources, const
     }
   }
   WatchScope noted(watch);
-  return from_status(e->ev->rotate_sum(item.data(), out2, groups, terms, s));
+  return from_status(e->ev->rotate_sum(item.data(), out2, groups, terms, s, weights));
 }
 
 long hipbfv_batch_rotate_rows_sum(void* h, const uint64_t* ct2, uint64_t sources, const uint32_t* src_index, uint64_t index_len, const int32_t* steps,
@@ -2267,6 +2267,23 @@ long hipbfv_batch_apply_galois_sum(void* h, const uint64_t* ct2, uint64_t source
   EVAL_OR_RETURN(h);
   if (!elts) return HIPBFV_E_POINTER;
   return batch_rotate_sum(e, (const u64*)ct2, sources, src_index, index_len, nullptr, elts, keys, (u64*)out2, groups, terms, (hipStream_t)stream);
+HIPBFV_END
+
+// ---- weighted sums of rotations: out2[g] = sum_t w_t (.) rotate(source of item g * terms + t, steps[t]) (include/hipbfv.h) ----
+// The calls above with one more host array; the plan, the chain terms (one rotation per distinct (source, step), whatever its weights)
+// and every refusal are theirs.  The weight is applied where a term enters the sum (Evaluator::rotate_sum).
+long hipbfv_batch_rotate_rows_sum_weighted(void* h, const uint64_t* ct2, uint64_t sources, const uint32_t* src_index, uint64_t index_len, const int32_t* steps,
+                                           const int32_t* weights, void* keys, uint64_t* out2, uint64_t groups, uint64_t terms, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!steps || !weights) return HIPBFV_E_POINTER;
+  return batch_rotate_sum(e, (const u64*)ct2, sources, src_index, index_len, steps, nullptr, keys, (u64*)out2, groups, terms, (hipStream_t)stream, weights);
+HIPBFV_END
+
+long hipbfv_batch_apply_galois_sum_weighted(void* h, const uint64_t* ct2, uint64_t sources, const uint32_t* src_index, uint64_t index_len, const uint32_t* elts,
+                                            const int32_t* weights, void* keys, uint64_t* out2, uint64_t groups, uint64_t terms, void* stream) HIPBFV_BEGIN
+  EVAL_OR_RETURN(h);
+  if (!elts || !weights) return HIPBFV_E_POINTER;
+  return batch_rotate_sum(e, (const u64*)ct2, sources, src_index, index_len, nullptr, elts, keys, (u64*)out2, groups, terms, (hipStream_t)stream, weights);
 HIPBFV_END
 
 // The plan of hipbfv_batch_rotate_rows_sum (include/hipbfv.h).  Host only.

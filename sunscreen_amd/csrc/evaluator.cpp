@@ -1145,7 +1145,7 @@ Evaluator::RotSumLease::~RotSumLease() {
 }
 
 // out2[g] = sum_t apply_galois(items[g * terms + t]) (evaluator.hpp)
-int Evaluator::rotate_sum(const RotSumItem* items, u64* out2, size_t groups, size_t terms, hipStream_t s) {
+int Evaluator::rotate_sum(const RotSumItem* items, u64* out2, size_t groups, size_t terms, hipStream_t s, const int32_t* weights) {
   const DevCtx& h = ctx_->host();
   const u32 n = h.n, K = h.K, KK = h.KK;
   if (!terms || !items) return kInvalidArg;
@@ -1164,6 +1164,10 @@ int Evaluator::rotate_sum(const RotSumItem* items, u64* out2, size_t groups, siz
     kidx[i] = (u32)d;
   }
   if (h.logn > 15) return kUnsupported;
+  WeightLease wl;  // (after every refusal: nothing is copied for a call that is refused)
+  if (weights)
+    if (int rc = stage_weights(weights, terms, s, wl)) return rc;
+  const MulOp* const wt = wl.wt;
   const size_t w = (size_t)2 * K * n;
   const bool split = fuse_galois_ && h.logn >= 12 && h.logn <= 14 && ks_split_for(count);
   // (the split kernels have the items on grid z; the whole-polynomial transforms of the other path have KK * K rows per item there)
@@ -1222,7 +1226,7 @@ int Evaluator::rotate_sum(const RotSumItem* items, u64* out2, size_t groups, siz
         HB_LAUNCH(kKernKsHead, c, launch_ks_head_src(ctx_->dev(), h.tw_fwd, h.logn, (int)h.pack_ks, mixed, K, rl.terms + first, T, c, s));
         HB_LAUNCH(kKernKsMid, c, launch_ks_mid(ctx_->dev(), h.tw_fwd, h.tw_inv, h.logn, h, T, nullptr, ACC, c, s, KeyMap{rl.km.keys, rl.km.order + first}));
       }
-      HB_LAUNCH(kKernKsTailSum, c, launch_ks_tail_sum(ctx_->dev(), h.tw_inv, h.logn, (int)h.pack_ks, mixed, K, ACC, rl.terms + first, out2 + st.group0 * w, st.groups, st.terms, st.accumulate, s));
+      HB_LAUNCH(kKernKsTailSum, c, launch_ks_tail_sum(ctx_->dev(), h.tw_inv, h.logn, (int)h.pack_ks, mixed, K, ACC, rl.terms + first, out2 + st.group0 * w, st.groups, st.terms, st.accumulate, s, wt ? wt + st.term0 * K : nullptr));
       return kOk;
     });
     if (rc) return rc;
@@ -1256,6 +1260,12 @@ int Evaluator::rotate_sum(const RotSumItem* items, u64* out2, size_t groups, siz
       for (size_t g = 0; g < st.groups; g++) {
         u64* o = out2 + (st.group0 + g) * w;
         const u64* t0 = stage + g * st.terms * w;
+        if (wt) {
+          // the weighted fold: out = (out or 0) + w_t * term, one scaled accumulate per term
+          for (size_t t = 0; t < st.terms; t++)
+            HB_LAUNCH(kKernEltwise, polys, launch_scaled_accumulate(ctx_->dev(), n, t || st.accumulate ? o : nullptr, t0 + t * w, wt + (st.term0 + t) * K, o, polys, s));
+          continue;
+        }
         size_t t = 0;
         if (!st.accumulate) {
           if (st.terms == 1)

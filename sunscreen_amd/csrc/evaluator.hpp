@@ -391,7 +391,12 @@ class Evaluator {
     u32 elt;
     const u64* key;
   };
-  int rotate_sum(const RotSumItem* items, u64* out2, size_t groups, size_t terms, hipStream_t s);
+  // weights (optional): a HOST array of `terms` int32_t shared by every group, read before the call returns and staged once on s
+  // (stage_weights, as multiply_sum_weighted's) -- out2[g] = sum_t w_t (.) apply_galois(...), every finished canonical residue of term t,
+  // row i multiplied by (w_t mod q_i) just before it is added: in ks_tail_sum_weighted_kernel on the split path (a slice that starts at
+  // term0 reads the table from row term0), by one scaled_accumulate per term and group elsewhere.  Identity terms are weighted as any
+  // other; a zero weight is a weight like any other.  All weights 1: the unweighted launches.
+  int rotate_sum(const RotSumItem* items, u64* out2, size_t groups, size_t terms, hipStream_t s, const int32_t* weights = nullptr);
   int mod_switch_next(const u64* ct, u32 size, u64* out, size_t count, hipStream_t s);  // out has K-1 residues per polynomial
   int add(const u64* a, const u64* b, u64* out, u32 size, size_t count, hipStream_t s);
   int sub(const u64* a, const u64* b, u64* out, u32 size, size_t count, hipStream_t s);

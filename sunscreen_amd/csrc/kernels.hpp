@@ -81,8 +81,10 @@ hipError_t launch_ks_tail(const DevCtx* ctx, const MulOp* twi, u32 logn, int pac
 // out2[g] (u64[groups][2][K][N], canonical) = the sum over group g's terms of what launch_ks_tail writes for a rotation of terms[.].src
 // -- its own mod-down, its own sigma_g(c0) -- and, for an identity term, of the source's words.  accumulate: added onto the rows
 // already in out2.  groups <= 65535 (grid z); no source may overlap out2.
+// wt (optional): a DEVICE table MulOp[nterms][K] of this launch's weights (evaluator.hpp weight_residues) -- every finished residue of
+// term t, row J is multiplied by wt[t * K + J] just before it is added (ks_tail_sum_weighted_kernel), identity terms included.
 hipError_t launch_ks_tail_sum(const DevCtx* ctx, const MulOp* twi, u32 logn, int pack, bool mixed, u32 K, const u64* ACC, const RotTerm* terms, u64* out2, size_t groups,
-                              size_t nterms, bool accumulate, hipStream_t s);
+                              size_t nterms, bool accumulate, hipStream_t s, const MulOp* wt = nullptr);
 // split BEHZ multiply (2 x 2 -> 3), K <= 4
 // Per-member operands of a MERGED multiply launch (graph executor): item i of the launch is item (first + i) % per of member
 // (first + i) / per, whose two factors are read where they are (u64[per][2][K][N] each; b == a for a squaring launch) -- no gather

@@ -3302,6 +3302,83 @@ __global__ __launch_bounds__(kHeadThreads) void ks_tail_sum_kernel(const DevCtx*
   }
 }
 
+// The weighted summing tail (Evaluator::rotate_sum with weights: out[g] = sum_t w_t (.) rotate(term t)): ks_tail_sum_kernel with every
+// finished canonical residue r of term `term`, row J replaced by r * wt[term][J] mod q_J just before it is added -- identity terms as
+// any other, and in the through-output form the first term too, which lands weighted on the descriptor without records.  wt =
+// MulOp[nterms][K] of this launch's terms (the weight mod q_J, canonical, and its Shoup quotient), indexed by the term and the row only:
+// wave-uniform, scalar loads.  A sibling and not a template parameter: ks_tail_sum_kernel's instantiations keep their names and their
+// instructions (as mul_tail_sum_weighted_kernel beside mul_tail_sum_kernel).
+// Form: the 8-prime instantiations sum through the output rows as their twins do, and so does the packed all-FP64 body at K <= 4:
+// its unweighted twin holds its sums in 95 VGPRs, one below the step from five waves per SIMD to four; with the weight's product
+// the register form takes 97 (four waves), and held to five waves by a bound it spills 8 bytes per lane.  Through the output rows it
+// takes 49 VGPRs, no scratch.  The 8-byte FP64 and the integer-policy bodies keep their sums in registers at
+// their twins' waves.
+template <bool PACK, bool MIXED, int KMAX>
+constexpr bool kTailSumWeightedThroughOut = kTailSumThroughOut<KMAX> || (PACK && !MIXED);
+template <int L, bool PACK, bool MIXED, int KMAX>
+__global__ __launch_bounds__(kHeadThreads) void ks_tail_sum_weighted_kernel(
+    const DevCtx* __restrict__ ctx, const MulOp* __restrict__ twi_base, const double* __restrict__ ACC, const RotTerm* __restrict__ terms,
+    u64* __restrict__ out, const MulOp* __restrict__ wt, u32 nterms, u32 accumulate) {
+  constexpr u32 N = 1u << L;
+  u32 bx = blockIdx.x, c = blockIdx.y, group = blockIdx.z;
+  if (KS_XCD_ROWS) {  // (ks_tail_sum_kernel)
+    const u32 TB = gridDim.x, R = gridDim.y * gridDim.z;
+    if ((R & 7u) == 0u) {
+      const u32 d = blockIdx.x + TB * (blockIdx.y + gridDim.y * blockIdx.z), q = d >> 3, row = (q / TB) * 8u + (d & 7u);
+      bx = q % TB, c = row % gridDim.y, group = row / gridDim.y;
+    }
+  }
+  const u32 t = bx * kHeadThreads + threadIdx.x;
+  const u32 K = ctx->K, KK = ctx->KK;
+  u64* o = out + ((size_t)group * 2 + c) * K * N;
+  const BufRsrc ro = buf_rsrc(o);
+  const RotTerm* tab = terms + (size_t)group * nterms;
+  const size_t term_words = (size_t)2 * KK * N;
+  const double* acc = ACC + ((size_t)group * nterms * 2 + c) * KK * N;
+  if constexpr (kTailSumWeightedThroughOut<PACK, MIXED, KMAX>) {
+#pragma unroll 1
+    for (u32 term = 0; term < nterms; term++, acc += term_words) {
+      const BufRsrc rin = buf_rsrc_opt(o, (accumulate | term) != 0);
+      const MulOp* __restrict__ wrow = wt + (size_t)term * K;
+      ks_tail_sum_term<L, PACK, MIXED, KMAX>(ctx, twi_base, acc, tab[term], c, t, [&](u32 J, u64 q, const u64(&r)[4]) {
+        const MulOp wj = wrow[J];
+        u64 w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = ld_tail_out<L>(buf_row(rin, (size_t)J * N), t, k);
+#pragma unroll
+        for (int k = 0; k < 4; k++) st_tail_out<L>(buf_row(ro, (size_t)J * N), t, k, add_mod(w[k], mul_shoup(r[k], wj, q), q));
+      });
+    }
+    return;
+  } else {
+    u64 sum[4][KMAX];
+    {
+      const BufRsrc rin = buf_rsrc_opt(o, accumulate != 0);
+#pragma unroll
+      for (int i = 0; i < KMAX; i++) {
+        const BufRow row = buf_row(rin, (size_t)((u32)i < K ? (u32)i : K - 1) * N);
+#pragma unroll
+        for (int k = 0; k < 4; k++) sum[k][i] = ld_tail_out<L>(row, t, k);
+      }
+    }
+#pragma unroll 1
+    for (u32 term = 0; term < nterms; term++, acc += term_words) {
+      const MulOp* __restrict__ wrow = wt + (size_t)term * K;
+      ks_tail_sum_term<L, PACK, MIXED, KMAX>(ctx, twi_base, acc, tab[term], c, t, [&](u32 J, u64 q, const u64(&r)[4]) {
+        const MulOp wj = wrow[J];
+#pragma unroll
+        for (int k = 0; k < 4; k++) sum[k][J] = add_mod(sum[k][J], mul_shoup(r[k], wj, q), q);
+      });
+    }
+#pragma unroll
+    for (int i = 0; i < KMAX; i++)
+      if ((u32)i < K) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) st_tail_out<L>(buf_row(ro, (size_t)i * N), t, k, sum[k][i]);
+      }
+  }
+}
+
 // -------------------------------------------------------------------------------------------------
 // multiply + relinearize, last kernel: ks_tail whose base ciphertext (c0, c1 of the product) is computed in place from the
 // multiply's intermediates D instead of being read back: c0 and c1 never travel through HBM (1 MB of the 12 MB a mul+relin
@@ -3934,9 +4011,18 @@ hipError_t launch_ks_head_src(const DevCtx* ctx, const MulOp* twf, u32 logn, int
 
 template <int L, int KMAX>
 static hipError_t ks_tail_sum_k(const DevCtx* ctx, const MulOp* twi, int pack_ks, bool mixed, const u64* ACC, const RotTerm* terms, u64* out2, size_t groups,
-                                size_t nterms, bool accumulate, hipStream_t s) {
+                                size_t nterms, bool accumulate, hipStream_t s, const MulOp* wt) {
   const dim3 grid((1u << L) / 4 / kHeadThreads, 2, (unsigned)groups);
   const double* acc = reinterpret_cast<const double*>(ACC);
+  if (wt) {  // the weighted sibling: the same choice of body
+    if (mixed)
+      ks_tail_sum_weighted_kernel<L, false, true, KMAX><<<grid, kHeadThreads, 0, s>>>(ctx, twi, acc, terms, out2, wt, (u32)nterms, accumulate ? 1u : 0u);
+    else if (pack_ks == 1)
+      ks_tail_sum_weighted_kernel<L, true, false, KMAX><<<grid, kHeadThreads, 0, s>>>(ctx, twi, acc, terms, out2, wt, (u32)nterms, accumulate ? 1u : 0u);
+    else
+      ks_tail_sum_weighted_kernel<L, false, false, KMAX><<<grid, kHeadThreads, 0, s>>>(ctx, twi, acc, terms, out2, wt, (u32)nterms, accumulate ? 1u : 0u);
+    return hipGetLastError();
+  }
   if (mixed)
     ks_tail_sum_kernel<L, false, true, KMAX><<<grid, kHeadThreads, 0, s>>>(ctx, twi, acc, terms, out2, (u32)nterms, accumulate ? 1u : 0u);
   else if (pack_ks == 1)  // (2 = per key prime: the rows of T only, the accumulator rows are doubles)
@@ -3947,15 +4033,15 @@ static hipError_t ks_tail_sum_k(const DevCtx* ctx, const MulOp* twi, int pack_ks
 }
 template <int L>
 static hipError_t ks_tail_sum_t(const DevCtx* ctx, const MulOp* twi, int pack_ks, bool mixed, u32 K, const u64* ACC, const RotTerm* terms, u64* out2, size_t groups,
-                                size_t nterms, bool accumulate, hipStream_t s) {
+                                size_t nterms, bool accumulate, hipStream_t s, const MulOp* wt) {
   if constexpr (L == 15) return hipErrorInvalidValue;
-  else if (K <= 4) return ks_tail_sum_k<L, 4>(ctx, twi, pack_ks, mixed, ACC, terms, out2, groups, nterms, accumulate, s);
-  else return ks_tail_sum_k<L, 8>(ctx, twi, pack_ks, mixed, ACC, terms, out2, groups, nterms, accumulate, s);
+  else if (K <= 4) return ks_tail_sum_k<L, 4>(ctx, twi, pack_ks, mixed, ACC, terms, out2, groups, nterms, accumulate, s, wt);
+  else return ks_tail_sum_k<L, 8>(ctx, twi, pack_ks, mixed, ACC, terms, out2, groups, nterms, accumulate, s, wt);
 }
 hipError_t launch_ks_tail_sum(const DevCtx* ctx, const MulOp* twi, u32 logn, int pack_ks, bool mixed, u32 K, const u64* ACC, const RotTerm* terms, u64* out2,
-                              size_t groups, size_t nterms, bool accumulate, hipStream_t s) {
+                              size_t groups, size_t nterms, bool accumulate, hipStream_t s, const MulOp* wt) {
   if (!terms || !groups || groups > 65535 || !nterms || nterms > 0xFFFFFFFFull) return hipErrorInvalidValue;
-  KS_DISPATCH(ks_tail_sum_t, ctx, twi, pack_ks, mixed, K, ACC, terms, out2, groups, nterms, accumulate, s)
+  KS_DISPATCH(ks_tail_sum_t, ctx, twi, pack_ks, mixed, K, ACC, terms, out2, groups, nterms, accumulate, s, wt)
 }
 
 template <int L>

@@ -165,3 +165,29 @@ def window_sum(ev, x, w: int, galois_keys):
         raise ValueError("window_sum needs a window of at least one slot")
     groups = x.shape[0]
     return ev.rotate_rows_sum(x, list(range(w)), galois_keys, groups=groups, src_index=[i // w for i in range(groups * w)])
+
+
+def convolution_terms(taps):
+    """(steps, weights) of a slot convolution with the integer taps taps[0 ... len - 1]: tap k is the step k with the weight taps[k], in
+    tap order, and a zero tap is dropped (it would cost a key switch and contribute nothing).  Pure Python; all taps zero gives two
+    empty lists."""
+    steps, weights = [], []
+    for k, tap in enumerate(taps):
+        tap = int(tap)
+        if tap:
+            steps.append(k)
+            weights.append(tap)
+    return steps, weights
+
+
+def convolve_slots(ev, x, taps, galois_keys):
+    """The slot convolution out[g] slot j = sum over k of taps[k] * x[g] slot (j + k), within each of the two rows (rotate_rows wraps
+    there), one ciphertext per group, in one call: BatchEvaluator.rotate_rows_sum_weighted over convolution_terms(taps) with
+    src_index[i] = i // terms; x is not replicated, no plaintext is multiplied and a tap multiplies its term's noise by |tap|.
+    galois_keys holds the keys of the non-zero taps' steps, or the power-of-two keys of their NAF chains.  Returns
+    int64[groups, 2, K, N]: the words of rotate_rows, negate and add."""
+    steps, weights = convolution_terms(taps)
+    if not steps:
+        raise ValueError("convolve_slots needs at least one non-zero tap")
+    groups, terms = x.shape[0], len(steps)
+    return ev.rotate_rows_sum_weighted(x, steps, weights, galois_keys, groups=groups, src_index=[i // terms for i in range(groups * terms)])
