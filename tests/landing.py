@@ -21,9 +21,20 @@ among D near j q / t, and a SMALL D never gives 0 or +1: its u' is at least 1). 
 form of (y_0, y_1) mod gamma: the nearest point of a two-dimensional lattice coset puts it on any target (land_gamma).
 tests/test_gpu_landing_multiply.py runs these.  Section I hands the same operands to the prepared-multiplicand products (in both
 roles: the oracle's multiply is symmetric) and to the weighted sums, with weight vectors chosen so that the sums of weighted residues
-pass through exactly q_i and q_i - 1 and end on 0, q_i - 1 and 1 (weighted_sum_case); tests/test_gpu_landing_shared.py runs those.
+pass through exactly q_i and q_i - 1 and end on 0, q_i - 1 and 1 (weighted_sum_case); tests/test_gpu_landing_shared.py runs those, and tests/test_gpu_landing_prepared_pair.py hands the operands of
+F, G and I to the products of TWO prepared operands.
 
-What the method cannot reach: polynomial 1 of a stand-alone key switch or rotation (it is ks1 alone), polynomial 1 of a product by
+Section J lands SUMS of rotations, sum_t w_t rotate(a_t, s_t) (tests/test_gpu_landing_rotate_sum.py runs them).  The caller owns c0
+of every rotated term and both polynomials of every identity term (step 0), and the key-switch part of a rotated term does not
+depend on its c0: every finished term's polynomial 0 is reachable (the edges in front of the mod-down's last reduction and of the
+weighting product), and so is every PARTIAL sum of polynomial 0, term after term, by solving the term's residue from the target and
+the sum so far, row by row (a row where w = 0 mod q_i has no inverse: the term adds 0 there and the target is the sum before it).
+Through an identity term the sum's polynomial 1 is reachable too: on the pattern after each identity term, on all zeros (a
+transparent sum) and on all zeros but one word.  land_rotation generalises land_galois to whatever rotation the oracle performs, a
+NAF chain over power-of-two keys included: c0 enters a chain of key switches by permutation and addition alone.
+
+What the method cannot reach: polynomial 1 of a stand-alone key switch or of a single rotated term (it is ks1 alone: in a sum of
+rotations it is reached only through the sum, by an identity term), polynomial 1 of a product by
 (1, 1) (a0 + a1 is not free once a0 and a1 are spent; it is compared all the same), and alpha_sk's own branch in the
 Shenoy-Kumaresan step (alpha is a small integer far from m_sk / 2 in any valid run)."""
 from __future__ import annotations
@@ -171,6 +182,7 @@ SETS = {
     "W2048": _create(2048, [60, 60, 60, 60]),                                  # 60-bit primes, K = 3
     "W4096": _create(4096, [60, 60, 60]),                                      # 60-bit primes, K = 2
     "S4096": _create(4096, [30, 30, 40, 40]),                                  # 30-bit primes at n = 4096: an int32 weight wraps them
+    "X8192": _create(8192, [50, 30, 30, 50, 50]),                              # K = 4 with 50-bit data primes: 8-byte FP64 rows
 }
 
 
@@ -1024,3 +1036,246 @@ def weighted_sum_case(L: "Landing", weights, groups: int = 2, terms: int = 3):
         return a, expected, events
 
     return L.cached(("weighted sum", weights, groups, terms), make)
+
+
+# -------------------------------------------------------------------------------------------------------- J: sums of rotations
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+ROTATION_SUM_MODES = ("terms", "partial", "ladder", "transparent", "almost", "gathers", "random")
+ROTATION_SUM_EVENTS = ("term 0", "term q - 1", "term 1", "term (q - 1) / 2", "term (q + 1) / 2", "weighted 0", "weighted q - 1", "raw q",
+                       "raw q - 1", "final 0", "final q - 1", "final 1", "zero weight")
+TRANSPARENT_GROUP = 1  # the group whose polynomial 1 the modes "transparent" and "almost" land; the others are "partial"
+STEPS_TWO_IDENTITIES = (1, 0, -3, 0)  # two identity terms, from different sources
+STEPS_IDENTITY_FIRST = (0, 1, -3)     # the landed first term is an identity term
+STEPS_CHAIN = (11, 0, 1, -13)         # under the power-of-two keys: 11 = [-1, -4, 16] and -13 = [-1, 4, -16] walk their NAF chains
+ROTATION_WEIGHTS = (None, (2, -1, 3, -2), (-1, 1, -1, 1), (0, -1, INT32_MIN, INT32_MAX))
+
+
+def galois_elements(L: "Landing") -> tuple:
+    """The Galois-element form's terms: an element that is no step's neighbour, the identity, the column element, the identity."""
+    return (2 * L.n - 5, 1, 2 * L.n - 1, 1)
+
+
+def rotation_modulus_weights(L: "Landing", terms: int) -> tuple:
+    """(2, q_1, -1, 1): the second weight is a 30-bit prime of the set, 0 modulo that prime alone (modulus_weights' idea)."""
+    q1 = next(q for q in L.primes if q.bit_length() == 30)
+    return (2, q1, -1, 1)[:terms]
+
+
+def rotation_sum_runs(L: "Landing") -> list:
+    """[(name, steps, weights, galois, pow2)]: the step and weight vectors of a parameter set, shared by tests/test_landing_cpu.py
+    (every one lands) and tests/test_gpu_landing_rotate_sum.py.  The first two carry every mode, the others terms, partial and
+    ladder (rotation_sum_modes).  The extreme vector's first weight is 0 in every row; the modulus-sized one (sets with a 30-bit prime) in one row alone."""
+    runs = [("two identities", STEPS_TWO_IDENTITIES, None, False, False),
+            ("two identities, small weights", STEPS_TWO_IDENTITIES, ROTATION_WEIGHTS[1], False, False),
+            ("identity first, +-1", STEPS_IDENTITY_FIRST, ROTATION_WEIGHTS[2][:3], False, False),
+            ("two identities, extreme weights", STEPS_TWO_IDENTITIES, ROTATION_WEIGHTS[3], False, False),
+            ("elements, +-1", galois_elements(L), ROTATION_WEIGHTS[2], True, False),
+            ("elements", galois_elements(L), None, True, False)]
+    if L.n >= 16384:
+        runs = runs[:3]  # (n = 16384 and above: the vectors that take another path there; the others stay with the smaller sets)
+    if any(q.bit_length() == 30 for q in L.primes):
+        runs.append(("two identities, a modulus-sized weight", STEPS_TWO_IDENTITIES, rotation_modulus_weights(L, 4), False, False))
+    if L.pid == "P1":
+        runs += [("chains", STEPS_CHAIN, None, False, True), ("chains, small weights", STEPS_CHAIN, ROTATION_WEIGHTS[1], False, True)]
+    return runs
+
+
+def rotation_sum_modes(run_index: int) -> tuple:
+    return ROTATION_SUM_MODES[:6] if run_index < 2 else ROTATION_SUM_MODES[:3]
+
+
+def _element(o, s: int, galois: bool) -> int:
+    return int(s) if galois else (1 if s == 0 else int(o.galois_elt_from_step(int(s))))
+
+
+def _rotate(o, ct, s: int, gk, galois: bool) -> np.ndarray:
+    """The oracle's rotation of one ciphertext by term s (a step of rotate_rows, or a Galois element); the identity is a copy."""
+    if _element(o, s, galois) == 1:
+        return np.array(ct, dtype=np.uint64)
+    return o.apply_galois(ct, int(s), gk) if galois else o.rotate_rows(ct, int(s), gk)
+
+
+def land_rotation(o, gk, step_or_elt: int, c1, T0, galois: bool = False, r=None):
+    """(ct2, expected): polynomial 0 of the oracle's rotation of ct2 == T0, for ANY rotation the oracle performs -- a direct key, a
+    NAF chain over the keys gk holds, the identity.  c0 enters a chain of key switches by permutation and addition alone, so
+    rotate((c0, c1))[0] = sigma_g(c0) + rotate((0, c1))[0] with g the total element, and c0 = sigma_{g^-1}(T0 - rotate((0, c1))[0]).
+    r: rotate((0, c1)) where the caller has it already."""
+    elt = _element(o, step_or_elt, galois)
+    if r is None:
+        r = _rotate(o, np.stack([np.zeros_like(c1), c1]), step_or_elt, gk, galois)
+    c0 = lin_mod(o.primes, [(1, T0), (-1, r[0])])
+    if elt != 1:
+        c0 = o.apply_galois_poly(c0, pow(elt, -1, 2 * o.n))
+    return np.stack([c0, c1]), np.stack([_u64(T0), r[1]])
+
+
+def pow2_elements(L: "Landing") -> list:
+    """The elements of every step +-2^i below n / 2 and of the column rotation: the holding "P" of tests/test_gpu_rotation_steps.py."""
+    h = L.n // 2
+    return sorted({L.o.galois_elt_from_step(s * (1 << i)) for i in range(h.bit_length() - 1) for s in (1, -1)} | {2 * L.n - 1})
+
+
+def rotation_sum_keys(L: "Landing", steps, galois: bool = False, pow2: bool = False) -> dict:
+    """The Galois keys of a case: the terms' own elements, or the power-of-two holding (a step without a key there is a chain)."""
+    if pow2:
+        return L.galois_keys(pow2_elements(L))
+    return L.galois_keys(sorted({_element(L.o, s, galois) for s in steps} - {1}))
+
+
+def scale_words(primes, a, w: int) -> np.ndarray:
+    """uint64[..., K, n]: every word of residue row i times (w mod q_i) mod q_i.  Weights within 8 of 0 modulo q_i stay in uint64
+    (8 q_i < 2^64), the others go through Python integers."""
+    a = np.asarray(a, dtype=np.uint64)
+    out = np.empty_like(a)
+    for i, q in enumerate(primes):
+        q, wm = int(q), int(w) % int(q)
+        row = a[..., i, :]
+        if wm <= 8:
+            out[..., i, :] = (row * np.uint64(wm)) % np.uint64(q)
+        elif q - wm <= 8:
+            neg = (row * np.uint64(q - wm)) % np.uint64(q)
+            out[..., i, :] = np.where(neg == 0, neg, np.uint64(q) - neg)
+        else:
+            out[..., i, :] = _u64(_obj(row) * wm % q)
+    return out
+
+
+def uncorrected_products(primes, a, w: int) -> np.ndarray:
+    """uint64[..., K, n]: the weighted residues as a Shoup product WITHOUT its last correction leaves them, in [0, 2 q_i):
+    r w - floor(r w' / 2^64) q_i with w = w mod q_i and w' = floor(w 2^64 / q_i).  The estimate of the quotient is one short where
+    the true residue is below about r q_i / 2^64 -- on small weighted residues such as 1 and 2, hardly ever on random ones."""
+    a = np.asarray(a, dtype=np.uint64)
+    out = np.empty_like(a)
+    for i, q in enumerate(primes):
+        q, wm = int(q), int(w) % int(q)
+        r = _obj(a[..., i, :])
+        out[..., i, :] = _u64(r * wm - ((r * ((wm << 64) // q)) >> 64) * q)
+    return out
+
+
+def fold_terms(primes, terms, weights, turned=None, events=None) -> np.ndarray:
+    """uint64[2][K][n]: sum_t (w_t mod q_i) terms[t] mod q_i in term order, the first term onto 0, as the kernels add:
+    raw = acc + weighted term, acc = raw - q_i if raw >= q_i.  turned "add": `>` for `>=` (a model that is WRONG at a raw sum of
+    exactly q_i and nowhere else); turned "product": the weighted residue left in [0, 2 q_i) (uncorrected_products).  events:
+    {name: int[K]} counters of ROTATION_SUM_EVENTS to add to."""
+    assert turned in (None, "add", "product"), turned
+    acc = np.zeros_like(np.asarray(terms[0], dtype=np.uint64))
+    qcol = np.array([int(q) for q in primes], dtype=np.uint64)[:, None]
+    last = len(terms) - 1
+    for t, (r, w) in enumerate(zip(terms, weights)):
+        r = np.asarray(r, dtype=np.uint64)
+        wr = uncorrected_products(primes, r, w) if turned == "product" else scale_words(primes, r, w)
+        raw = acc + wr
+        over = raw > qcol if turned == "add" else raw >= qcol
+        nxt = np.where(over, raw - qcol, raw)
+        if events is not None:
+            half = qcol >> np.uint64(1)
+            zero_w = np.array([int(w) % int(q) == 0 for q in primes])[:, None]
+            for name, hit in (("term 0", r == 0), ("term q - 1", r == qcol - 1), ("term 1", r == 1), ("term (q - 1) / 2", r == half),
+                              ("term (q + 1) / 2", r == half + 1), ("weighted 0", wr == 0), ("weighted q - 1", wr == qcol - 1),
+                              ("raw q", raw == qcol), ("raw q - 1", raw == qcol - 1), ("zero weight", (r != 0) & zero_w)):
+                events[name] += hit.sum(axis=(0, 2))
+            if t == last:
+                for name, hit in (("final 0", nxt == 0), ("final q - 1", nxt == qcol - 1), ("final 1", nxt == 1)):
+                    events[name] += hit.sum(axis=(0, 2))
+        acc = nxt
+    return acc
+
+
+def _solve_term(primes, T, acc, w: int, filler) -> np.ndarray:
+    """uint64[K][n]: the residue r with acc + (w mod q_i) r == T mod q_i; in a row where w = 0 mod q_i, `filler`'s row."""
+    out = np.array(filler, dtype=np.uint64)
+    diff = lin_mod(primes, [(1, T), (-1, acc)])
+    for i, q in enumerate(primes):
+        wm = int(w) % int(q)
+        if wm == 1:
+            out[i] = diff[i]
+        elif wm == int(q) - 1:
+            out[i] = np.where(diff[i] == 0, diff[i], np.uint64(q) - diff[i])
+        elif wm:
+            out[i] = _u64(_obj(diff[i]) * pow(wm, -1, int(q)) % int(q))
+    return out
+
+
+def _sum_target(primes, n: int, mode: str, t: int, shift: int) -> np.ndarray:
+    """uint64[2][K][n]: where the sum stands after term t.  ladder: q - 1, 0, q - 1, 0 in every word of polynomial 0 and the other
+    phase in polynomial 1 (an identity term in an odd place ends it on q - 1, never on a transparent 0)."""
+    if mode == "ladder":
+        hi, lo = constant(primes, n, lambda q: q - 1), constant(primes, n, 0)
+        return np.stack([hi, lo] if t % 2 == 0 else [lo, hi])
+    return pattern(primes, 2, n, shift)
+
+
+def rotation_sum_case(L: "Landing", steps, weights, mode: str, groups: int, galois: bool = False, pow2: bool = False):
+    """(sources uint64[groups * terms][2][K][n], expected uint64[groups][2][K][n], events {name: int[K]}): item g * terms + t is the
+    source of term t of group g; expected[g] = sum_t (w_t mod q_i) rotate(source, steps[t]) folded in term order (fold_terms), from
+    the landed values and the oracle's rotate((0, c1)) -- tests/test_landing_cpu.py shows that the oracle's rotations of the sources,
+    scaled and added, give exactly that.  weights None: all ones.  galois: the terms are Galois elements (1: the identity).  pow2: the
+    keys are the power-of-two holding.  Group g moves every pattern by g.
+
+    terms        polynomial 0 of every finished rotated term and both polynomials of every identity term on pattern(shift = t)
+    partial      the running sum after term t on pattern(shift = t): polynomial 0 after every term, polynomial 1 after every
+                 identity term.  In a row where w_t = 0 mod q_i the term adds 0 and the sum stays where it was.
+    ladder       the same with constant targets: the sums go q - 1, 0, q - 1, 0, the weighted terms q - 1, 1, q - 1, 1 and the raw
+                 sums q - 1, q, q - 1, q in every word
+    transparent  partial, and the last identity term of group TRANSPARENT_GROUP lands the FINAL polynomial 1 on all zeros
+    almost       the same on almost_zero
+    gathers      compared, not landed: random sources, but c0 and c1 of the first rotated term of every group cycle 0, q - 1, 1
+    random       random sources (the control of the turned model)"""
+    import zlib
+
+    assert mode in ROTATION_SUM_MODES, mode
+    steps = tuple(int(s) for s in steps)
+    terms = len(steps)
+    wts = (1,) * terms if weights is None else tuple(int(w) for w in weights)
+    assert len(wts) == terms
+    key = ("rotation sum", steps, wts, mode, groups, galois, pow2)
+
+    def make():
+        o, P, n, K = L.o, L.primes, L.n, L.K
+        gk = rotation_sum_keys(L, steps, galois, pow2)
+        rng = L.rng(zlib.crc32(repr(key).encode()))
+        ident = [_element(o, s, galois) == 1 for s in steps]
+        zero = np.zeros((K, n), dtype=np.uint64)
+        sources = np.zeros((groups * terms, 2, K, n), dtype=np.uint64)
+        expected = np.zeros((groups, 2, K, n), dtype=np.uint64)
+        events = {e: np.zeros(K, dtype=np.int64) for e in ROTATION_SUM_EVENTS}
+        for g in range(groups):
+            if mode in ("gathers", "random"):
+                src = random_residues(rng, P, (terms, 2), n)
+                if mode == "gathers":
+                    t0 = ident.index(False)
+                    src[t0] = np.stack([cycle(P, n, lambda q: [0, q - 1, 1]), cycle(P, n, lambda q: [1, 0, q - 1, 0, q - 1])])
+                vals = [_rotate(o, src[t], steps[t], gk, galois) for t in range(terms)]
+            else:
+                # the key-switch part of every rotated term: it does not depend on c0
+                c1 = {t: random_residues(rng, P, (), n) for t in range(terms) if not ident[t]}
+                R = {t: _rotate(o, np.stack([zero, c1[t]]), steps[t], gk, galois) for t in c1}
+                final1 = None  # (t, target): the identity term that lands the FINAL polynomial 1
+                if mode in ("transparent", "almost") and g == TRANSPARENT_GROUP:
+                    t1 = max(t for t in range(terms) if ident[t])
+                    assert all(wts[t1] % q for q in P), "the landing identity term needs an invertible weight in every row"
+                    rest = [(-1, scale_words(P, R[t][1], wts[t])) for t in range(t1 + 1, terms)]
+                    final1 = (t1, lin_mod(P, [(1, zero if mode == "transparent" else almost_zero(P, n))] + rest))
+                acc = np.zeros((2, K, n), dtype=np.uint64)
+                src, vals = [], []
+                for t in range(terms):
+                    shift = t + g
+                    filler = pattern(P, 2, n, shift)
+                    if mode == "terms":
+                        val = filler if ident[t] else np.stack([filler[0], R[t][1]])
+                    else:
+                        T = _sum_target(P, n, mode, t, shift)
+                        if final1 is not None and final1[0] == t:
+                            T[1] = final1[1]
+                        v0 = _solve_term(P, T[0], acc[0], wts[t], filler[0])
+                        val = np.stack([v0, _solve_term(P, T[1], acc[1], wts[t], filler[1]) if ident[t] else R[t][1]])
+                    src.append(val if ident[t] else land_rotation(o, gk, steps[t], c1[t], val[0], galois, R[t])[0])
+                    vals.append(val)
+                    acc = fold_terms(P, [acc, val], [1, wts[t]])
+            for t in range(terms):
+                sources[g * terms + t] = src[t]
+            expected[g] = fold_terms(P, vals, wts, events=events)
+        return sources, expected, events
+
+    return L.cached(key, make)

@@ -463,3 +463,157 @@ def test_weighted_sums_land_and_meet_every_event_in_every_row(pid):
         qm2 = np.array(P, dtype=np.uint64)[:, None] - 2
         ones_sum = LD.weighted_sum_case(L, (1, 1, 1))[1]
         assert (ones_sum[:, 0] == qm2).all() and (ones_sum[:, 2] == qm2).all()
+
+
+# ---- J: sums of rotations (tests/test_gpu_landing_rotate_sum.py) -------------------------------------------------------------
+ROTATION_SUM_SETS = ["P1", "P2", "P3", "P4", "P5", "S4096", "U1024", "W2048", "X8192"]
+CPU_GROUPS = 2
+
+
+def _oracle_scaled(o, ct, w):
+    """LD.scale_words of one rotated term; for 0 < |w| <= 3 also the oracle's own negate / add chain."""
+    out = LD.scale_words(o.primes, ct, w)
+    if 0 < abs(w) <= 3:
+        one = o.negate(ct) if w < 0 else ct
+        acc = one
+        for _ in range(abs(w) - 1):
+            acc = o.add(acc, one)
+        assert (np.asarray(acc) == out).all(), w
+    return out
+
+
+def _oracle_sum(L, sources, steps, weights, gk, galois, g):
+    """The oracle's rotate, scale and add chain of group g (the exception for a transparent sum switched off)."""
+    o = L.o
+    acc = None
+    for t, s in enumerate(steps):
+        term = _oracle_scaled(o, LD._rotate(o, sources[g * len(steps) + t], s, gk, galois), weights[t])
+        acc = term if acc is None else o.add(acc, term)
+    return acc
+
+
+@pytest.mark.parametrize("pid", ROTATION_SUM_SETS)
+def test_sums_of_rotations_land_and_meet_every_event_in_every_row(pid):
+    """Every step and weight vector of the set in every mode: the oracle's rotations of the crafted sources, scaled and added, are
+    `expected` on every word, the landed words are where the mode says, and the vectors together put every event of
+    LD.ROTATION_SUM_EVENTS in front of every residue row."""
+    L = landing(pid)
+    o, P, n, K = L.o, L.primes, L.n, L.K
+    if pid == "X8192":
+        assert n == 8192 and [q.bit_length() for q in L.key_primes] == [50, 30, 30, 50, 50] and K == 4
+    qm1 = np.array(P, dtype=np.uint64)[:, None] - 1
+    total = {e: np.zeros(K, dtype=np.int64) for e in LD.ROTATION_SUM_EVENTS}
+    o.throw_on_transparent = False
+    try:
+        for k, (name, steps, weights, galois, pow2) in enumerate(LD.rotation_sum_runs(L)):
+            gk = LD.rotation_sum_keys(L, steps, galois, pow2)
+            terms = len(steps)
+            wts = weights or (1,) * terms
+            ident = [LD._element(o, s, galois) == 1 for s in steps]
+            for mode in LD.rotation_sum_modes(k):
+                src, want, events = LD.rotation_sum_case(L, steps, weights, mode, CPU_GROUPS, galois, pow2)
+                assert src.shape == (CPU_GROUPS * terms, 2, K, n) and want.shape == (CPU_GROUPS, 2, K, n)
+                assert all((src[:, :, i] < q).all() for i, q in enumerate(P))  # canonical residues
+                print(pid, name, mode, {e: [int(v) for v in c] for e, c in events.items()})
+                for e in LD.ROTATION_SUM_EVENTS:
+                    total[e] += events[e]
+                for g in range(CPU_GROUPS):
+                    assert (_oracle_sum(L, src, steps, wts, gk, galois, g) == want[g]).all(), (pid, name, mode, g)
+                    last = terms - 1
+                    free = np.array([wts[last] % q != 0 for q in P])  # rows whose last weight has an inverse
+                    if mode == "terms":
+                        for t, s in enumerate(steps):
+                            r = LD._rotate(o, src[g * terms + t], s, gk, galois)
+                            pat = LD.pattern(P, 2, n, t + g)
+                            assert (r[0] == pat[0]).all() and (not ident[t] or (r[1] == pat[1]).all()), (pid, name, t, g)
+                    elif mode == "partial" or (mode in ("transparent", "almost") and g != LD.TRANSPARENT_GROUP):
+                        pat = LD.pattern(P, 2, n, last + g)
+                        assert (want[g, 0][free] == pat[0][free]).all() and (not ident[last] or (want[g, 1][free] == pat[1][free]).all())
+                    elif mode == "ladder":
+                        end = qm1 if last % 2 == 0 else np.zeros_like(qm1)
+                        assert (want[g, 0][free] == np.broadcast_to(end, (K, n))[free]).all(), (pid, name, g)
+                    elif mode == "transparent":
+                        assert not want[g, 1].any() and want[g, 0].any()
+                    elif mode == "almost":
+                        assert (want[g, 1] == LD.almost_zero(P, n)).all()
+                    elif mode == "gathers":
+                        t0 = ident.index(False)
+                        assert all(set(int(v) for v in src[g * terms + t0, p, i]) == {0, 1, q - 1} for p in range(2) for i, q in enumerate(P))
+                if mode == "ladder" and all(w % q for w in wts for q in P):  # every word: raw sums q - 1, q, q - 1, q
+                    words = CPU_GROUPS * n
+                    polys1 = [sum(1 for t in range(terms) if ident[t] and t <= u) > 0 for u in range(terms)]
+                    assert all(c >= words * (terms // 2) for c in events["raw q"]) and all(c >= words * ((terms + 1) // 2) for c in events["raw q - 1"]), (events, polys1)
+                if weights is not None and len(weights) == 4 and weights[1] in P and mode == "partial":  # the modulus-sized weight
+                    row = P.index(weights[1])
+                    assert events["zero weight"][row] > 0 and all(events["zero weight"][i] == 0 for i in range(K) if i != row), events["zero weight"]
+    finally:
+        o.throw_on_transparent = True
+    print(pid, "events over all vectors and modes:", {e: [int(v) for v in c] for e, c in total.items()})
+    zero_rows = np.array([any(w % q == 0 for r in LD.rotation_sum_runs(L) for w in (r[2] or ())) for q in P])
+    for e in LD.ROTATION_SUM_EVENTS:
+        assert ((total[e] > 0) == (zero_rows if e == "zero weight" else True)).all(), (pid, e, total[e])
+    # the oracle reports the landed sum transparent, and the almost transparent one not
+    name, steps, weights, galois, pow2 = LD.rotation_sum_runs(L)[0]
+    gk = LD.rotation_sum_keys(L, steps, galois, pow2)
+    src, want, _ = LD.rotation_sum_case(L, steps, weights, "transparent", CPU_GROUPS, galois, pow2)
+    with pytest.raises(RuntimeError, match="transparent"):
+        _oracle_sum(L, src, steps, (1,) * len(steps), gk, galois, LD.TRANSPARENT_GROUP)
+    src, want, _ = LD.rotation_sum_case(L, steps, weights, "almost", CPU_GROUPS, galois, pow2)
+    assert (_oracle_sum(L, src, steps, (1,) * len(steps), gk, galois, LD.TRANSPARENT_GROUP) == want[LD.TRANSPARENT_GROUP]).all()
+
+
+@pytest.mark.parametrize("pid", ["P1", "S4096", "X8192"])
+def test_the_turned_folds_differ_on_the_crafted_sums_only(pid):
+    """LD.fold_terms with one comparison turned gives other words than the reference on the crafted sums and the same words on a
+    random control of the same shape.  "add": `> q` for `>= q` -- every raw sum of exactly q_i that is the last one, or is followed by
+    a weighted 0, stays q_i.  "product": the weighted residue without the Shoup product's last correction, left in [0, 2 q_i); the
+    add's one subtraction repairs it unless the sum wraps as well, which the partial sums put in front of one thread in five at the
+    last term (the sum on q_i - 1, the weighted residue 2) and the ladder in front of every one.  The quotient estimate is one short
+    where the true residue is below about r q_i / 2^64, so a residue of 1 or 2 shows it at primes above 2^33 under a negative weight
+    (w mod q_i and r both of the size of q_i; with weight 1 the estimate is exact); on random words it shows with probability q_i / 2^64.  It is judged at S4096 (a 40-bit row:
+    shown on the crafted sums, 2^-24 per random word); at 50-bit primes the random control would meet it as well."""
+    L = landing(pid)
+    o, P = L.o, L.primes
+    for k in (0, 1):
+        name, steps, weights, galois, pow2 = LD.rotation_sum_runs(L)[k]
+        gk = LD.rotation_sum_keys(L, steps, galois, pow2)
+        wts = weights or (1,) * len(steps)
+        turns = ("add", "product") if k == 1 and pid == "S4096" else ("add",)
+        for mode in ("partial", "ladder", "random"):
+            src, want, events = LD.rotation_sum_case(L, steps, weights, mode, CPU_GROUPS, galois, pow2)
+            differ = dict.fromkeys(turns, 0)
+            for g in range(CPU_GROUPS):
+                vals = [LD._rotate(o, src[g * len(steps) + t], s, gk, galois) for t, s in enumerate(steps)]
+                assert (LD.fold_terms(P, vals, wts) == want[g]).all()
+                for turn in turns:
+                    differ[turn] += int((LD.fold_terms(P, vals, wts, turned=turn) != want[g]).sum())
+            print(pid, name, mode, "words where the turned fold differs:", differ, "raw sums of exactly q:", [int(v) for v in events["raw q"]])
+            if mode == "random":
+                assert not any(differ.values()) and not events["raw q"].any()
+            else:
+                assert all(d >= CPU_GROUPS * L.n // 5 for d in differ.values()) and (events["raw q"] > 0).all()
+
+
+def test_chain_terms_land_under_the_power_of_two_keys():
+    """land_rotation through the oracle's NAF chains over the holding "P" of tests/test_gpu_rotation_steps.py (same parameters): 11 and
+    -13 (three hops, mixed signs), 2045 and 1707 (the skipped part of n / 2), and a step with a key of its own."""
+    from tests.bfv_helpers import params
+
+    L = landing("P1")
+    o, P, n = L.o, L.primes, L.n
+    pn, pprimes, pt = params("default_4096_16")
+    assert (pn, [int(p) for p in pprimes], int(pt)) == (n, L.key_primes, L.t)
+    gk = LD.rotation_sum_keys(L, LD.STEPS_CHAIN, pow2=True)
+    assert len(gk) == 2 * 11 + 1 - 1  # (the steps 1024 and -1024 share their element)
+    rng = L.rng(300)
+    for k, step in enumerate((11, -13, 2045, 1707, 1, -1024)):
+        assert (o.galois_elt_from_step(step) in gk) == (step in (1, -1024))
+        T0 = LD.pattern(P, 1, n, k)[0]
+        ct, want = LD.land_rotation(o, gk, step, LD.random_residues(rng, P, (), n), T0)
+        got = o.rotate_rows(ct, step, gk)
+        assert (got == want).all() and (got[0] == T0).all(), step
+    # the Galois-element form of the same builder is land_galois
+    elt = 2 * n - 5
+    c1 = LD.random_residues(rng, P, (), n)
+    a, b = LD.land_rotation(o, L.galois_keys([elt]), elt, c1, T0, galois=True), LD.land_galois(o, L.galois_keys([elt]), elt, c1, T0)
+    assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
