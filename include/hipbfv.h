@@ -279,6 +279,9 @@ long hipbfv_PublicKey_Assign(void *key, void *context, const uint64_t *host_data
 long hipbfv_Encryptor_SetSeed(void *encryptor, uint64_t seed);                      /* reproducible runs (tests) */
 long hipbfv_KeyGenerator_SetSeed(void *key_generator, uint64_t seed);               /* keys created afterwards */
 long hipbfv_KeyGenerator_CreateSeeded(void *context, uint64_t seed, void **key_generator); /* reproducible secret */
+/* TEST ONLY: sigma_g(secret) in coefficient form, u64[K+1][N], as the Galois key of galois_elt takes it up before its
+ * forward transform (every word canonical: a sign-flipped 0 is 0) */
+long hipbfv_debug_keygen_galois_secret(void *key_generator, uint32_t galois_elt, uint64_t *host_out);
 
 /* Host-only helpers of the SEAL 4.0 wire format (no device access; used by the CPU tests against the
  * reference's binary fixtures): parms_id = BLAKE2b-256([scheme=1, n, primes..., t]); decode/encode one object. */

@@ -170,6 +170,7 @@ _SIGNATURES = {
     "KeyGenerator_CreateGaloisKeysAll": [vp, C.c_bool, vpp],
     "KeyGenerator_CreateGaloisKeysFromSteps": [vp, u64, C.POINTER(C.c_int), C.c_bool, vpp],
     "hipbfv_KeyGenerator_SetSeed": [vp, u64], "hipbfv_KeyGenerator_CreateSeeded": [vp, u64, vpp],
+    "hipbfv_debug_keygen_galois_secret": [vp, C.c_uint32, u64p],
     "BatchEncoder_Create": [vp, vpp], "BatchEncoder_Destroy": [vp],
     "BatchEncoder_Encode1": [vp, u64, u64p, vp], "BatchEncoder_Encode2": [vp, u64, C.POINTER(C.c_int64), vp],
     "BatchEncoder_Decode1": [vp, vp, u64p, u64p, vp], "BatchEncoder_Decode2": [vp, vp, u64p, C.POINTER(C.c_int64), vp],

@@ -4368,6 +4368,23 @@ long KeyGenerator_CreateGaloisKeysAll(void* h, bool save_seed, void** galois_key
   }
   return KeyGenerator_CreateGaloisKeysFromElts(h, elts.size(), elts.data(), save_seed, galois_keys);
 HIPBFV_END
+// TEST ONLY: sigma_g(s) as keygen_galois_kernel leaves it, u64[K+1][N] in coefficient form -- the w of the Galois key for
+// galois_elt BEFORE its forward transform.  The transform accepts a word equal to q_i and canonicalises its output, so a
+// sign-flipped 0 stored as q_i shows in no key; it shows here (tests/test_gpu_keygen_model.py).
+long hipbfv_debug_keygen_galois_secret(void* h, uint32_t galois_elt, uint64_t* host_out) HIPBFV_BEGIN
+  KeyGenObj* g = as<KeyGenObj>(h, kMagicKeyGen);
+  if (!g || !host_out) return HIPBFV_E_POINTER;
+  const size_t words = (size_t)g->ctx->KK() * g->ctx->n();
+  u64* buf = g_buffers.get(words);
+  if (!buf) return from_status(kOutOfMemory);
+  hipStream_t s = thread_stream();
+  const int st = g->ev->keygen_galois_poly(g->sk_coeff->dev, galois_elt, buf, s);
+  long hr = sync_stream(s);
+  if (st) hr = from_status(st);
+  if (hr == HIPBFV_S_OK && hipMemcpy(host_out, buf, words * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) hr = from_status(kHipError);
+  g_buffers.put(buf, words);
+  return hr;
+HIPBFV_END
 
 }  // extern "C"
 #pragma GCC visibility pop

@@ -424,6 +424,7 @@ class Evaluator {
   int crt_compose(const u64* consts, u32 kc, const u64* in, u64* out, u32 polys, hipStream_t s);
   int crt_decompose(u32 kc, const u64* in, u64* out, u32 polys, hipStream_t s);
   int keygen_kswitch(const RngSeed& seed, u64 stream, const u64* sk_coeff, const u64* sk_ntt, u32 galois_elt, u64* key, hipStream_t s);
+  int keygen_galois_poly(const u64* sk_coeff, u32 galois_elt, u64* out, hipStream_t s);
   // watch_zero: an all-zero plaintext raises the transparent-result status of the enclosing WatchScope -- 1: the plaintexts are
   // the items of a batch (item = index), 2: they are shared by the whole batch (item 0): the graph executor's transform-domain
   // sums never form the single product SEAL's multiply_plain would have refused

@@ -151,6 +151,17 @@ int Evaluator::keygen_zero_encryptions(const RngSeed& seed, u64 stream, const u6
   return kOk;
 }
 
+// out[KK][N] = sigma_g(s) in coefficient form: the w of a Galois key before its transform
+int Evaluator::keygen_galois_poly(const u64* sk_coeff, u32 galois_elt, u64* out, hipStream_t s) {
+  const DevCtx& h = ctx_->host();
+  if (h.logn > 15) return kUnsupported;
+  if (!(galois_elt & 1) || galois_elt >= 2 * h.n) return kInvalidArg;
+  u64 inv = 1;
+  for (int i = 0; i < 6; i++) inv = inv * (2 - (u64)galois_elt * inv);
+  HC_CHECK(launch_keygen_galois(ctx_->dev(), h.n, h.KK, sk_coeff, out, (u32)(inv & (2 * h.n - 1)), s));
+  return kOk;
+}
+
 // relin: w = s^2; galois element g: w = NTT(sigma_g(s)).  key: u64[K][2][KK][N]
 int Evaluator::keygen_kswitch(const RngSeed& seed, u64 stream, const u64* sk_coeff, const u64* sk_ntt, u32 galois_elt, u64* key, hipStream_t s) {
   const DevCtx& h = ctx_->host();
@@ -162,10 +173,7 @@ int Evaluator::keygen_kswitch(const RngSeed& seed, u64 stream, const u64* sk_coe
   if (galois_elt == 0) {
     HC_CHECK(launch_keygen_square(ctx_->dev(), n, KK, sk_ntt, w, s));
   } else {
-    if (!(galois_elt & 1) || galois_elt >= 2 * n) return kInvalidArg;
-    u64 inv = 1;
-    for (int i = 0; i < 6; i++) inv = inv * (2 - (u64)galois_elt * inv);
-    HC_CHECK(launch_keygen_galois(ctx_->dev(), n, KK, sk_coeff, w, (u32)(inv & (2 * n - 1)), s));
+    if (int st = keygen_galois_poly(sk_coeff, galois_elt, w, s)) return st;
     HC_CHECK(launch_ntt(ctx_->dev(), h.tw_fwd, h.logn, w, KK, range_plan(KK), false, 0, s));
   }
   return keygen_zero_encryptions(seed, stream, sk_ntt, w, key, h.K, s);

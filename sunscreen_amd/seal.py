@@ -764,6 +764,13 @@ class KeyGenerator:
         k._h = C.c_void_p()
         return k
 
+    def debug_galois_secret(self, galois_elt: int) -> np.ndarray:
+        """hipbfv extension (tests): sigma_g(secret) in coefficient form, uint64[K+1][N], as the Galois key of galois_elt takes
+        it up before its forward transform."""
+        out = np.empty((self._ctx.KK, self._ctx.poly_modulus_degree), dtype=np.uint64)
+        _check(_lib.load().hipbfv_debug_keygen_galois_secret(self._h, int(galois_elt), out.ctypes.data_as(_lib.u64p)))
+        return out
+
     def secret_key(self) -> SecretKey:
         k = self._adopt(SecretKey)
         _check(_lib.load().KeyGenerator_SecretKey(self._h, C.byref(k._h)))

@@ -6,9 +6,9 @@ what the kernel's OWN output must be in every thread and solve for the operand t
 Encryption.  The sampled u and e depend on (seed, counter, coefficient) alone, never on the key, and the public key is the caller's.
 Once u and e are known, pk_c = NTT(T_c - e_c) / NTT(u) pointwise in every key-level residue makes pk_c (*) u + e_c = T_c for any
 target T_c (the host checks that NTT(u) has no zero entry).  u is recomputed from tests/rng_ref.py; e is HARVESTED from the
-component-returning call on the device (the Gaussian is float arithmetic -- logf, cospif -- and stays pinned statistically,
-tests/test_gpu_client.py; what is asserted of e is |e| <= 19, the sampler's clip, and that every residue row holds the same small
-integer).  Given u and e the encryption is stated twice in Python integers: finish_rns, SEAL's divide_and_round_q_last residue by
+component-returning call on the device (the Gaussian is float arithmetic -- logf, cospif: tests/test_gpu_keygen_model.py holds it
+against a float64 model; what is asserted of e HERE is |e| <= 19, the sampler's clip, and that every residue row holds the same
+small integer).  Given u and e the encryption is stated twice in Python integers: finish_rns, SEAL's divide_and_round_q_last residue by
 residue followed by + (Delta mod q_j) m + r, and finish_integers, floor((X + floor(q_sp / 2)) / q_sp) mod q_j of the CRT lift X.
 The two share nothing but the key-level residues.
 

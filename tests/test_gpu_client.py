@@ -1,8 +1,10 @@
 """The steps either side of the evaluator on the device: BatchEncoder, Decryptor, Encryptor.
 
-BatchEncoder and Decryptor are deterministic: bit-exact against the oracle.  Encryptor is randomised (the reference
-pins its sampler only statistically): ciphertexts must decrypt to the message under the ORACLE's decryptor with the
-noise budget of a fresh SEAL encryption, and the sampled polynomials must have the right distribution.
+BatchEncoder and Decryptor are deterministic: bit-exact against the oracle.  Encryptor is randomised (the reference's
+own stream is not reproduced): ciphertexts must decrypt to the message under the ORACLE's decryptor with the
+noise budget of a fresh SEAL encryption, and the sampled polynomials must have the right distribution.  The sampler's
+draws themselves -- every word of generated keys, the Gaussian of keys and encryptions against a float64 model of it --
+are held in tests/test_gpu_keygen_model.py.
 Reference interfaces: seal_fhe/src/encoder.rs:50-215, seal_fhe/src/encryptor_decryptor.rs:140-260,596-690.
 """
 import hashlib

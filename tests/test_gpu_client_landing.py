@@ -6,8 +6,8 @@ A / B  public-key encryption with a crafted public key: the divide-and-round by 
        the data rows and the words after the division and after the plaintext addition on 0, q_j - 1 and 1, on the fused route
        (the batched encrypt and the handle's encrypt: encrypt_finish_kernel) and on the component-returning route
        (add_key_level_kernel -> ks_moddown_kernel -> add_plain).  u is recomputed from tests/rng_ref.py and must equal the device's
-       in every coefficient; e is harvested from the device (the Gaussian is float arithmetic: its exact values stay pinned
-       statistically in tests/test_gpu_client.py) and is asserted small, |e| <= 19, the one inequality of this file.
+       in every coefficient; e is harvested from the device (the Gaussian is float arithmetic: its values are held against a
+       float64 model in tests/test_gpu_keygen_model.py) and is asserted small, |e| <= 19, the one inequality of this file.
 C      a batch against handle calls (first_op, a chunk boundary inside the batch, the shared plaintext, n = 32768) and the sampling
        counter across 2^32.
 D      PolynomialArray's compose and decompose on crafted residues, every coefficient.  Decompose only ever sees limbs that compose
